@@ -18,13 +18,30 @@ Workloads (`--workload`, default `auto`):
   c2   configs[2] shape: 6,000,000 Gaussians sharded over the N ranks, 1920x1080, bsz 1: ONE image split into N
        row bands (Grendel's pixel partition), dynamic load balancing on.                      <- auto at N > 1
   c4   configs[4] shape: 40,000,000 Gaussians sharded over N ranks, 3840x2160, bsz 1, image split N ways
-       (reported beside c2 in `extra_workloads` at N > 1 unless --no-extra).
+       (reported beside c2 in `extra_workloads` at N > 1 with --full, unless --no-extra).
   weak bsz = N cameras per step on the c1 scene sharded N ways (every rank renders a whole image).
-At N > 1 the total work of c2 / c4 does not depend on N ("scaling": "strong"); every line also carries
+At N > 1 the total work of c2 / c4 does not depend on N ("scaling": "strong"); every --full line also carries
 `same_workload_1gpu` -- the SAME scene and camera on one GPU, measured in the same run on rank 0's device -- and
 `speedup_vs_1gpu`, which is the pixel-partition scaling north_star asks about.
 
-One JSON line is printed by rank 0; besides the contract fields it carries
+A plain run does only what the headline figure needs: set-up, W warmup steps, ONE timed region of exactly K steps,
+the outputs of the last timed step if `--dump-outputs DIR` is given, and one JSON line with the contract fields
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) and `timing`.
+  --dump-outputs DIR : right after the timed region, what its LAST step computed, as DIR/<name>.npy (float32 /
+                       float64, < 64 MB in all): `loss` (float64 [1]); `images` [B, 3, H, W] -- the rendered images of
+                       the batch, or a fixed seeded sample of 8 Mi of their elements (in flat order) when larger; and the
+                       six parameters after the optimizer step (`xyz`, `features_dc`, `features_rest`, `opacity`,
+                       `scaling`, `rotation`) at a fixed seeded sample of 65536 Gaussian rows (sorted; all rows when
+                       fewer) -- rank 0's shard at N > 1.  Inputs are a function of the arguments only (seeded scene,
+                       cameras and ground-truth images), so two builds can be compared output for output; on one GPU
+                       the outputs are reproducible from run to run (include/gsraster.h: gsr_render_backward_seg_d).
+                       Eager loop only: refused with --graph on, whose replays write the graph's own output tensors.
+Everything else is measured with `--full` only: the repeated timed regions (`--repeats`), the instrumented replay with
+per-kernel events and `roofline`, the two-kernel optimizer leg, the forward-only render legs (`--render-steps`), the
+extra workloads, the CPU baseline and, at N > 1, the pipelined / same-workload-1-GPU / hipGraph legs.  An explicit
+`--repeats` or `--render-steps` is honoured in a plain run as well.
+
+With --full, the JSON line printed by rank 0 carries besides the contract fields
   kernels      : every HIP kernel group of the step with HIP-event time (recorded on the launch stream) and the
                  algorithmic bytes OF THE SAME LAUNCHES (each launch's own N / P / D / Px).  The events are recorded in
                  an instrumented REPLAY of the timed steps (same cameras, same order, same sizes) right after the contract
@@ -250,6 +267,19 @@ def run_guarded_leg(n, argv, timeout_s):
             "stderr_tail": (se or "")[-600:]}
 
 
+def without_dump(argv):
+    """argv minus --dump-outputs DIR: the outputs of a run are its headline region's, never a leg's"""
+    out, skip = [], False
+    for x in argv:
+        if skip:
+            skip = False
+        elif x == "--dump-outputs":
+            skip = True
+        elif not x.startswith("--dump-outputs="):
+            out.append(x)
+    return out
+
+
 def brief_leg(d):
     """the fields of a leg's line that the parent line carries"""
     if d is None or "error" in d:
@@ -265,6 +295,46 @@ def percentile(xs, q):
     k = (len(xs) - 1) * q
     lo, hi = int(math.floor(k)), int(math.ceil(k))
     return xs[lo] + (xs[hi] - xs[lo]) * (k - lo)
+
+
+DUMP_IMAGE_ELEMS = 8 << 20  # images: all elements up to 32 MB, else a seeded sample of this many
+DUMP_ROWS = 65536            # parameters: a seeded sample of this many Gaussian rows (59 floats each: 15.5 MB)
+
+
+def collect_outputs(model, state):
+    """-> {name: numpy array} of what the last step returned to its caller (see the module docstring), on the host"""
+    import numpy as np
+
+    out = {"loss": np.asarray([float(state["loss"])], dtype=np.float64)}
+    # per camera a [3, H, W] image; at N > 1 a rank that renders no part of a camera has None (or a scalar stand-in)
+    # there, which is dumped as zeros
+    full = [im for im in state["images"] if im is not None and im.dim() == 3]
+    imgs = torch.stack([im.detach().float() if im is not None and im.dim() == 3 else torch.zeros_like(full[0])
+                        for im in state["images"]]) if full else torch.zeros(0)
+    flat = imgs.reshape(-1)
+    if flat.numel() > DUMP_IMAGE_ELEMS:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(flat.numel(), generator=g)[:DUMP_IMAGE_ELEMS].sort().values
+        out["images"] = flat[idx.to(flat.device)].cpu().numpy().astype(np.float32)
+    else:
+        out["images"] = imgs.cpu().numpy().astype(np.float32)
+    n = int(model._xyz.shape[0])
+    rows = None
+    if n > DUMP_ROWS:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values
+        rows = rows.to(model._xyz.device)
+    for name in ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation"):
+        p = getattr(model, "_" + name).detach()
+        out[name] = (p if rows is None else p[rows]).float().cpu().numpy()
+    return out
+
+
+def write_outputs(outs, d):
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    for name, arr in outs.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
 
 
 def densify_leg(a, model, opt, train_step, timed, state, steps, dgr):
@@ -373,8 +443,9 @@ def densify_leg(a, model, opt, train_step, timed, state, steps, dgr):
 
 
 def run_workload(a, name, world, rank, dev, steps, warmup, repeats, render_steps, single_view=False,
-                 collect_kernels=True, two_kernel_leg=None):
-    """-> dict of measurements of one workload on the current process group view (world ranks)"""
+                 collect_kernels=True, two_kernel_leg=None, dump_dir=None):
+    """-> dict of measurements of one workload on the current process group view (world ranks); dump_dir: write the
+    outputs of the timed region's last step there (rank 0)"""
     import diff_gaussian_rasterization as dgr
     import synthetic_scene as S
     import utils.general_utils as utils
@@ -420,6 +491,7 @@ def run_workload(a, name, world, rank, dev, steps, warmup, repeats, render_steps
     opt = FusedAdam(model.param_groups(), lr=0.0, eps=1e-15, fuse_backward=not a.no_fuse_backward,
                     grad_scale=1.0 / bsz)
     state = {"it": 0, "sizes": None}
+    dump = bool(dump_dir) and rank == 0
 
     def batch():
         s = (state["it"] * bsz) % n_views
@@ -468,6 +540,8 @@ def run_workload(a, name, world, rank, dev, steps, warmup, repeats, render_steps
             cam.original_image = None
         state["sizes"] = pkg["gpui_to_gpuj_imgk_size"]
         state["loss"] = loss
+        if dump:
+            state["images"] = images
         _ph("tail", t)
         return loss
 
@@ -566,6 +640,12 @@ def run_workload(a, name, world, rank, dev, steps, warmup, repeats, render_steps
         host_phases.clear()  # (diagnostics: the timed region and what follows only, not the cold steps)
     it0 = state["it"]
     dt = timed(train_step, steps)  # THE timed region of the contract: exactly `steps` steps between two fences
+    if dump:  # what the region's last step computed, before anything below steps the model again
+        if graphed is not None:
+            graphed.validate()
+        torch.cuda.synchronize()
+        write_outputs(collect_outputs(model, state), dump_dir)
+        state["images"] = None
     # Per-kernel HIP events: an instrumented REPLAY of the same steps (same cameras in the same order, hence the same
     # launches with the same sizes) right after the contract region.  Sixteen event packets per iteration cost ~5 % of
     # the step (measured: 1.40 against 1.32 ms), so they are kept out of the region `value` is computed from; the
@@ -782,12 +862,26 @@ def run_workload(a, name, world, rank, dev, steps, warmup, repeats, render_steps
     return out
 
 
+def resolve_run(a):
+    """the defaults that depend on --full: a plain run measures ONE region of exactly --steps steps and nothing else
+    (no repeats, render legs, extra workloads, CPU baseline or multi-GPU legs); an explicit --repeats / --render-steps
+    holds either way"""
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    if a.render_steps is None:
+        a.render_steps = 20 if a.full else 0
+    if not a.full:
+        a.no_extra = a.no_cpu_baseline = a.no_legs = a.no_1gpu_leg = True
+    return a
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps; value = the first one")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps; value = the first one (default: 5 with --full, else 1)")
     ap.add_argument("--workload", default="auto", choices=["auto"] + list(WORKLOADS))
     ap.add_argument("--gaussians", type=int, default=0, help="override the workload's Gaussian count")
     ap.add_argument("--width", type=int, default=0)
@@ -823,12 +917,21 @@ def main():
                          "the load balancer; the partition is frozen in between (0, default: every iteration feeds it -- "
                          "replays through their device timestamps)")
     ap.add_argument("--no-1gpu-leg", action="store_true", help="N > 1: skip the same-workload single-GPU leg")
-    ap.add_argument("--render-steps", type=int, default=20, help="forward-only views/sec leg (untimed by driver)")
+    ap.add_argument("--render-steps", type=int, default=None,
+                    help="forward-only views/sec leg (untimed by driver; default: 20 with --full, else 0)")
     ap.add_argument("--densify-every", type=int, default=0,
                     help="also time the steps with the densification statistics every iteration and densify_and_prune "
                          "every N-th (densification.py:5-86 of the reference): reported as `densification`")
     ap.add_argument("--pmc-calib", action="store_true", help="also run a 256 MiB streaming multiply (PMC calibration)")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: repeated regions, per-kernel events and roofline, the "
+                         "two-kernel optimizer leg, render legs, extra workloads, CPU baseline, multi-GPU legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
+    a = resolve_run(ap.parse_args())
+    if a.dump_outputs and a.graph == "on":
+        # (replays write the captured body's static outputs, not the tensors the eager run of the body left behind)
+        ap.error("--dump-outputs takes the outputs of the eager loop: it cannot be combined with --graph on")
 
     import utils.general_utils as utils
 
@@ -847,8 +950,8 @@ def main():
             "steps": a.steps, "warmup": a.warmup, "higher_is_better": True, "data": "synthetic", "dtype": "f32",
             "error": main_leg["error"], "stderr_tail": main_leg.get("stderr_tail")}
         if not a.no_legs and a.graph == "off":
-            g = run_guarded_leg(a.gpus, argv + ["--leg-child", "--graph", "on", "--no-extra", "--no-1gpu-leg",
-                                                "--repeats", "1", "--render-steps", "0"], a.leg_timeout)
+            g = run_guarded_leg(a.gpus, without_dump(argv) + ["--leg-child", "--graph", "on", "--no-extra", "--no-1gpu-leg",
+                                                              "--repeats", "1", "--render-steps", "0"], a.leg_timeout)
             out["graph_leg"] = brief_leg(g)
         print(json.dumps(out), flush=True)
         sys.exit(0 if "error" not in main_leg else 1)
@@ -867,7 +970,8 @@ def main():
 
         set_balance_timing(a.balance_timing)
     name = a.workload if a.workload != "auto" else ("c1" if world == 1 else "c2")
-    main_res = run_workload(a, name, world, rank, dev, a.steps, a.warmup, a.repeats, a.render_steps)
+    main_res = run_workload(a, name, world, rank, dev, a.steps, a.warmup, a.repeats, a.render_steps,
+                            collect_kernels=a.full, two_kernel_leg=a.full and a.repeats > 1, dump_dir=a.dump_outputs)
     legs = {}
     legs_wanted = world > 1 and not a.no_legs and a.graph == "off" and (not a.leg_child or a.with_pipelined_leg)
     if legs_wanted and a.balance_timing == "exact":
@@ -972,8 +1076,8 @@ def main():
     kern = main_res["kernels"]
     dom = max(kern, key=lambda k: kern[k]["avg_ms"] * kern[k]["launches"]) if kern else None
     roofline = None
-    src = source_hash()
-    pmc, pmc_note = load_pmc(src)
+    src = source_hash() if a.full else None
+    pmc, pmc_note = load_pmc(src) if a.full else (None, None)
     for kname, kv in kern.items():  # measured HBM bytes (PMC, separate rocprofv3 passes of this command) per kernel
         pk_ = (pmc or {}).get("kernels", {}).get(kname, {})
         if pk_.get("hbm_bytes_per_launch") and pk_.get("avg_ms"):
@@ -1085,6 +1189,10 @@ def main():
         "reference_published": {"a100_bicycle_1gpu_images_per_s": 16.6, "note": "README.md:342 of the reference; "
                                 "other hardware, real data at 1237x822 -- not comparable, hence vs_baseline null"},
     }
+    if not a.full:  # not measured in a plain run
+        for k in ("kernels", "roofline", "kernels_region_ms_per_step") + (
+                ("rendered_views_per_sec", "rendered_views") if a.render_steps <= 0 else ()):
+            del out[k]
     if "exchange" in main_res:
         out["exchange"] = main_res["exchange"]
     if one_gpu is not None:
@@ -1137,8 +1245,8 @@ def main():
             pass
         torch.cuda.empty_cache()
         argv = [x for x in sys.argv[1:] if x not in ("--with-pipelined-leg",)]
-        g = run_guarded_leg(world, argv + ["--leg-child", "--graph", "on", "--no-extra", "--no-1gpu-leg", "--repeats", "1",
-                                           "--render-steps", "0"], a.leg_timeout)
+        g = run_guarded_leg(world, without_dump(argv) + ["--leg-child", "--graph", "on", "--no-extra", "--no-1gpu-leg",
+                                                         "--repeats", "1", "--render-steps", "0"], a.leg_timeout)
         out["graph_leg"] = brief_leg(g)
     print(json.dumps(out), flush=True)
 

@@ -476,13 +476,14 @@ constexpr int MB = 8;      // entries per MFMA batch: rows 0-7 of the 16 x 16 re
 constexpr int MSTR = 66;   // row stride of the (q, w) matrix in 8-byte elements: phase A writes and phase B reads conflict-free
 
 // segment `sidx` of tile `tile`: the list entries [sidx * SEG_LEN, next boundary with a checkpoint or the end)
+template <typename Acc>
 __device__ __forceinline__ void
 composite_backward_segment(const int tile, const int sidx, int W, int H, int gx, const int2 *__restrict__ ranges,
                            const uint32_t *__restrict__ point_list, const float2 *__restrict__ means2D,
                            const float4 *__restrict__ conic_opacity, const float *__restrict__ rgb,
                            const uint8_t *__restrict__ compute_locally, const float *__restrict__ bg,
                            const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
-                           const float *__restrict__ dL_dpixels, float *__restrict__ dL_record,
+                           const float *__restrict__ dL_dpixels, Acc *__restrict__ dL_record,
                            const float *__restrict__ out_color, const SegWs &seg) {
     if (!compute_locally[tile]) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -738,7 +739,7 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
             if (idx < 576) {
                 const float val = sout[10 * e + col];
 #ifndef GSR_ABL_NOATOMIC
-                if (val != 0.f) atomicAdd(dL_record + 9 * (size_t)__float_as_uint(sout[10 * e + 9]) + col, val);
+                if (val != 0.f) atomicAdd(dL_record + 9 * (size_t)__float_as_uint(sout[10 * e + 9]) + col, (Acc)val);
 #else
                 asm volatile("" ::"v"(val));
 #endif
@@ -754,13 +755,14 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
     }
 }
 
+template <typename Acc>
 __global__ void __launch_bounds__(256, 4)  // 4 waves per SIMD: <= 128 VGPRs (LDS admits 4 workgroups per CU)
 composite_backward_kernel(int W, int H, int gx, int tiles, const int2 *__restrict__ ranges,
                           const uint32_t *__restrict__ point_list, const float2 *__restrict__ means2D,
                           const float4 *__restrict__ conic_opacity, const float *__restrict__ rgb,
                           const uint8_t *__restrict__ compute_locally, const float *__restrict__ bg,
                           const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
-                          const float *__restrict__ dL_dpixels, float *__restrict__ dL_record,
+                          const float *__restrict__ dL_dpixels, Acc *__restrict__ dL_record,
                           const float *__restrict__ out_color, const SegWs seg, int band_first, int band_tiles) {
     // workgroups [0, nstatic): segment 0 of every tile (of the band, when the caller named it: see K8), XCD-contiguous
     // spans.  The others are persistent workers: they take the segments K8 queued (their number is only known on the
@@ -860,14 +862,24 @@ int gsr_launch_composite_forward(int P, int W, int H, const int32_t *ranges, con
     return 0;
 }
 
+// the fp64 sums of K10 rounded once to the fp32 record (gsr_render_backward_seg_d)
+__global__ void record_from_f64_kernel(const double *__restrict__ acc, float *__restrict__ rec, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) rec[i] = (float)acc[i];
+}
+
 int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
                                   const float *means2D, const float *conic_opacity, const float *rgb,
                                   const uint8_t *compute_locally, const float *bg, const float *final_T,
                                   const int32_t *n_contrib, const float *dL_dpixels, float *dL_record,
                                   const float *out_color, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
-                                  int record_is_zero, hipStream_t stream) {
-    // (record_is_zero: the forward launch cleared it, gsr_render_forward_seg_z)
-    if (!record_is_zero) GSR_HIP(hipMemsetAsync(dL_record, 0, sizeof(float) * 9 * (size_t)P, stream));
+                                  int record_is_zero, hipStream_t stream, double *acc64) {
+    // (record_is_zero: the forward launch cleared the buffer K10 adds into -- the record, or acc64 when given --
+    // gsr_render_forward_seg_z; acc64: [P,9] fp64 sums, rounded once to the record afterwards, which is written whole)
+    if (!record_is_zero) {
+        if (acc64) GSR_HIP(hipMemsetAsync(acc64, 0, sizeof(double) * 9 * (size_t)P, stream));
+        else GSR_HIP(hipMemsetAsync(dL_record, 0, sizeof(float) * 9 * (size_t)P, stream));
+    }
     if (P == 0) return 0;
     const int gx = (W + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (H + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
     // row_lo == -1: `row_hi` tile rows are a CAPACITY, the band is read from the device (see composite_forward_kernel)
@@ -881,11 +893,22 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
     // walks the queued segments again (rearming it inside the kernel cost K10 its 128-register budget: 196 B of spills,
     // +20 % on every launch; this is a 4-byte fill on the thin-band path only)
     if (seg_ws) GSR_HIP(hipMemsetAsync(reinterpret_cast<char *>(seg_ws) + sizeof(uint32_t), 0, sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(composite_backward_kernel, dim3((band ? band_tiles : gx * gy) + (seg_ws ? SEG_WORKERS : 0)),
-                       dim3(256), 0, stream, W, H, gx, gx * gy, reinterpret_cast<const int2 *>(ranges), point_list,
-                       reinterpret_cast<const float2 *>(means2D), reinterpret_cast<const float4 *>(conic_opacity), rgb,
-                       compute_locally, bg, final_T, n_contrib, dL_dpixels, dL_record, out_color, seg, band_first,
-                       band_tiles);
+    const dim3 grid((band ? band_tiles : gx * gy) + (seg_ws ? SEG_WORKERS : 0));
+    if (acc64) {
+        hipLaunchKernelGGL(composite_backward_kernel<double>, grid, dim3(256), 0, stream, W, H, gx, gx * gy,
+                           reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
+                           reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
+                           dL_dpixels, acc64, out_color, seg, band_first, band_tiles);
+        GSR_LAUNCH_CHECK();
+        const size_t n = 9 * (size_t)P;
+        hipLaunchKernelGGL(record_from_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, acc64,
+                           dL_record, n);
+    } else {
+        hipLaunchKernelGGL(composite_backward_kernel<float>, grid, dim3(256), 0, stream, W, H, gx, gx * gy,
+                           reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
+                           reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
+                           dL_dpixels, dL_record, out_color, seg, band_first, band_tiles);
+    }
     GSR_LAUNCH_CHECK();
     return 0;
 }

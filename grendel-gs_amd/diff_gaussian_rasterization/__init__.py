@@ -1028,13 +1028,15 @@ class _RenderGaussians(torch.autograd.Function):
                 seg_bytes = int(lib.gsr_render_seg_bytes(W, H))
                 seg_ws = torch.empty((seg_bytes,), dtype=torch.uint8, device=dev)
             lists = [point_list]  # (a list: a late pair count may replace the point_list, see settle below)
-            # K10's [P,9] gradient record (means2D 0:2, rgb 2:5, conic_opacity 5:9) is allocated HERE when a backward can
-            # follow, and cleared by K8's own workgroups (include/gsraster.h: gsr_render_forward_seg_z) instead of by a
-            # 36 MB fill launch at the head of the backward
-            record = None
+            # K10's [P,9] gradient record (means2D 0:2, rgb 2:5, conic_opacity 5:9) and the [P,9] fp64 sums it is rounded
+            # from are allocated HERE when a backward can follow; the sums are cleared by K8's own workgroups
+            # (include/gsraster.h: gsr_render_forward_seg_z) instead of by a 72 MB fill launch at the head of the
+            # backward, and the record is written whole by the backward
+            record = acc64 = None
             if any(ctx.needs_input_grad[:3]) and P > 0 and _ZERO_IN_FORWARD[0]:
                 record = torch.empty((P, 9), dtype=torch.float32, device=dev)
-            ctx.record = record
+                acc64 = torch.empty((P, 9), dtype=torch.float64, device=dev)
+            ctx.record = (record, acc64) if record is not None else None
 
             def launch_k8(meta_D):
                 with kernel_timer.range("composite_forward", P=P, D=meta_D, **ctx.px_meta) as k8t, \
@@ -1042,7 +1044,7 @@ class _RenderGaussians(torch.autograd.Function):
                     check(lib.gsr_render_forward_seg_z(P, W, H, _ptr(ranges), _ptr(lists[0]), _ptr(means2D),
                                                        _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(out),
                                                        _ptr(final_T), _ptr(n_contrib), _ptr(seg_ws), seg_bytes, row_lo,
-                                                       row_hi, _ptr(record), 36 * P if record is not None else 0,
+                                                       row_hi, _ptr(acc64), 72 * P if acc64 is not None else 0,
                                                        _stream()), "gsr_render_forward_seg_z")
                 return k8t
 
@@ -1103,12 +1105,16 @@ class _RenderGaussians(torch.autograd.Function):
         g_out = g_out.float().contiguous()
         # ONE [P,9] record (means2D 0:2, rgb 2:5, conic_opacity 5:9): K10 flushes a (tile, Gaussian) pair's nine sums
         # from nine adjacent lanes into one row; K11 and the exchange read the record through its row stride
-        # (cleared by the forward's composite kernel when it was allocated there; a second backward over the same
-        # forward -- retain_graph, gradcheck -- takes a fresh one and the fill)
-        record, ctx.record = ctx.record, None
-        record_is_zero = record is not None
-        if record is None:
-            record = torch.empty((P, 9), dtype=torch.float32, device=dev)
+        # K10 adds the tiles' contributions into [P,9] fp64 sums (cleared by the forward's composite kernel when they
+        # were allocated there; a second backward over the same forward -- retain_graph, gradcheck -- takes fresh ones
+        # and the fill) and rounds each sum once into the record: on one GPU the record, hence the training step, is
+        # reproducible from run to run in practice (fp32 atomic adds made it depend on the order the tiles finished)
+        pair, ctx.record = ctx.record, None
+        record_is_zero = pair is not None
+        if pair is None:
+            pair = (torch.empty((P, 9), dtype=torch.float32, device=dev),
+                    torch.empty((P, 9), dtype=torch.float64, device=dev))
+        record, acc64 = pair
         d_means2D, d_rgb, d_conic_opacity = record[:, 0:2], record[:, 2:5], record[:, 5:9]
         timing = ctx.timing
         with _on(dev):
@@ -1122,11 +1128,11 @@ class _RenderGaussians(torch.autograd.Function):
             with kernel_timer.range("composite_backward", P=P, D=ctx.num_rendered, **ctx.px_meta), \
                     zhx_range(ctx.cuda_args, "b10 render time"):
                 seg_ws, seg_bytes, row_lo, row_hi = ctx.seg
-                check(lib.gsr_render_backward_seg_z(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                check(lib.gsr_render_backward_seg_d(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
                                                     _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(final_T),
                                                     _ptr(n_contrib), _ptr(g_out), _ptr(record), _ptr(out_img),
                                                     _ptr(seg_ws), seg_bytes, row_lo, row_hi, 1 if record_is_zero else 0,
-                                                    _stream()), "gsr_render_backward_seg_z")
+                                                    _ptr(acc64), _stream()), "gsr_render_backward_seg_d")
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("bwd1", id(cap_stats))
             if timing != "off":

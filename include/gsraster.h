@@ -323,6 +323,19 @@ int gsr_render_backward_seg_z(int P, int width, int height, const int32_t *range
                               const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
                               void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero,
                               gsr_stream_t stream);
+/* gsr_render_backward_seg_d (ABI 14; the training backward): the same, with K10's per-tile contributions added in fp64
+ * into `acc64` ([P,9] doubles, device scratch of the caller) and each sum rounded once into the record, which is
+ * written whole.  record_is_zero = 1: the forward cleared acc64 (pass it as zero_ptr, 72 * P bytes), else it is cleared
+ * here.  fp64 adds still depend on their order, but the fp32 result of a sum of fp32 terms then differs only in the
+ * rare case that the fp64 sum lies within fp64 rounding of an fp32 rounding boundary: on one GPU the record is
+ * reproducible from run to run in practice, where fp32 adds made it depend on the order the tiles finished.  (At N > 1
+ * the exchange's gradient scatter still adds in fp32.) */
+int gsr_render_backward_seg_d(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                              const float *means2D, const float *conic_opacity, const float *rgb,
+                              const uint8_t *compute_locally, const float *bg, const float *final_T,
+                              const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
+                              void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero,
+                              double *acc64, gsr_stream_t stream);
 /* Measurement aid (bench.py's roofline leg; the reference has nothing to bind here): list entries the composite kernels
  * WALKED since the last reset, summed over launches -- out2[0] K8, out2[1] K10; per tile the entries its longest-walking
  * quadrant goes through (K8: up to the chunk in which the last pixel saturates; K10: the largest n_contrib of the

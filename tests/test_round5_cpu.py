@@ -61,14 +61,14 @@ def test_a_failed_capture_disables_replays_on_every_rank():
 
 
 def test_bench_supervisor_prints_one_json_line_whatever_the_legs_do():
-    """`python bench.py --gpus 2` without a launcher supervises its legs as time-limited children: on a box without two
-    GPUs both legs die (here: no GPU at all), and the supervisor still prints exactly ONE JSON line that carries the
-    metric's fields and an error per leg"""
+    """`python bench.py --gpus 2 --full` without a launcher supervises its legs as time-limited children: on a box
+    without two GPUs both legs die (here: no GPU at all), and the supervisor still prints exactly ONE JSON line that
+    carries the metric's fields and an error per leg"""
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--leg-timeout", "90"], capture_output=True, text=True, env=env, timeout=600)
+                        "--leg-timeout", "90", "--full"], capture_output=True, text=True, env=env, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])

@@ -58,9 +58,9 @@ for st in $STAGES; do
 done
 if has shapes; then
   for wl in c2 c4; do
-    timeout 600 python bench.py --workload $wl --no-cpu-baseline --no-extra --steps 10 --warmup 4 --repeats 1 --render-steps 4 > $O/bench_${wl}_shape.json 2> $O/bench_${wl}_shape.err
+    timeout 600 python bench.py --full --workload $wl --no-cpu-baseline --no-extra --steps 10 --warmup 4 --repeats 1 --render-steps 4 > $O/bench_${wl}_shape.json 2> $O/bench_${wl}_shape.err
     echo "bench $wl shape exit $?"; summ $O/bench_${wl}_shape.json $wl
-    GSR_BIN_PERSIST=0 timeout 600 python bench.py --workload $wl --no-cpu-baseline --no-extra --steps 10 --warmup 4 --repeats 1 --render-steps 4 > $O/bench_${wl}_shape_off.json 2> $O/bench_${wl}_shape_off.err
+    GSR_BIN_PERSIST=0 timeout 600 python bench.py --full --workload $wl --no-cpu-baseline --no-extra --steps 10 --warmup 4 --repeats 1 --render-steps 4 > $O/bench_${wl}_shape_off.json 2> $O/bench_${wl}_shape_off.err
     summ $O/bench_${wl}_shape_off.json "$wl persist=0"
   done
 fi
@@ -76,9 +76,9 @@ if has cull; then
   timeout 300 python tools/binbench.py --iters 10 --width 3840 --height 2160 --modes off both --cull 0 1 > $O/binbench_4k.txt 2> $O/binbench_4k.err
   echo "binbench 4k exit $?"; cat $O/binbench_4k.txt; tail -2 $O/binbench_4k.err | grep -v amdgpu
   for v in 0 1; do
-    GSR_TILE_CULL=$v timeout 600 python bench.py --workload c1_4k --no-cpu-baseline --no-extra --steps 10 --warmup 4 --repeats 1 --render-steps 4 > $O/bench_4k_cull$v.json 2> $O/bench_4k_cull$v.err
+    GSR_TILE_CULL=$v timeout 600 python bench.py --full --workload c1_4k --no-cpu-baseline --no-extra --steps 10 --warmup 4 --repeats 1 --render-steps 4 > $O/bench_4k_cull$v.json 2> $O/bench_4k_cull$v.err
     summ $O/bench_4k_cull$v.json "c1_4k cull=$v"
-    GSR_TILE_CULL=$v timeout 600 python bench.py --no-cpu-baseline --no-extra --steps 20 --warmup 6 --repeats 2 --render-steps 10 > $O/bench_c1_cull$v.json 2> $O/bench_c1_cull$v.err
+    GSR_TILE_CULL=$v timeout 600 python bench.py --full --no-cpu-baseline --no-extra --steps 20 --warmup 6 --repeats 2 --render-steps 10 > $O/bench_c1_cull$v.json 2> $O/bench_c1_cull$v.err
     summ $O/bench_c1_cull$v.json "c1 cull=$v"
   done
 fi

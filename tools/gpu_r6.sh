@@ -33,7 +33,7 @@ if has k11ab; then
   for bsz in ${K11_BSZ:-4}; do
     for lib in "" $(ls variants/libgsraster_*.so 2>/dev/null); do
       n=production; [ -n "$lib" ] && { n=$(basename $lib .so); n=${n#libgsraster_}; }
-      GSRASTER_LIB=${lib:+$R/$lib} timeout 300 python bench.py --bsz $bsz --no-cpu-baseline --no-extra --steps 20 --warmup 5 --repeats 2 --render-steps 2 > $O/k11ab_${n}_b$bsz.json 2> $O/k11ab_${n}_b$bsz.err
+      GSRASTER_LIB=${lib:+$R/$lib} timeout 300 python bench.py --full --bsz $bsz --no-cpu-baseline --no-extra --steps 20 --warmup 5 --repeats 2 --render-steps 2 > $O/k11ab_${n}_b$bsz.json 2> $O/k11ab_${n}_b$bsz.err
       line $O/k11ab_${n}_b$bsz.json "$n bsz$bsz" | tee -a $O/k11ab.txt
     done
   done

@@ -83,16 +83,16 @@ if has test; then
   tail -6 $O/gputest.log
 fi
 if has bench; then
-  timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+  timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
   echo "bench exit $?"
   summ $O/bench.json bench
 fi
 if has benchq; then
-  timeout 300 python bench.py --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/benchq.json 2> $O/benchq.err
+  timeout 300 python bench.py --full --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/benchq.json 2> $O/benchq.err
   summ $O/benchq.json benchq | tee -a $O/ab.txt
 fi
 if has benchg; then
-  timeout 300 python bench.py --graph on --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/benchg.json 2> $O/benchg.err
+  timeout 300 python bench.py --full --graph on --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/benchg.json 2> $O/benchg.err
   summ $O/benchg.json "graph=on" | tee -a $O/ab.txt
   python -c "import json; d=json.load(open('$O/benchg.json')); print(d.get('graph'), d['timing'])"
 fi
@@ -100,10 +100,10 @@ if has ab; then
   for lib in $(ls variants/libgsraster_*.so 2>/dev/null); do
     [[ $lib == *stats* ]] && continue
     n=$(basename $lib .so); n=${n#libgsraster_}
-    GSRASTER_LIB=$R/$lib timeout 300 python bench.py --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/ab_$n.json 2> $O/ab_$n.err
+    GSRASTER_LIB=$R/$lib timeout 300 python bench.py --full --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/ab_$n.json 2> $O/ab_$n.err
     summ $O/ab_$n.json $n | tee -a $O/ab.txt
   done
-  timeout 300 python bench.py --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/ab_production2.json 2> $O/ab_production2.err
+  timeout 300 python bench.py --full --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/ab_production2.json 2> $O/ab_production2.err
   summ $O/ab_production2.json production2 | tee -a $O/ab.txt
 fi
 if has abfake8; then
@@ -116,7 +116,7 @@ if has abfake8; then
 fi
 if has abseg; then
   for v in 1 0 1 0; do
-    GSR_SEGMENTS=$v timeout 300 python bench.py --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/abseg_$v.json 2> $O/abseg_$v.err
+    GSR_SEGMENTS=$v timeout 300 python bench.py --full --no-cpu-baseline --no-extra --steps 30 --warmup 6 --repeats 3 --render-steps 10 > $O/abseg_$v.json 2> $O/abseg_$v.err
     summ $O/abseg_$v.json "segments=$v" | tee -a $O/abseg.txt
     GSR_SEGMENTS=$v timeout 300 python tools/fake_world_bench.py --workload c2 --worlds 8 --steps 20 --graph on > $O/abseg_fake8_$v.txt 2> $O/abseg_fake8_$v.err
     echo "segments=$v fake8: $(cut -c1-400 $O/abseg_fake8_$v.txt | head -1)" | tee -a $O/abseg.txt
@@ -125,7 +125,7 @@ fi
 if has ablow; then
   for v in "1 1" "0 1" "1 0" "0 0"; do
     set -- $v
-    GSR_SEGMENTS=$1 GSR_BAND_GRID=$2 timeout 300 python bench.py --no-cpu-baseline --no-extra --steps 20 --warmup 5 --repeats 2 --render-steps 5 --opacity-logit-mean -2 --opacity-logit-std 1 > $O/ablow_$1$2.json 2> $O/ablow_$1$2.err
+    GSR_SEGMENTS=$1 GSR_BAND_GRID=$2 timeout 300 python bench.py --full --no-cpu-baseline --no-extra --steps 20 --warmup 5 --repeats 2 --render-steps 5 --opacity-logit-mean -2 --opacity-logit-std 1 > $O/ablow_$1$2.json 2> $O/ablow_$1$2.err
     summ $O/ablow_$1$2.json "lowop seg=$1 band=$2" | tee -a $O/ablow.txt
     GSR_SEGMENTS=$1 GSR_BAND_GRID=$2 timeout 300 python tools/fake_world_bench.py --workload c2 --worlds 4 8 --steps 20 --graph on > $O/ablow_fake_$1$2.txt 2> $O/ablow_fake_$1$2.err
     cut -c1-330 $O/ablow_fake_$1$2.txt | sed "s/^/seg=$1 band=$2 /" | tee -a $O/ablow.txt
@@ -173,7 +173,7 @@ if has pmc; then
   [ -s $O/pmc.json ] && cp $O/pmc.json $R/profiles/${PMC_NAME:-r04_pmc}.json && cp $O/pmc.txt $R/profiles/${PMC_NAME:-r04_pmc}.txt
 fi
 if has benchfull; then
-  timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err
+  timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err
   echo "bench exit $?"
   summ $O/bench.json bench
   python -c "import json; d=json.load(open('$O/bench.json')); print(json.dumps(d['roofline'])[:900]); print([ (w['workload'][:30], w.get('value')) for w in d.get('extra_workloads', [])]); print(d['cpu_baseline'])"

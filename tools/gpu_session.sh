@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-BENCH="python $R/bench.py --no-cpu-baseline --no-extra --steps 16 --warmup 4 --repeats 1 --render-steps 8 ${GSR_SESSION_BENCH_ARGS:-}"
+BENCH="python $R/bench.py --full --no-cpu-baseline --no-extra --steps 16 --warmup 4 --repeats 1 --render-steps 8 ${GSR_SESSION_BENCH_ARGS:-}"
 has() { [[ " $STAGES " == *" $1 "* ]]; }
 cd $R
 if has test; then
@@ -18,7 +18,7 @@ if has test; then
   tail -5 $O/gputest.log
 fi
 if has bench; then
-  timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -c 600 $O/bench.json
+  timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -c 600 $O/bench.json
 fi
 cd /tmp
 for st in trace sq fetch write; do
@@ -43,7 +43,7 @@ if has trace || has sq || has fetch || has write; then
   find $O -name "*.db" -size +20M -delete
 fi
 if has lowop; then
-  timeout 600 python bench.py --no-cpu-baseline --no-extra --opacity-logit-mean -2 --opacity-logit-std 1 > $O/bench_lowopacity.json 2> $O/bench_lowopacity.err
+  timeout 600 python bench.py --full --no-cpu-baseline --no-extra --opacity-logit-mean -2 --opacity-logit-std 1 > $O/bench_lowopacity.json 2> $O/bench_lowopacity.err
   echo "lowop exit $?"
 fi
 if has multirank; then

@@ -4,7 +4,7 @@ waits there (slack); if the wait is ~0 the iteration is host-bound."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.argv = ["bench.py", "--steps", "60", "--warmup", "10", "--no-cpu-baseline", "--repeats", "1", "--render-steps", "0"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--steps", "60", "--warmup", "10", "--no-cpu-baseline", "--repeats", "1", "--render-steps", "0"] + sys.argv[1:]
 import bench  # noqa
 import diff_gaussian_rasterization as dgr  # noqa
 

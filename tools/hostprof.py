@@ -2,7 +2,7 @@
 import cProfile, os, pstats, sys, io
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.argv = ["bench.py", "--steps", "200", "--warmup", "20", "--no-cpu-baseline", "--gaussians", "4000", "--width", "128",
+sys.argv = ["bench.py", "--full", "--steps", "200", "--warmup", "20", "--no-cpu-baseline", "--gaussians", "4000", "--width", "128",
             "--height", "128", "--render-steps", "1"]
 import bench  # noqa
 pr = cProfile.Profile()

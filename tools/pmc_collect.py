@@ -2,10 +2,10 @@
 
 Inputs: rocpd sqlite databases written by (each in its OWN run, as MI355X_MICROARCH.md prescribes: TCC slot limits,
 and never combined with the hip / hsa / memory-copy trace domains):
-    rocprofv3 --kernel-trace                      -d DIR_TRACE -- python bench.py --no-cpu-baseline ...
-    rocprofv3 --kernel-trace --pmc SQ_...(<= 8)   -d DIR_SQ    -- python bench.py --no-cpu-baseline ...
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE     -d DIR_FETCH -- python bench.py --no-cpu-baseline --pmc-calib ...
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE     -d DIR_WRITE -- python bench.py --no-cpu-baseline --pmc-calib ...
+    rocprofv3 --kernel-trace                      -d DIR_TRACE -- python bench.py --full --no-cpu-baseline ...
+    rocprofv3 --kernel-trace --pmc SQ_...(<= 8)   -d DIR_SQ    -- python bench.py --full --no-cpu-baseline ...
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE     -d DIR_FETCH -- python bench.py --full --no-cpu-baseline --pmc-calib ...
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE     -d DIR_WRITE -- python bench.py --full --no-cpu-baseline --pmc-calib ...
 Usage: python tools/pmc_collect.py --trace DIR --sq DIR --fetch DIR --write DIR --out profiles/r02_pmc.json \
                                    --command "<the bench.py command line>" > profiles/r02_pmc.txt
 

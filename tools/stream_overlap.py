@@ -1,5 +1,5 @@
 """Do the views of bench.py's two-stream render legs overlap on the device?  From a rocprofv3 kernel trace (rocpd database) of
-    rocprofv3 --kernel-trace -d DIR -- python bench.py --no-cpu-baseline --no-extra --steps 4 --warmup 2 --repeats 1 --render-steps N
+    rocprofv3 --kernel-trace -d DIR -- python bench.py --full --no-cpu-baseline --no-extra --steps 4 --warmup 2 --repeats 1 --render-steps N
 the last N views are the pipelined two-stream leg, the N before them the plain two-stream leg, the N before those the
 sequential one-stream leg (warm-up views of a leg are attributed to it).  For each leg: wall span of its kernels, the sum of
 their durations, the time during which kernels of TWO queues ran at once, and the pairs that overlapped most.
