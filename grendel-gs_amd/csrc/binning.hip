@@ -695,6 +695,13 @@ int prepare_lookback(const PrepCall &c, uint32_t *ticket) {
     return 0;
 }
 
+// GSR_BIN_DEPTH_SORT = lsd (read per call): the depth sort of the persistent prepare kernel as four global LSD passes
+// (A/B measurements, tests); default: one global pass by depth bucket + a workgroup-local sort (binning_persist.h)
+bool depth_buckets_on() {
+    const char *e = getenv("GSR_BIN_DEPTH_SORT");
+    return !(e && strcmp(e, "lsd") == 0);
+}
+
 // K3-K4 as ONE persistent launch (binning_persist.h).  -> 0 launched, 1 not applicable here (use the look-back
 // pipeline), otherwise an error
 int prepare_persistent(const PrepCall &c, uint32_t *ticket) {
@@ -754,6 +761,8 @@ int prepare_persistent(const PrepCall &c, uint32_t *ticket) {
     a.grp = reinterpret_cast<uint32_t *>(ctrl + PL.grp);
     a.cnt = reinterpret_cast<uint32_t *>(ctrl + PL.cnt);
     a.wtot = reinterpret_cast<unsigned long long *>(ctrl + PL.wtot);
+    a.bins = reinterpret_cast<uint32_t *>(ctrl + PL.bins);
+    a.depth_buckets = depth_buckets_on() ? 1 : 0;
     a.host_total = host_total;
     a.seq = seq;
     a.done_word = g_persist_done[dev];

@@ -9,9 +9,16 @@
 // offsets from the published counts -- no state words, no ripple, no tickets.
 //
 //   bin_prepare_persist_kernel  (<= one 1024-thread workgroup per CU, contiguous 4096-element tiles per workgroup)
-//       T   K3: rect / tile count / depth key per Gaussian (keys stay in registers), digit counts of pass 0
+//       T   K3: rect / tile count / depth key per Gaussian (keys stay in registers), the key range of the live ones
+//       B M C G   the depth sort by BUCKETS (one tile per workgroup, <= 256 workgroups): 4096 bins over the key range
+//           counted over the grid; every workgroup derives the same monotone map bin -> one of min(G, 255) buckets of
+//           about live / buckets rows; ONE stable global pass by bucket (culled and padding rows: digit 255, behind)
+//       L S1 S2   workgroup w sorts bucket w in LDS (stable 8-bit passes over the bits in which its keys differ), keeps
+//           the ids, sums their tile counts; offsets = exclusive scan of tiles_touched[sorted id] from the buckets' sums
+//       -- five grid barriers and one global scatter.  A bucket that exceeds a workgroup (8192 rows), a view without a live
+//       Gaussian, several tiles per workgroup, GSR_BIN_DEPTH_SORT=lsd: the four global passes, in the same launch --
 //       B0 A1 B1 A2 B2 A3 B3   four LSD passes: B = scatter with offsets from the published counts, A = count
-//       S1 S2   offsets = exclusive scan of tiles_touched[sorted id]; the pair count D to the pinned host slot
+//       S1 S2   offsets as above, over the tiles; the pair count D to the pinned host slot
 //   bin_sort_persist_kernel     (four 512-thread workgroups per CU, contiguous 4096-pair tiles per workgroup)
 //       E0  column-digit counts of the workgroup's slots FROM THE RECTS (O(Gaussians), nothing is decoded), and the
 //           owner Gaussian of every 512-slot chunk (so the emission never searches)
@@ -391,12 +398,14 @@ __device__ __forceinline__ uint32_t gsr_rect_tiles(const float2 xy, const float4
 // LDS of a persistent sort workgroup (the staging area doubles as scratch of the phases that do not scatter)
 template <int ITEMS, int THREADS>
 struct PersistSmem {
+    // (the small members first: the prepare kernel looks at one allocation with ITEMS = 4 and with ITEMS = 8, and only the
+    // staging area may differ between the two views)
     uint16_t wtab[THREADS / 64][RADIX_DIGITS];  // per-wave digit counts, then per-wave cursors
     uint32_t gbase[RADIX_DIGITS];               // global start of the digit's run minus its start inside the tile
-    uint32_t skey[ITEMS * THREADS], sval[ITEMS * THREADS];
-    uint32_t scan_tmp[THREADS / 64];
     unsigned long long scan64[THREADS / 64];
+    uint32_t scan_tmp[THREADS / 64];
     uint32_t flag;
+    uint32_t skey[ITEMS * THREADS], sval[ITEMS * THREADS];
 };
 
 template <int ITEMS, int THREADS>
@@ -405,18 +414,42 @@ __device__ __forceinline__ void clear_wtab(PersistSmem<ITEMS, THREADS> &sm) {
     for (int i = threadIdx.x; i < (THREADS / 64) * RADIX_DIGITS / 2; i += THREADS) p[i] = 0u;
 }
 
+// The digit of a key in one counting / scatter pass: a byte of the key (the LSD passes) ...
+struct ByteDigit {
+    int shift;
+    uint32_t mask;
+    __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return (k >> shift) & mask; }
+};
+// ... or the depth bucket of the key (bin_prepare_persist_kernel's bucket path): map = LDS [BK_BINS], bin -> bucket;
+// digit 255 = culled / padding rows (key 0xFFFFFFFF), which stay in arrival order behind every live bucket
+constexpr int BK_BINS = 4096, BK_BIN_BITS = 12;
+constexpr uint32_t BK_TAIL = 255u;
+struct BucketDigit {
+    const uint8_t *map;
+    uint32_t kmin;
+    int sh;
+    __device__ __forceinline__ uint32_t operator()(uint32_t k) const {
+        return k == 0xFFFFFFFFu ? BK_TAIL : (uint32_t)map[(k - kmin) >> sh];
+    }
+};
+
 // per-wave digit counts of the ITEMS pairs a thread holds (element r of a lane: wbase + r * 64 + lane < n is valid)
-template <int ITEMS, int THREADS>
+template <int ITEMS, int THREADS, class DG>
 __device__ __forceinline__ void count_wave_digits(PersistSmem<ITEMS, THREADS> &sm, const uint32_t (&key)[ITEMS],
-                                                  long long wbase, long long n, int shift, uint32_t mask) {
+                                                  long long wbase, long long n, const DG digit) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int r = 0; r < ITEMS; r++) {
         if (wbase + r * 64 + lane < n) {
-            const uint32_t dg = (key[r] >> shift) & mask;
+            const uint32_t dg = digit(key[r]);
             atomicAdd(reinterpret_cast<uint32_t *>(sm.wtab[wave]) + (dg >> 1), 1u << (16 * (dg & 1u)));  // no carry: <= 512
         }
     }
+}
+template <int ITEMS, int THREADS>
+__device__ __forceinline__ void count_wave_digits(PersistSmem<ITEMS, THREADS> &sm, const uint32_t (&key)[ITEMS],
+                                                  long long wbase, long long n, int shift, uint32_t mask) {
+    count_wave_digits(sm, key, wbase, n, ByteDigit{shift, mask});
 }
 
 // One tile of a scatter phase, in two steps so that the caller can have the loads of its global offsets in flight
@@ -425,12 +458,11 @@ __device__ __forceinline__ void count_wave_digits(PersistSmem<ITEMS, THREADS> &s
 // lanes in order); thread d < 256 gets the tile's count of digit d and the digit's start inside the tile.
 // scatter_write -- `first` (thread d < 256) = global position of the first pair of digit d that THIS tile writes;
 // streams the staged pairs out (coalesced runs per digit).  Ends with a workgroup barrier (LDS reusable).
-template <int ITEMS, int THREADS>
+template <int ITEMS, int THREADS, class DG>
 __device__ __forceinline__ void scatter_rank(PersistSmem<ITEMS, THREADS> &sm, const uint32_t (&key)[ITEMS],
-                                             const uint32_t (&val)[ITEMS], long long tbase, long long n, int shift,
+                                             const uint32_t (&val)[ITEMS], long long tbase, long long n, const DG digit,
                                              int nbits, uint32_t &tot_out, uint32_t &run_out) {
     constexpr int WAVES = THREADS / 64;
-    const uint32_t mask = (1u << nbits) - 1u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long wbase = tbase + (long long)wave * (ITEMS * 64);
     const uint32_t d = threadIdx.x;
@@ -456,7 +488,7 @@ __device__ __forceinline__ void scatter_rank(PersistSmem<ITEMS, THREADS> &sm, co
 #pragma unroll
     for (int r = 0; r < ITEMS; r++) {
         const bool valid = wbase + r * 64 + lane < n;
-        const uint32_t dg = (key[r] >> shift) & mask;
+        const uint32_t dg = digit(key[r]);
         const unsigned long long m = match_digit(dg, valid, nbits);
         const uint32_t rank = __popcll(m & lt);
         uint16_t *cursor = sm.wtab[wave];
@@ -472,6 +504,13 @@ __device__ __forceinline__ void scatter_rank(PersistSmem<ITEMS, THREADS> &sm, co
             sm.sval[pos] = val[r];
         }
     }
+}
+
+template <int ITEMS, int THREADS>
+__device__ __forceinline__ void scatter_rank(PersistSmem<ITEMS, THREADS> &sm, const uint32_t (&key)[ITEMS],
+                                             const uint32_t (&val)[ITEMS], long long tbase, long long n, int shift,
+                                             int nbits, uint32_t &tot_out, uint32_t &run_out) {
+    scatter_rank(sm, key, val, tbase, n, ByteDigit{shift, (1u << nbits) - 1u}, nbits, tot_out, run_out);
 }
 
 template <int ITEMS, int THREADS, bool WT_VALS>
@@ -512,6 +551,25 @@ __device__ __forceinline__ uint32_t scatter_tile(PersistSmem<ITEMS, THREADS> &sm
 __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// Butterfly reductions of the prepare kernel.  The exchange addresses ((lane ^ d) << 2) are formed from a lane id the
+// compiler cannot connect to other uses: shared with the reductions further down the kernel they would stay in registers
+// from phase T to the scan (six registers that the 1024-thread workgroup does not have: 128 per thread).
+__device__ __forceinline__ uint32_t xor_lane(uint32_t v, int lane, int d) {
+    return (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)v);
+}
+__device__ __forceinline__ int opaque_lane() {
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+__device__ __forceinline__ unsigned long long wave_sum64_local(unsigned long long v) {
+    const int lane = opaque_lane();
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        v += (unsigned long long)xor_lane((uint32_t)v, lane, d) | ((unsigned long long)xor_lane((uint32_t)(v >> 32), lane, d) << 32);
     return v;
 }
 
@@ -567,9 +625,12 @@ struct PrepPersistArgs {
     uint4 *zero16;              // the control block of the tile sort that follows (cleared here), or null
     size_t zero16_n;
     GridSync sync;
-    uint32_t *cnt;  // [4][G][256]
-    uint32_t *grp;  // [4][ngroups][256], zero before the launch
+    uint32_t *cnt;  // [5][G][256]: the four LSD passes, then the bucket pass
+    uint32_t *grp;  // [5][ngroups][256], zero before the launch
     unsigned long long *wtot;  // [G]
+    uint32_t *bins;            // bucket path: [BK_BINS] bin counts, then { ~min key, max key } of the live Gaussians; zero
+                               // before the launch
+    int depth_buckets;         // 1: one bucket pass + a workgroup-local sort where it applies; 0: four LSD passes
     uint32_t *host_total;      // pinned: { pair count, sequence tag }
     uint32_t seq;
     uint32_t *done_word;  // pinned: sequence number of the last persistent launch that passed its last barrier
@@ -584,13 +645,133 @@ struct PPExtra {
     int s_lo, s_hi;
 };
 
+// ---- the bucket path of the depth sort: ONE global pass by depth bucket, then every bucket is sorted by the workgroup
+// that owns it.  A bucket is a range of keys (the map bin -> bucket is monotone) and the global pass is stable, so a
+// bucket arrives in arrival order and stable LSD passes over the bits in which its keys differ give the order of the
+// four global passes, ties included.
+constexpr int BK_ITEMS = 8;                        // pairs per thread of the local sort
+constexpr int BK_CAP = BK_ITEMS * PP_THREADS;      // ... hence the largest bucket a workgroup takes
+constexpr int BK_PASS = RADIX_MAX_PASSES;          // slot of the bucket pass in cnt / grp
+struct PPBucket {
+    uint8_t map[BK_BINS];  // bin -> bucket
+    uint32_t lo, n, live;  // this workgroup's bucket: [lo, lo + n) of the scattered arrays; live rows of the view
+};
+
+// streams the pairs that scatter_rank staged to their buckets: live pairs to (keys_out, vals_out), written through (the
+// bucket's owner reads them); the ids of the culled tail straight to their final place in ids_out (digit BK_TAIL starts at
+// `live`), which only the next kernel reads.  Ends with a workgroup barrier.
+template <int ITEMS, int THREADS>
+__device__ __forceinline__ void bucket_scatter_write(PersistSmem<ITEMS, THREADS> &sm, long long n, const BucketDigit digit,
+                                                     uint32_t first, uint32_t run, uint32_t *__restrict__ keys_out,
+                                                     uint32_t *__restrict__ vals_out, uint32_t *__restrict__ ids_out) {
+    constexpr int TILE = ITEMS * THREADS;
+    if (threadIdx.x < RADIX_DIGITS) sm.gbase[threadIdx.x] = first - run;
+    __syncthreads();  // (also: every wave has staged its pairs)
+    const int count = n < TILE ? (int)n : TILE;
+#pragma unroll
+    for (int r = 0; r < ITEMS; r++) {
+        const int i = r * THREADS + threadIdx.x;
+        if (i < count) {
+            const uint32_t k = sm.skey[i];
+            const uint32_t dg = digit(k);
+            const uint32_t dst = sm.gbase[dg] + (uint32_t)i;
+            if (dg == BK_TAIL) {
+                ids_out[dst] = sm.sval[i];
+            } else {
+                st_agent(&keys_out[dst], k);
+                st_agent(&vals_out[dst], sm.sval[i]);
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// Sorts the n <= BK_CAP pairs (kin, vin)[lo, lo + n) by key, stably, inside the workgroup and leaves the ids in
+// s.sval[0, n).  red: 2 * THREADS / 64 words of LDS scratch.  Ends with a workgroup barrier.
+template <int THREADS>
+__device__ __forceinline__ void bucket_sort_span(PersistSmem<BK_ITEMS, THREADS> &s, const uint32_t *__restrict__ kin,
+                                                 const uint32_t *__restrict__ vin, uint32_t lo, uint32_t n,
+                                                 uint32_t *__restrict__ red) {
+    constexpr int WAVES = THREADS / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t wbase = (uint32_t)wave * (BK_ITEMS * 64);
+    uint32_t key[BK_ITEMS], val[BK_ITEMS];
+    uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+#pragma unroll
+    for (int r = 0; r < BK_ITEMS; r++) {
+        const uint32_t i = wbase + r * 64 + lane;
+        key[r] = i < n ? ld_agent(&kin[lo + i]) : 0xFFFFFFFFu;
+        val[r] = i < n ? ld_agent(&vin[lo + i]) : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < BK_ITEMS; r++) {
+        if (wbase + r * 64 + lane < n) {
+            mn = min(mn, key[r]);
+            mx = max(mx, key[r]);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        mn = min(mn, (uint32_t)__shfl_xor(mn, d, 64));
+        mx = max(mx, (uint32_t)__shfl_xor(mx, d, 64));
+    }
+    if (lane == 0) {
+        red[wave] = mn;
+        red[WAVES + wave] = mx;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int wv = 0; wv < WAVES; wv++) {
+        mn = min(mn, red[wv]);
+        mx = max(mx, red[WAVES + wv]);
+    }
+    const uint32_t diff = mx > mn ? mx - mn : 0u;  // (an empty span: mn > mx)
+    const int nbits = diff ? 32 - __clz(diff) : 0;  // the bits of key - min in which the span's keys differ
+#pragma unroll
+    for (int r = 0; r < BK_ITEMS; r++) key[r] -= mn;
+    if (nbits == 0) {  // one key value: the span is in order as it arrived
+#pragma unroll
+        for (int r = 0; r < BK_ITEMS; r++) {
+            const uint32_t i = wbase + r * 64 + lane;
+            if (i < n) s.sval[i] = val[r];
+        }
+        __syncthreads();
+        return;
+    }
+    // as few passes as 8-bit digits allow, the bits spread evenly over them (a digit bit is a ballot per pair in the ranking)
+    const int passes = (nbits + 7) / 8, pb = (nbits + passes - 1) / passes;
+    for (int shift = 0; shift < nbits; shift += pb) {
+        clear_wtab(s);
+        __syncthreads();
+        count_wave_digits(s, key, (long long)wbase, (long long)n, shift, (1u << pb) - 1u);
+        __syncthreads();
+        uint32_t tot, run;
+        scatter_rank(s, key, val, 0ll, (long long)n, shift, pb, tot, run);
+        __syncthreads();
+        if (shift + pb < nbits) {  // the staged pairs are this pass's output: take them back in wave-striped order
+#pragma unroll
+            for (int r = 0; r < BK_ITEMS; r++) {
+                const uint32_t i = wbase + r * 64 + lane;
+                if (i < n) {
+                    key[r] = s.skey[i];
+                    val[r] = s.sval[i];
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 
 template <int PP_ITEMS>
 __global__ void __launch_bounds__(PP_THREADS)
 bin_prepare_persist_kernel(const PrepPersistArgs a) {
     constexpr int PP_TILE = PP_THREADS * PP_ITEMS;
-    __shared__ PersistSmem<PP_ITEMS, PP_THREADS> sm;
+    // (the staging area holds a whole bucket of the local sort; the phases of a tile use its first PP_TILE pairs)
+    __shared__ PersistSmem<BK_ITEMS, PP_THREADS> sm8;
+    PersistSmem<PP_ITEMS, PP_THREADS> &sm = *reinterpret_cast<PersistSmem<PP_ITEMS, PP_THREADS> *>(&sm8);
     __shared__ PPExtra ex;
+    __shared__ PPBucket bk;
     __shared__ uint32_t red2[2 * PP_THREADS];  // reduction scratch of counts_finish (the staging area is in use then)
     const uint32_t G = gridDim.x, w = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -598,6 +779,8 @@ bin_prepare_persist_kernel(const PrepPersistArgs a) {
     const long long nb = (P + PP_TILE - 1) / PP_TILE;
     const long long t0 = (long long)w * nb / G, t1 = (long long)(w + 1) * nb / G;  // contiguous tiles of this workgroup
     const bool keep = (t1 - t0) == 1;  // one tile: its pairs live in registers from a count phase to its scatter phase
+    // the bucket path needs EVERY workgroup to keep its one tile in registers (uniform over the grid)
+    const bool try_buckets = a.depth_buckets && nb == (long long)G && counts_fit_registers<PP_THREADS>(G);
     const uint32_t d = threadIdx.x;
     uint32_t epoch = 0;
     GSR_TS(0);
@@ -634,6 +817,7 @@ bin_prepare_persist_kernel(const PrepPersistArgs a) {
     }
     uint32_t mytot = 0;  // thread d < 256: this workgroup's count of digit d in the pass being counted
     unsigned long long nsum = 0;  // this thread's share of the pair count
+    uint32_t kmn = 0xFFFFFFFFu, kmx = 0u;  // smallest / largest key of this thread's live Gaussians
     for (long long t = t0; t < t1; t++) {
         const long long wbase = t * PP_TILE + (long long)wave * (PP_ITEMS * 64);
         // every input of four of the thread's Gaussians is requested before the first is looked at (clamped indices, no
@@ -677,7 +861,11 @@ bin_prepare_persist_kernel(const PrepPersistArgs a) {
                                                a.tile_hist ? ex.dxy : nullptr, rect);
                     }
                 }
-                if (n) key[r] = __float_as_uint(dep[q4]);
+                if (n) {
+                    key[r] = __float_as_uint(dep[q4]);
+                    kmn = min(kmn, key[r]);
+                    kmx = max(kmx, key[r]);
+                }
                 nsum += n;
                 // (gathered by other workgroups in the scan phase; the rows of the rect -- its row segments -- ride in the
                 // upper bits on the (row, column) path)
@@ -690,6 +878,7 @@ bin_prepare_persist_kernel(const PrepPersistArgs a) {
             }
         }
         }
+        if (try_buckets) continue;  // (the digit of the one global pass is not known yet: the key range comes first)
         count_wave_digits(sm, key, wbase, P, 0, 0xFFu);
         __syncthreads();
         if (d < RADIX_DIGITS) {
@@ -702,16 +891,36 @@ bin_prepare_persist_kernel(const PrepPersistArgs a) {
             __syncthreads();
         }
     }
-    if (d < RADIX_DIGITS) publish_counts(a.cnt, a.grp, w, d, mytot);
+    if (!try_buckets && d < RADIX_DIGITS) publish_counts(a.cnt, a.grp, w, d, mytot);
     {  // this workgroup's share of the pair count (read by workgroup 0 behind the first barrier): ONE atomic per workgroup
-        nsum = wave_sum64(nsum);
+        nsum = wave_sum64_local(nsum);
+        {
+            const int ol = opaque_lane();
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                kmn = min(kmn, xor_lane(kmn, ol, o));
+                kmx = max(kmx, xor_lane(kmx, ol, o));
+            }
+        }
         __syncthreads();  // (scan64 is free: nothing has used it yet, but keep the phases apart)
-        if (lane == 0) sm.scan64[wave] = nsum;
+        if (lane == 0) {
+            sm.scan64[wave] = nsum;
+            red2[wave] = kmn;
+            red2[PP_WAVES + wave] = kmx;
+        }
         __syncthreads();
         if (threadIdx.x == 0) {
             unsigned long long tot = 0;
-            for (int wv = 0; wv < PP_WAVES; wv++) tot += sm.scan64[wv];
+            for (int wv = 0; wv < PP_WAVES; wv++) {
+                tot += sm.scan64[wv];
+                kmn = min(kmn, red2[wv]);
+                kmx = max(kmx, red2[PP_WAVES + wv]);
+            }
             if (tot) __hip_atomic_fetch_add(a.early, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (try_buckets && kmn <= kmx) {  // the key range of the view's live Gaussians (the words start at zero)
+                __hip_atomic_fetch_max(&a.bins[BK_BINS], ~kmn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_max(&a.bins[BK_BINS + 1], kmx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
     }
     if (a.tile_hist) {  // the tile sort's digit histograms, for the look-back tile sort (large D, contended device)
@@ -749,6 +958,186 @@ bin_prepare_persist_kernel(const PrepPersistArgs a) {
     const uint64_t forever = 100000000ull;
     // ------------------------------------------------------------------ four LSD passes over the depth bits
     const uint32_t ngroups = (G + GB_FAN - 1) / GB_FAN;
+    if (try_buckets) {
+        // -------------------------------------------------------------- the bucket path (see bucket_sort_span)
+        static_assert(BK_BINS == 4 * PP_THREADS, "four bins per thread");
+        const long long wbase0 = t0 * PP_TILE + (long long)wave * (PP_ITEMS * 64);
+        const uint32_t kmin = ~ld_agent(&a.bins[BK_BINS]), kmax = ld_agent(&a.bins[BK_BINS + 1]);
+        const uint32_t NB = min(G, BK_TAIL);
+        // every decision below is taken on words the whole grid sees alike.  No live Gaussian, or a live key that equals
+        // the mark of the culled rows: four passes
+        bool buckets = kmin <= kmax && kmax != 0xFFFFFFFFu;
+        if (buckets) {
+            // B: 4096 bins of equal width over the key range of the view, counted over the grid
+            const uint32_t range = kmax - kmin;
+            const int sh = max((range ? 32 - __clz(range) : 0) - BK_BIN_BITS, 0);
+            const BucketDigit digit{bk.map, kmin, sh};
+            uint32_t *const lbin = sm8.skey;
+            for (int i = threadIdx.x; i < BK_BINS; i += PP_THREADS) lbin[i] = 0u;
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < PP_ITEMS; r++)
+                if (key[r] != 0xFFFFFFFFu) atomicAdd(&lbin[(key[r] - kmin) >> sh], 1u);
+            __syncthreads();
+            for (int i = threadIdx.x; i < BK_BINS; i += PP_THREADS) {
+                const uint32_t c = lbin[i];
+                if (c) __hip_atomic_fetch_add(&a.bins[i], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            GSR_TS(21);
+            if (!grid_barrier(a.sync, G, epoch, forever, &sm.flag)) { barrier_fault(a.done_word, 0x200u + epoch); return; }
+            GSR_TS(22);
+            // M: splitters.  The bin that starts at live row s goes to bucket s * NB / live: monotone in the bin, the same
+            // in every workgroup, at most live / NB rows + one bin per bucket (s * NB < 2^32: s <= 256 tiles of 8192 rows)
+            {
+                uint32_t c4[4], s4 = 0, live;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    c4[k] = ld_agent(&a.bins[threadIdx.x * 4 + k]);
+                    s4 += c4[k];
+                }
+                uint32_t start = block_exclusive_scan_n<PP_WAVES>(s4, sm.scan_tmp, &live);
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    bk.map[threadIdx.x * 4 + k] = (uint8_t)(start * NB / live);
+                    start += c4[k];
+                }
+            }
+            __syncthreads();
+            // C: this tile's rows per bucket (digit 255: its culled and padding rows)
+            count_wave_digits(sm, key, wbase0, P, digit);
+            __syncthreads();
+            if (d < RADIX_DIGITS) {
+                mytot = 0;
+#pragma unroll
+                for (int wv = 0; wv < PP_WAVES; wv++) mytot += sm.wtab[wv][d];
+                publish_counts(a.cnt + (size_t)BK_PASS * G * RADIX_DIGITS, a.grp + (size_t)BK_PASS * ngroups * RADIX_DIGITS, w,
+                               d, mytot);
+            }
+            GSR_TS(23);
+            if (!grid_barrier(a.sync, G, epoch, forever, &sm.flag)) { barrier_fault(a.done_word, 0x200u + epoch); return; }
+            GSR_TS(24);
+            // G: the one global pass
+            // (the offsets first and the ranking after the decision, so that a launch that falls back ranks nothing; the loads
+            // are not in flight during the ranking as they are in the LSD passes -- not measured, a microsecond or two)
+            uint32_t tot, run, before, total, all;
+            counts_before<PP_THREADS>(a.cnt + (size_t)BK_PASS * G * RADIX_DIGITS,
+                                      a.grp + (size_t)BK_PASS * ngroups * RADIX_DIGITS, G, w,
+                                      reinterpret_cast<uint32_t *>(red2), before, total);
+            // a bucket that one workgroup cannot hold (many equal depths, a few far outliers that stretch the bins): four
+            // passes, decided on the totals every workgroup has
+            if (__syncthreads_or(d < BK_TAIL && total > (uint32_t)BK_CAP)) {
+                buckets = false;
+            } else {
+                scatter_rank(sm, key, val, t0 * PP_TILE, P, digit, 8, tot, run);
+                const uint32_t dstart = block_exclusive_scan_n<PP_WAVES>(total, sm.scan_tmp, &all);
+                if (d == w) {
+                    bk.lo = dstart;
+                    bk.n = w < NB ? total : 0u;
+                }
+                if (d == BK_TAIL) bk.live = dstart;
+                bucket_scatter_write(sm, P - t0 * PP_TILE, digit, dstart + before, run, a.kB, a.vB, a.vA);
+            }
+        }
+        if (buckets) {
+            GSR_TS(25);
+            if (!grid_barrier(a.sync, G, epoch, forever, &sm.flag)) { barrier_fault(a.done_word, 0x200u + epoch); return; }
+            GSR_TS(26);
+            // L: workgroup w sorts bucket w and goes on into the scan with the ids it holds (LDS)
+            const uint32_t lo = bk.lo, n = bk.n, live = bk.live;
+            bucket_sort_span<PP_THREADS>(sm8, a.kB, a.vB, lo, n, reinterpret_cast<uint32_t *>(red2));
+#pragma unroll
+            for (int r = 0; r < BK_ITEMS; r++) {
+                const uint32_t i = r * PP_THREADS + threadIdx.x;
+                if (i < n) a.vA[lo + i] = sm8.sval[i];
+            }
+            uint32_t v[BK_ITEMS], hv[BK_ITEMS], s = 0, sh2 = 0;
+#pragma unroll
+            for (int k = 0; k < BK_ITEMS; k++) {  // eight CONSECUTIVE elements per thread
+                const uint32_t i = threadIdx.x * BK_ITEMS + k;
+                const uint32_t x = i < n ? ld_agent(&a.tt[sm8.sval[i]]) : 0u;
+                v[k] = a.tile_hist ? (x & TT_MASK) : x;
+                hv[k] = a.tile_hist ? (x >> TT_SHIFT) : 0u;
+                s += v[k];
+                sh2 += hv[k];
+            }
+            unsigned long long wsum = wave_sum64((unsigned long long)s | ((unsigned long long)sh2 << 32));
+            if (lane == 0) sm.scan64[wave] = wsum;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                unsigned long long tot = 0;
+                for (int wv = 0; wv < PP_WAVES; wv++) tot += sm.scan64[wv];
+                st_agent64(&a.wtot[w], tot);
+            }
+            GSR_TS(27);
+            if (!grid_barrier(a.sync, G, epoch, forever, &sm.flag)) { barrier_fault(a.done_word, 0x200u + epoch); return; }
+            GSR_TS(28);
+            if (w == 0 && threadIdx.x == 0 && a.done_seq)
+                __hip_atomic_store(a.done_word, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            // S: the sums of the buckets in front of this one, and of all of them (what the culled tail starts at)
+            unsigned long long carry, gtot;
+            {
+                unsigned long long x = 0, y = 0;
+                for (uint32_t k = threadIdx.x; k < G; k += PP_THREADS) {
+                    const unsigned long long t = ld_agent64(&a.wtot[k]);
+                    y += t;
+                    if (k < w) x += t;
+                }
+                x = wave_sum64(x);
+                y = wave_sum64(y);
+                __syncthreads();  // (scan64 was read above)
+                if (lane == 0) {
+                    sm.scan64[wave] = x;
+                    reinterpret_cast<unsigned long long *>(red2)[wave] = y;
+                }
+                __syncthreads();
+                carry = gtot = 0;
+                for (int wv = 0; wv < PP_WAVES; wv++) {
+                    carry += sm.scan64[wv];
+                    gtot += reinterpret_cast<unsigned long long *>(red2)[wv];
+                }
+            }
+            uint32_t tots, toth;
+            const uint32_t local = block_exclusive_scan_n<PP_WAVES>(s, sm.scan_tmp, &tots);
+            const uint32_t localh = block_exclusive_scan_n<PP_WAVES>(sh2, sm.scan_tmp, &toth);
+            uint32_t runp = (uint32_t)carry + local, runh = (uint32_t)(carry >> 32) + localh;
+#pragma unroll
+            for (int k = 0; k < BK_ITEMS; k++) {
+                const uint32_t i = threadIdx.x * BK_ITEMS + k;
+                if (i < n) {
+                    a.offsets[lo + i] = runp;
+                    a.segoff[lo + i] = runh;
+                }
+                runp += v[k];
+                runh += hv[k];
+            }
+            // the culled tail has no owner: its ids are in place since the global pass, its rows add nothing
+            for (long long j = (long long)live + (long long)w * PP_THREADS + threadIdx.x; j < P; j += (long long)G * PP_THREADS) {
+                a.offsets[j] = (uint32_t)gtot;
+                a.segoff[j] = (uint32_t)(gtot >> 32);
+            }
+            if (w == G - 1 && threadIdx.x == 0) {
+                a.offsets[P] = clamp_pair_count(__hip_atomic_load(a.early, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                a.segoff[P] = (uint32_t)(gtot >> 32);
+            }
+            GSR_TS(31);
+            return;
+        }
+        // fall-back: the counts of LSD pass 0, which phase T left out, from the keys in the registers -- one more barrier
+        __syncthreads();
+        clear_wtab(sm);
+        __syncthreads();
+        count_wave_digits(sm, key, wbase0, P, 0, 0xFFu);
+        __syncthreads();
+        if (d < RADIX_DIGITS) {
+            mytot = 0;
+#pragma unroll
+            for (int wv = 0; wv < PP_WAVES; wv++) mytot += sm.wtab[wv][d];
+            publish_counts(a.cnt, a.grp, w, d, mytot);
+        }
+        GSR_TS(17);
+        if (!grid_barrier(a.sync, G, epoch, forever, &sm.flag)) { barrier_fault(a.done_word, 0x200u + epoch); return; }
+        GSR_TS(18);
+    }
     for (int p = 0; p < 4; p++) {
         const int shift = 8 * p;
         uint32_t *const ksrc = (p & 1) ? a.kB : a.kA, *const vsrc = (p & 1) ? a.vB : a.vA;
@@ -760,12 +1149,17 @@ bin_prepare_persist_kernel(const PrepPersistArgs a) {
         if (keep && counts_fit_registers<PP_THREADS>(G)) {
             // one tile, its pairs and per-wave counts are in place: rank it while the counts of the other workgroups
             // travel (an agent-scope load is a trip to memory), then form the offsets and stream the tile out
+            // (the workgroup's number through an empty asm: the rows' addresses are then formed in the pass that uses them --
+            // kept over all four passes, and over the bucket path in front of them, they do not fit the 128 registers of
+            // a thread and were spilled)
+            uint32_t wp = w;
+            asm volatile("" : "+s"(wp));
             CountLoads cl;
-            counts_issue<PP_THREADS>(cnt_p, grp_p, G, w, cl);
+            counts_issue<PP_THREADS>(cnt_p, grp_p, G, wp, cl);
             uint32_t tot, run;
             scatter_rank(sm, key, val, t0 * PP_TILE, P, shift, 8, tot, run);
             // (the reduction scratch must not be the staging area: the ranked pairs are in it)
-            counts_finish<PP_THREADS>(cl, w, reinterpret_cast<uint32_t *>(red2), before, total);
+            counts_finish<PP_THREADS>(cl, wp, reinterpret_cast<uint32_t *>(red2), before, total);
             first = block_exclusive_scan_n<PP_WAVES>(total, sm.scan_tmp, &all) + before;
             scatter_write<PP_ITEMS, PP_THREADS, true>(sm, t0 * PP_TILE, P, shift, 8, first, run, kdst, vdst);
         } else {
@@ -1334,16 +1728,17 @@ bin_sort_persist_kernel(const SortPersistArgs a) {
 
 // ------------------------------------------------------------------------------------------ host side
 struct PersistLayoutP {  // inside the control block of the prepare workspace
-    size_t sync, grp, cnt, wtot, zero_bytes, total;
+    size_t sync, grp, bins, cnt, wtot, zero_bytes, total;
 };
 inline PersistLayoutP persist_layout_p(int G) {
     PersistLayoutP L;
     const int ngroups = (G + GB_FAN - 1) / GB_FAN;
     size_t o = 0;
     L.sync = o; o += align_up(sizeof(uint32_t) * grid_sync_words(G));
-    L.grp = o; o += align_up(sizeof(uint32_t) * 4 * (size_t)ngroups * RADIX_DIGITS);
+    L.grp = o; o += align_up(sizeof(uint32_t) * (BK_PASS + 1) * (size_t)ngroups * RADIX_DIGITS);
+    L.bins = o; o += align_up(sizeof(uint32_t) * (BK_BINS + 2));  // bin counts, { ~min, max } key (bucket path)
     L.zero_bytes = o;  // [0, zero_bytes) is cleared before every launch
-    L.cnt = o; o += align_up(sizeof(uint32_t) * 4 * (size_t)G * RADIX_DIGITS);
+    L.cnt = o; o += align_up(sizeof(uint32_t) * (BK_PASS + 1) * (size_t)G * RADIX_DIGITS);
     L.wtot = o; o += align_up(sizeof(unsigned long long) * (size_t)G);
     L.total = o;
     return L;
@@ -1403,8 +1798,8 @@ std::atomic<int> g_persist_override{-1};  // gsr_set_bin_persistent: -1 = enviro
 unsigned long long *g_timeline[2] = {nullptr, nullptr};
 int g_timeline_grid[2] = {0, 0};
 unsigned long long *timeline_buffer(int which, int G) {
-    static const bool on = [] { const char *e = getenv("GSR_BIN_TIMELINE"); return e && *e == '1'; }();
-    if (!on) return nullptr;
+    const char *e = getenv("GSR_BIN_TIMELINE");  // (read per call: a test switches it on for the launches it looks at)
+    if (!(e && *e == '1')) return nullptr;
     if (!g_timeline[which]) {
         void *p = nullptr;
         if (hipMalloc(&p, sizeof(unsigned long long) * 32 * PERSIST_MAX_GRID_S) != hipSuccess) return nullptr;

@@ -25,11 +25,18 @@ for p in range(4):
     if p < 3:
         P_NAMES[5 + 4 * p] = f"A{p + 1} (load + count)"
         P_NAMES[6 + 4 * p] = "barrier"
+# the depth sort by buckets (the default): bins, splitters + bucket counts, ONE global pass, the workgroup-local sort of a
+# bucket with its tile-count sums, offsets.  17 / 18 are stamped only when a launch left that path for the four passes above
+# (a bucket too large for a workgroup, or nothing live), 21-28 only on the bucket path.
+P_NAMES.update({17: "fall-back: recount of pass 0", 18: "barrier (fall-back)", 21: "B (key bins)", 22: "barrier",
+                23: "M + C (splitters, bucket counts)", 24: "barrier", 25: "G (global bucket pass)", 26: "barrier",
+                27: "L + S1 (local sort, tile-count sums)", 28: "barrier"})
+P_ORDER = [0, 1, 2, 21, 22, 23, 24, 25, 26, 27, 28, 17, 18] + list(range(3, 17)) + [19, 20, 31]
 S_NAMES = {0: "start", 1: "E0 (column counts from rects)", 2: "barrier", 3: "E1 (decode + scatter by column)", 4: "barrier",
            5: "R0 (count rows)", 6: "barrier", 7: "R1 (scatter by row)", 8: "barrier", 9: "T (tile ranges)"}
 
 
-def report(which, names):
+def report(which, names, order=None):
     grid = ctypes.c_int(0)
     buf = np.zeros(4096 * 32, dtype=np.uint64)
     rc = dgr.lib.gsr_bin_timeline(which, buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(grid))
@@ -40,7 +47,8 @@ def report(which, names):
         return
     t = buf[:G * 32].reshape(G, 32).astype(np.float64) / 100.0  # us
     t0 = t[:, 0][t[:, 0] > 0].min()
-    keys = sorted(names)
+    # the phases in the order the kernel runs them, those the launch did not stamp left out
+    keys = [k for k in (order or sorted(names)) if (t[:, k] > 0).any()]
     print(f"  grid {G} workgroups; starts spread over {t[:, 0].max() - t0:.1f} us")
     prev = keys[0]
     for k in keys[1:]:
@@ -59,6 +67,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--band", type=int, nargs=2, default=None)
     ap.add_argument("--view", type=int, default=0)
+    ap.add_argument("--equal-depths", action="store_true", help="one depth for every Gaussian: the bucket path falls back")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H = a.width, a.height
@@ -70,6 +79,8 @@ def main():
     with torch.no_grad():
         m2, rgb, co, radii, depths = dgr.GaussianRasterizer(rs).preprocess_gaussians(
             g["means3D"], g["scales"], g["rotations"], g["shs"], g["opacities"], {})
+    if a.equal_depths:
+        depths = torch.full_like(depths, 3.25)
     gx, gy = (W + 15) // 16, (H + 15) // 16
     mask = torch.ones(gy, gx, dtype=torch.uint8, device=dev)
     if a.band:
@@ -83,7 +94,7 @@ def main():
         torch.cuda.synchronize()
     print(f"P = {m2.shape[0]}, D = {D}, {W}x{H}, band {a.band}")
     print("prepare kernel:")
-    report(0, P_NAMES)
+    report(0, P_NAMES, P_ORDER)
     print("sort kernel:")
     report(1, S_NAMES)
 
