@@ -10,9 +10,16 @@
 //                    into compacted tensors (prune), into the columns of ONE record matrix that a single
 //                    all-to-all-v redistributes (the reference's disabled "implementation_2",
 //                    scene/gaussian_model.py:1206-1238), or back out of it.
+// and, on top of the same idea, the whole densification event as two launches (bottom of this file):
+//   gsr_densify_plan: one single-sweep scan over a class byte per row -> ranks in four categories + four counts;
+//   gsr_densify_move: one launch writes every row of the clone / split / prune result for all tensors.
 #include "common.h"
 
 #include "radix.h"
+
+// no FMA contraction in this file: a split child's position is evaluated with the roundings of the reference's elementwise
+// torch expressions (child_rotation_row below); the only fused operation left is the explicit fmaf of densify_stats_kernel
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -208,4 +215,321 @@ extern "C" int gsr_scatter_rows(int64_t n_in, const int32_t *order, int num_tens
     if (n_in > 0 && !order) return GSR_EINVAL;
     return launch_rows(true, n_in, order, num_tensors, srcs, dsts, widths, src_strides, dst_strides,
                        reinterpret_cast<hipStream_t>(stream_));
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// One-pass densification event.  The reference's clone -> split -> prune sequence (scene/gaussian_model.py:789-921 the
+// row surgery, :922-1044 densify_and_split / densify_and_clone / densify_and_prune) has a closed-form result in terms of
+// the ORIGINAL rows: [kept originals | kept clones | first children | second children], original order inside each
+// segment (DESIGN.md "One-pass densification").  The host classifies every row into a byte; the plan ranks the rows of
+// the four categories in one sweep and the move writes every destination row of every tensor from the plan.
+namespace {
+
+constexpr int PLAN_THREADS = 256, PLAN_ITEMS = 8, PLAN_TILE = PLAN_THREADS * PLAN_ITEMS, PLAN_WAVES = PLAN_THREADS / 64;
+constexpr int PLAN_CATS = 4;
+// category order of ranks[] and counts[] (the class bit each one tests): kept original, kept clone, parent whose
+// children are kept, split parent
+__host__ __device__ constexpr uint32_t plan_bit(int c) {
+    return c == 0 ? GSR_DENSIFY_KEEP_ORIGINAL : c == 1 ? GSR_DENSIFY_KEEP_CLONE
+         : c == 2 ? GSR_DENSIFY_KEEP_CHILDREN : GSR_DENSIFY_SPLIT_PARENT;
+}
+
+struct PlanLayout {
+    size_t ticket, state, total;
+    long long tiles;
+};
+PlanLayout plan_layout(long long P) {
+    PlanLayout L;
+    L.tiles = (P + PLAN_TILE - 1) / PLAN_TILE;
+    L.ticket = 0;
+    L.state = 256;
+    L.total = L.state + (((size_t)(L.tiles > 0 ? L.tiles : 1) * PLAN_CATS * sizeof(uint32_t) + 255) & ~(size_t)255);
+    return L;
+}
+
+// Single-sweep scan, decoupled look-back on the state words of radix.h (0 = nothing yet, bit 31 = inclusive prefix,
+// otherwise aggregate + 1; an aggregate is at most PLAN_TILE).  Tiles are taken by ticket, so every tile a workgroup
+// looks back at is held by a workgroup that already runs.  Wave w owns PLAN_ITEMS consecutive rounds of 64 rows; the rank
+// of a row inside its wave's chunk is (rows of the earlier rounds) + popcount(ballot below the lane), one ballot per
+// category.
+__global__ void __launch_bounds__(PLAN_THREADS)
+densify_plan_kernel(long long P, const uint8_t *__restrict__ cls, int32_t *__restrict__ ranks,
+                    int32_t *__restrict__ split_rows, int64_t *__restrict__ counts, uint32_t *__restrict__ ticket,
+                    uint32_t *__restrict__ state, uint32_t tiles) {
+    __shared__ uint32_t s_bid;
+    __shared__ uint32_t s_wave[PLAN_WAVES][PLAN_CATS];  // totals, then exclusive offsets of the waves inside the tile
+    __shared__ uint32_t s_base[PLAN_CATS];
+    if (threadIdx.x == 0) s_bid = atomicAdd(ticket, 1u);
+    __syncthreads();
+    const uint32_t bid = s_bid;
+    if (bid >= tiles) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const long long wbase = (long long)bid * PLAN_TILE + (long long)wave * (PLAN_ITEMS * 64);
+    uint8_t code[PLAN_ITEMS];
+    uint16_t local[PLAN_ITEMS][PLAN_CATS];
+    uint32_t run[PLAN_CATS] = {0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < PLAN_ITEMS; r++) {
+        const long long j = wbase + r * 64 + lane;
+        code[r] = j < P ? cls[j] : (uint8_t)0;
+#pragma unroll
+        for (int c = 0; c < PLAN_CATS; c++) {
+            const unsigned long long m = __ballot((code[r] & plan_bit(c)) != 0);
+            local[r][c] = (uint16_t)(run[c] + (uint32_t)__popcll(m & lt));
+            run[c] += (uint32_t)__popcll(m);
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < PLAN_CATS; c++) s_wave[wave][c] = run[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < PLAN_CATS) {
+        const int c = threadIdx.x;
+        uint32_t tot = 0;
+        for (int w = 0; w < PLAN_WAVES; w++) {
+            const uint32_t v = s_wave[w][c];
+            s_wave[w][c] = tot;
+            tot += v;
+        }
+        st_agent(&state[(size_t)bid * PLAN_CATS + c], bid == 0 ? (tot | LB_PRE) : (tot + 1u));
+        uint32_t excl = 0;
+        if (bid > 0) {
+            long long j = (long long)bid - 1;
+            for (;;) {
+                uint32_t x = ld_agent(&state[(size_t)j * PLAN_CATS + c]);
+                while (x == 0u) {
+                    __builtin_amdgcn_s_sleep(1);
+                    x = ld_agent(&state[(size_t)j * PLAN_CATS + c]);
+                }
+                if (x & LB_PRE) {
+                    excl += x & LB_VAL;
+                    break;
+                }
+                excl += x - 1u;
+                j--;
+            }
+            st_agent(&state[(size_t)bid * PLAN_CATS + c], ((excl + tot) & LB_VAL) | LB_PRE);
+        }
+        s_base[c] = excl;
+        if (bid == tiles - 1) counts[c] = (int64_t)(excl + tot);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < PLAN_ITEMS; r++) {
+        const long long j = wbase + r * 64 + lane;
+        if (j < P) {
+#pragma unroll
+            for (int c = 0; c < PLAN_CATS; c++) {
+                const uint32_t rk = s_base[c] + s_wave[wave][c] + local[r][c];
+                ranks[(size_t)c * P + j] = (int32_t)rk;
+                if (c == 3 && split_rows && (code[r] & GSR_DENSIFY_SPLIT_PARENT)) split_rows[rk] = (int32_t)j;
+            }
+        }
+    }
+}
+
+constexpr int MOVE_THREADS = 256, MOVE_ROWS = 256;  // rows per workgroup and round
+constexpr int MOVE_UNROLL = 4;                      // words a thread has in flight
+constexpr int MOVE_MAX_WIDTH = 1 << 20;             // MOVE_ROWS * width stays far inside 32 bits
+
+struct MoveArgs {
+    const uint32_t *src[GATHER_MAX_TENSORS];
+    const uint32_t *alt[GATHER_MAX_TENSORS];
+    uint32_t *dst[GATHER_MAX_TENSORS];
+    int32_t width[GATHER_MAX_TENSORS], role[GATHER_MAX_TENSORS];
+    int64_t src_stride[GATHER_MAX_TENSORS], dst_stride[GATHER_MAX_TENSORS];  // in words
+};
+
+// row `c` of R(q) exactly as the reference's build_rotation (utils/general_utils.py:416-439) evaluates it elementwise:
+// the norm with a correctly rounded sqrtf, true divisions, every product and sum rounded on its own (contraction is off
+// in this file, no fast-math)
+__device__ __forceinline__ void child_rotation_row(int c, const float *__restrict__ q4, float &r0, float &r1, float &r2) {
+    const float a = q4[0], b = q4[1], cc = q4[2], d = q4[3];
+    const float norm = sqrtf(a * a + b * b + cc * cc + d * d);
+    const float w = a / norm, x = b / norm, y = cc / norm, z = d / norm;
+    if (c == 0) {
+        r0 = 1.0f - 2.0f * (y * y + z * z);
+        r1 = 2.0f * (x * y - w * z);
+        r2 = 2.0f * (x * z + w * y);
+    } else if (c == 1) {
+        r0 = 2.0f * (x * y + w * z);
+        r1 = 1.0f - 2.0f * (x * x + z * z);
+        r2 = 2.0f * (y * z - w * x);
+    } else {
+        r0 = 2.0f * (x * z - w * y);
+        r1 = 2.0f * (y * z + w * x);
+        r2 = 1.0f - 2.0f * (x * x + y * y);
+    }
+}
+
+// A workgroup takes MOVE_ROWS consecutive SOURCE rows per round: one thread per row turns class + ranks into the
+// destination rows (LDS), then for every tensor one thread per 4-byte word of those rows reads the word once and writes
+// it wherever the row goes.  Consecutive threads hold consecutive words of consecutive rows, and the kept rows of a
+// segment land on consecutive destination rows, so reads are coalesced and writes are coalesced runs.
+__global__ void __launch_bounds__(MOVE_THREADS)
+densify_move_kernel(long long P, const uint8_t *__restrict__ cls, const int32_t *__restrict__ ranks, long long n_orig,
+                    long long n_clone, long long n_child, long long n_split, int copies, int num_tensors,
+                    const float *__restrict__ rotation, const float *__restrict__ samples, MoveArgs a) {
+    __shared__ long long s_orig[MOVE_ROWS], s_clone[MOVE_ROWS], s_child[MOVE_ROWS];
+    __shared__ int32_t s_sample[MOVE_ROWS];
+    __shared__ uint8_t s_kind[MOVE_ROWS];  // bit 0: the original stays, bit 1: a clone, bit 2: children; 0: dropped
+    const long long child0 = n_orig + n_clone;
+    const long long rounds = (P + MOVE_ROWS - 1) / MOVE_ROWS;
+    for (long long rd = blockIdx.x; rd < rounds; rd += gridDim.x) {
+        const long long base = rd * MOVE_ROWS;
+        const int nrows = (int)(P - base < MOVE_ROWS ? P - base : MOVE_ROWS);
+        if ((int)threadIdx.x < nrows) {
+            const long long i = base + threadIdx.x;
+            const uint8_t code = cls[i];
+            long long o = -1, c = -1, ch = -1;
+            int32_t sj = 0;
+            // (a destination outside the result -- class bytes that do not belong to this plan -- is dropped, never written)
+            if (code & GSR_DENSIFY_KEEP_ORIGINAL) {
+                o = ranks[i];
+                if (o >= n_orig) o = -1;
+            }
+            if (code & GSR_DENSIFY_KEEP_CLONE) {
+                c = n_orig + ranks[(size_t)P + i];
+                if (c >= child0) c = -1;
+            }
+            if ((code & GSR_DENSIFY_KEEP_CHILDREN) && (code & GSR_DENSIFY_SPLIT_PARENT)) {
+                const long long rk = ranks[(size_t)2 * P + i];
+                sj = ranks[(size_t)3 * P + i];
+                if (rk < n_child && (long long)sj < n_split) ch = child0 + rk;
+            }
+            s_orig[threadIdx.x] = o;
+            s_clone[threadIdx.x] = c;
+            s_child[threadIdx.x] = ch;
+            s_sample[threadIdx.x] = sj;
+            s_kind[threadIdx.x] = (uint8_t)((o >= 0 ? 1 : 0) | (c >= 0 ? 2 : 0) | (ch >= 0 ? 4 : 0));
+        }
+        __syncthreads();
+        for (int k = 0; k < num_tensors; k++) {
+            const uint32_t w = (uint32_t)a.width[k];
+            const int role = a.role[k];
+            const uint32_t *__restrict__ src = a.src[k];
+            uint32_t *__restrict__ dst = a.dst[k];
+            const int64_t ss = a.src_stride[k], ds = a.dst_stride[k];
+            const uint32_t total = (uint32_t)nrows * w;
+            // word t of the round is (row t / w, column t % w); a thread's words are MOVE_THREADS apart, so row and column
+            // advance by a constant with at most one carry: one division per tensor instead of one per word
+            const uint32_t q = MOVE_THREADS / w, rem = MOVE_THREADS % w;
+            uint32_t r = threadIdx.x / w, col = threadIdx.x - r * w;
+            for (uint32_t t = threadIdx.x; t < total; t += MOVE_UNROLL * MOVE_THREADS) {
+                uint32_t rr[MOVE_UNROLL], cc[MOVE_UNROLL], v[MOVE_UNROLL];
+                uint8_t kind[MOVE_UNROLL];
+#pragma unroll
+                for (int u = 0; u < MOVE_UNROLL; u++) {  // all loads of the group first
+                    rr[u] = r;
+                    cc[u] = col;
+                    kind[u] = t + (uint32_t)u * MOVE_THREADS < total ? s_kind[r] : (uint8_t)0;
+                    // a dropped row is not even read, nor is a moment row whose original goes (its new rows are zero)
+                    v[u] = (kind[u] & (role == GSR_DENSIFY_ROLE_MOMENT ? 1 : 7)) ? src[(base + r) * ss + col] : 0u;
+                    col += rem;
+                    r += q;
+                    if (col >= w) {
+                        col -= w;
+                        r++;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < MOVE_UNROLL; u++) {
+                    if (kind[u] & 1) dst[s_orig[rr[u]] * ds + cc[u]] = v[u];
+                    if (kind[u] & 2) dst[s_clone[rr[u]] * ds + cc[u]] = role == GSR_DENSIFY_ROLE_MOMENT ? 0u : v[u];
+                    if (kind[u] & 4) {
+                        const long long i = base + rr[u], ch = s_child[rr[u]];
+                        uint32_t cv = v[u];
+                        if (role == GSR_DENSIFY_ROLE_MOMENT) cv = 0u;
+                        else if (role == GSR_DENSIFY_ROLE_SCALING) cv = a.alt[k][i * 3 + cc[u]];
+                        float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+                        if (role == GSR_DENSIFY_ROLE_XYZ) child_rotation_row((int)cc[u], rotation + i * 4, r0, r1, r2);
+                        for (int cp = 0; cp < copies; cp++) {
+                            if (role == GSR_DENSIFY_ROLE_XYZ) {  // R . sample + xyz, the dot summed left to right
+                                const float *s3 = samples + ((long long)cp * n_split + s_sample[rr[u]]) * 3;
+                                cv = __float_as_uint(r0 * s3[0] + r1 * s3[1] + r2 * s3[2] + __uint_as_float(v[u]));
+                            }
+                            dst[(ch + (long long)cp * n_child) * ds + cc[u]] = cv;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+}  // namespace
+
+extern "C" size_t gsr_densify_plan_bytes(int64_t P) {
+    if (P < 0) return 0;
+    return plan_layout(P).total;
+}
+
+extern "C" int gsr_densify_plan(int64_t P, const uint8_t *cls, int32_t *ranks, int32_t *split_rows, int64_t *counts,
+                                void *workspace, size_t workspace_bytes, gsr_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (P < 0 || P > RADIX_MAX_N) return GSR_EINVAL;
+    if (P == 0) {
+        if (counts) GSR_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * PLAN_CATS, stream));
+        return 0;
+    }
+    if (!cls || !ranks || !counts || !workspace) return GSR_EINVAL;
+    const PlanLayout L = plan_layout(P);
+    if (workspace_bytes < L.total) return GSR_ENOSPACE;
+    char *base = reinterpret_cast<char *>(workspace);
+    GSR_HIP(hipMemsetAsync(base, 0, L.total, stream));
+    hipLaunchKernelGGL(densify_plan_kernel, dim3((unsigned)L.tiles), dim3(PLAN_THREADS), 0, stream, (long long)P, cls,
+                       ranks, split_rows, counts, reinterpret_cast<uint32_t *>(base + L.ticket),
+                       reinterpret_cast<uint32_t *>(base + L.state), (uint32_t)L.tiles);
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int gsr_densify_move(int64_t P, const uint8_t *cls, const int32_t *ranks, int64_t n_orig, int64_t n_clone,
+                                int64_t n_child, int64_t n_split, int copies, int num_tensors,
+                                const void *const *srcs, void *const *dsts, const void *const *alts,
+                                const int32_t *widths, const int32_t *roles, const int64_t *src_strides,
+                                const int64_t *dst_strides, int64_t dst_rows, const float *rotation,
+                                const float *samples, gsr_stream_t stream_) {
+    if (P < 0 || P > RADIX_MAX_N || n_orig < 0 || n_clone < 0 || n_child < 0 || n_split < 0 || copies < 1 ||
+        copies > 16 || num_tensors < 0 || num_tensors > GATHER_MAX_TENSORS || dst_rows < 0)
+        return GSR_EINVAL;
+    if (n_orig > P || n_clone > P || n_split > P || n_child > n_split) return GSR_EINVAL;
+    if (n_orig + n_clone + (int64_t)copies * n_child > dst_rows) return GSR_EINVAL;
+    if (P == 0 || num_tensors == 0) return 0;
+    if (!cls || !ranks || !srcs || !dsts || !widths || !roles || !src_strides || !dst_strides) return GSR_EINVAL;
+    MoveArgs a{};
+    for (int k = 0; k < num_tensors; k++) {
+        if (!srcs[k] || !dsts[k] || widths[k] <= 0 || widths[k] > MOVE_MAX_WIDTH) return GSR_EINVAL;
+        if (src_strides[k] < widths[k] || dst_strides[k] < widths[k]) return GSR_EINVAL;
+        switch (roles[k]) {
+        case GSR_DENSIFY_ROLE_COPY:
+        case GSR_DENSIFY_ROLE_MOMENT:
+            break;
+        case GSR_DENSIFY_ROLE_XYZ:
+            if (widths[k] != 3 || (n_child > 0 && (!rotation || !samples))) return GSR_EINVAL;
+            break;
+        case GSR_DENSIFY_ROLE_SCALING:
+            if (widths[k] != 3 || !alts || !alts[k]) return GSR_EINVAL;
+            break;
+        default:
+            return GSR_EINVAL;
+        }
+        a.src[k] = reinterpret_cast<const uint32_t *>(srcs[k]);
+        a.dst[k] = reinterpret_cast<uint32_t *>(dsts[k]);
+        a.alt[k] = alts ? reinterpret_cast<const uint32_t *>(alts[k]) : nullptr;
+        a.width[k] = widths[k];
+        a.role[k] = roles[k];
+        a.src_stride[k] = src_strides[k];
+        a.dst_stride[k] = dst_strides[k];
+    }
+    long long blocks = (P + MOVE_ROWS - 1) / MOVE_ROWS;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(densify_move_kernel, dim3((unsigned)blocks), dim3(MOVE_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream_), (long long)P, cls, ranks, (long long)n_orig,
+                       (long long)n_clone, (long long)n_child, (long long)n_split, copies, num_tensors,
+                       rotation, samples, a);
+    GSR_LAUNCH_CHECK();
+    return 0;
 }

@@ -19,8 +19,12 @@ _features_dc, _features_rest, _opacity, _scaling, _rotation`, `optimizer` (one g
 xyz / f_dc / f_rest / opacity / scaling / rotation), the statistics `xyz_gradient_accum, denom, max_radii2D,
 sum_visible_count_in_one_batch, send_to_gpui_cnt`, `percent_dense`, and the getters.
 There is no CPU fallback: the tensors live on the gfx950 device.
+
+Opt-in (`GSR_FUSED_DENSIFY=1` or `set_fused_densify(True)`): `densify_and_prune` as ONE pass over reserved row storage
+-- `densify_and_prune_fused` below, DESIGN.md "One-pass densification".
 """
 import math
+import os
 
 import torch
 import torch.distributed as dist
@@ -28,6 +32,7 @@ from torch import nn
 
 import diff_gaussian_rasterization as dgr
 import utils.general_utils as utils
+from row_arena import RowArena
 
 _ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity",
          "scaling": "_scaling", "rotation": "_rotation"}
@@ -182,7 +187,7 @@ def densify_and_split(self, grads, grad_threshold, scene_extent, N=2):
     prune_points(self, prune_filter)
 
 
-def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
+def _sync_replicated_statistics(self):
     args = utils.get_args()
     if not getattr(args, "gaussians_distribution", True) and utils.DEFAULT_GROUP.size() > 1:
         # replicated storage (scene/gaussian_model.py:1006-1016): every rank saw only its own pixels, so the replicas
@@ -191,6 +196,17 @@ def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
         dist.all_reduce(self.max_radii2D, op=dist.ReduceOp.MAX, group=group)
         dist.all_reduce(self.xyz_gradient_accum, op=dist.ReduceOp.SUM, group=group)
         dist.all_reduce(self.denom, op=dist.ReduceOp.SUM, group=group)
+
+
+def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
+    if fused_densify_enabled():
+        return densify_and_prune_fused(self, max_grad, min_opacity, extent, max_screen_size)
+    _sync_replicated_statistics(self)
+    _densify_and_prune_steps(self, max_grad, min_opacity, extent, max_screen_size)
+
+
+def _densify_and_prune_steps(self, max_grad, min_opacity, extent, max_screen_size):
+    """clone, split, prune one after the other, as the reference orders them"""
     grads = self.xyz_gradient_accum / self.denom
     grads[grads.isnan()] = 0.0
     densify_and_clone(self, grads, max_grad, extent)
@@ -201,6 +217,128 @@ def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
         big_points_ws = self.get_scaling.max(dim=1).values > 0.1 * extent
         prune_mask = torch.logical_or(torch.logical_or(prune_mask, big_points_vs), big_points_ws)
     prune_points(self, prune_mask)
+
+
+# ------------------------------------------------------------------------ one-pass densification
+# The clone -> split -> prune sequence above has a closed-form result in terms of the ORIGINAL rows (DESIGN.md
+# "One-pass densification"): [kept originals | kept clones | first children | second children], original order inside
+# each segment.  The rows are classified with the model's own getters (plain torch, any device), ranked by one scan
+# (gsr_densify_plan), and written for all tensors by one launch (gsr_densify_move) from one half of a RowArena into the
+# other: no torch.cat, no boolean indexing, one host read-back.
+_FUSED = [None]  # None: the environment decides
+
+
+def set_fused_densify(on):
+    """True / False: densify_and_prune takes / does not take the one-pass path; None: GSR_FUSED_DENSIFY decides"""
+    _FUSED[0] = None if on is None else bool(on)
+
+
+def fused_densify_enabled():
+    if _FUSED[0] is not None:
+        return _FUSED[0]
+    return os.environ.get("GSR_FUSED_DENSIFY", "0") not in ("", "0")  # read at call time
+
+
+def densify_classes(self, max_grad, min_opacity, extent, max_screen_size, N=2):
+    """-> (cls uint8 [P], child_scaling [P,3], get_scaling [P,3]): what the reference's densify_and_prune does to every ORIGINAL row, in the
+    expressions of densify_and_clone / densify_and_split / densify_and_prune applied to the model's own getters
+    (scene/gaussian_model.py:922-1044), so the selection is the reference's whatever the activations are.
+    Bits: 1 the original stays, 2 a clone is appended, 4 the row is split, 8 its children survive the final prune.
+    child_scaling = scaling_inverse_activation(get_scaling / (0.8 N)), the children's raw scale (:940), through the
+    model's own inverse activation / activation where it names them (log / exp otherwise).  The final prune's
+    `max_radii2D > max_screen_size` never fires (densification_postfix zeroes max_radii2D first) and is left out;
+    clones carry gradient 0 in the split step, so they are never split for max_grad > 0 (the caller's precondition)."""
+    grads = self.xyz_gradient_accum / self.denom
+    grads[grads.isnan()] = 0.0
+    scaling = self.get_scaling
+    s = torch.max(scaling, dim=1).values
+    clone = torch.logical_and(torch.norm(grads, dim=-1) >= max_grad, s <= self.percent_dense * extent)
+    split = torch.logical_and(grads.reshape(-1) >= max_grad, s > self.percent_dense * extent)
+    child_scaling = getattr(self, "scaling_inverse_activation", torch.log)(scaling / (0.8 * N))
+    drop = (self.get_opacity < min_opacity).reshape(-1)
+    drop_child = drop
+    if max_screen_size:
+        # the getter's view of the children's new raw parameter: the model's own activation where it names one
+        act = getattr(self, "scaling_activation", torch.exp)
+        drop_child = torch.logical_or(drop, act(child_scaling).max(dim=1).values > 0.1 * extent)
+        drop = torch.logical_or(drop, s > 0.1 * extent)
+    keep, keep_child = ~drop, ~drop_child
+    cls = (~split & keep).to(torch.uint8)
+    cls += (clone & keep).to(torch.uint8) * 2
+    cls += split.to(torch.uint8) * 4
+    cls += (split & keep_child).to(torch.uint8) * 8
+    return cls, child_scaling, scaling
+
+
+def _has_adam_state(self):
+    for group in self.optimizer.param_groups:
+        st = self.optimizer.state.get(group["params"][0], None)
+        if st is None or "exp_avg" not in st or "exp_avg_sq" not in st:
+            return False
+    return True
+
+
+def row_arena(self, capacity=None):
+    """the model's RowArena, created at the first one-pass event (or here, e.g. with an explicit capacity)"""
+    arena = getattr(self, "_row_arena", None)
+    if arena is None:
+        arena = self._row_arena = RowArena(self._xyz.shape[0], self._xyz.device, capacity)
+    return arena
+
+
+_ROLE = {"xyz": dgr.DENSIFY_ROLE_XYZ, "scaling": dgr.DENSIFY_ROLE_SCALING}
+
+
+@torch.no_grad()
+def densify_and_prune_fused(self, max_grad, min_opacity, extent, max_screen_size, N=2):
+    """densify_and_prune (scene/gaussian_model.py:1007-1044) as one pass: same arguments, same result -- bit for bit,
+    except that a child's position is R . sample + xyz evaluated by the move kernel instead of torch.bmm (a few ulp).
+    Falls back to the step-by-step path when max_grad <= 0 (clones could then be split) or the optimizer has no Adam
+    moments yet."""
+    _sync_replicated_statistics(self)
+    if not max_grad > 0 or not _has_adam_state(self):
+        return _densify_and_prune_steps(self, max_grad, min_opacity, extent, max_screen_size)
+    cls, child_scaling, scaling = densify_classes(self, max_grad, min_opacity, extent, max_screen_size, N)
+    P, dev = cls.shape[0], cls.device
+    arena = row_arena(self)
+    cap = max(P, arena.capacity)  # (the plan's buffers are reserved for the capacity, like the rows)
+    ranks, split_rows, counts = dgr.densify_plan(
+        cls, arena.scratch("ranks", 4 * cap, torch.int32), arena.scratch("split_rows", cap, torch.int32),
+        arena.scratch("plan", dgr.lib.gsr_densify_plan_bytes(cap), torch.uint8))
+    n_orig, n_clone, n_child, n_split = counts.cpu().tolist()  # THE host read-back of the event
+    _log("Number of cloned gaussians kept: {}\n".format(n_clone))
+    _log("Number of split gaussians: {}\n".format(n_split))
+    # the reference's draw (:933-936), same call on the same device -> the same bits: the standard deviations are the
+    # scales of the split rows in row order, repeated N times
+    stds = scaling.index_select(0, split_rows[:n_split]).repeat(N, 1)
+    samples = torch.normal(mean=torch.zeros((stds.size(0), 3), device=dev), std=stds)
+    n_new = n_orig + n_clone + N * n_child
+    slots = _optimizer_slots(self)
+    srcs = [_slot_tensor(self, g, k) for g, k in slots]
+    keys = [(g["name"], k) for g, k in slots]
+    roles = [dgr.DENSIFY_ROLE_MOMENT if k is not None else _ROLE.get(g["name"], dgr.DENSIFY_ROLE_COPY) for g, k in slots]
+    alts = [child_scaling if r == dgr.DENSIFY_ROLE_SCALING else None for r in roles]
+    cnt = getattr(self, "send_to_gpui_cnt", None)
+    if cnt is not None:
+        srcs.append(cnt)
+        keys.append(("send_to_gpui_cnt", None))
+        roles.append(dgr.DENSIFY_ROLE_COPY)
+        alts.append(None)
+    srcs = [t.detach().contiguous() for t in srcs]
+    dsts = [arena.destination(key, t, n_new) for key, t in zip(keys, srcs)]
+    dgr.densify_move(cls, ranks, (n_orig, n_clone, n_child, n_split), srcs, dsts, roles, alts,
+                     self._rotation.detach().contiguous(), samples, copies=N)
+    views = [d[:n_new] for d in dsts]
+    _replace_optimizer_rows(self, slots, views[:len(slots)])
+    if cnt is not None:
+        self.send_to_gpui_cnt = views[-1]
+    for key, v in zip(keys, views):
+        arena.release_other(key, v)
+    self.xyz_gradient_accum = arena.zeros("xyz_gradient_accum", n_new, (1,))
+    self.denom = arena.zeros("denom", n_new, (1,))
+    self.max_radii2D = arena.zeros("max_radii2D", n_new)
+    self.sum_visible_count_in_one_batch = arena.zeros("sum_visible_count_in_one_batch", n_new)
+    arena.events += 1
 
 
 # --------------------------------------------------------------------------------- redistribution
@@ -336,8 +474,8 @@ def reset_opacity(self):
 def install(cls):
     """graft level B3: make these functions the methods of the reference's GaussianModel class"""
     for fn in (prune_points, cat_tensors_to_optimizer, densification_postfix, densify_and_clone, densify_and_split,
-               densify_and_prune, need_redistribute_gaussians, redistribute_gaussians, add_densification_stats,
-               update_densification_stats,
+               densify_and_prune, densify_and_prune_fused, need_redistribute_gaussians, redistribute_gaussians,
+               add_densification_stats, update_densification_stats,
                replace_tensor_to_optimizer, reset_opacity):
         setattr(cls, fn.__name__, fn)
     return cls

@@ -28,7 +28,7 @@ from ._lib import check, lib
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "_C", "load_image_tiles_by_pos",
            "merge_image_tiles_by_pos", "set_timing_mode", "fused_l1_ssim_band", "fused_band_loss", "fused_activations", "pack_camera",
-           "preprocess_gaussians_raw_batched", "knn_mean_dist2", "group_rows", "gather_rows", "exchange_need",
+           "preprocess_gaussians_raw_batched", "knn_mean_dist2", "group_rows", "gather_rows", "densify_plan", "densify_move", "exchange_need",
            "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "densify_stats",
            "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing"]
 
@@ -1627,6 +1627,94 @@ def gather_rows(order, n_out, srcs, dsts=None, row0=0, _scatter=False):
     check(fn(n_out, order_ptr, K, VP(*[s_.data_ptr() for s_ in srcs]), VP(*[d_.data_ptr() for d_ in dsts]),
              (ctypes.c_int32 * K)(*widths), (ctypes.c_int64 * K)(*ss), (ctypes.c_int64 * K)(*ds), _stream()), what)
     return dsts
+
+
+DENSIFY_KEEP_ORIGINAL, DENSIFY_KEEP_CLONE, DENSIFY_SPLIT_PARENT, DENSIFY_KEEP_CHILDREN = 1, 2, 4, 8  # class bits
+DENSIFY_ROLE_COPY, DENSIFY_ROLE_MOMENT, DENSIFY_ROLE_XYZ, DENSIFY_ROLE_SCALING = 0, 1, 2, 3
+
+
+def densify_plan(cls, ranks=None, split_rows=None, workspace=None):
+    """the plan of a one-pass densification event (include/gsraster.h: gsr_densify_plan): cls uint8 [P] class bytes ->
+    (ranks int32 [4,P], split_rows int32 [P], counts int64 [4] ON THE DEVICE = n_orig, n_clone, n_child, n_split).
+    No host read-back here: the caller reads the four counts once.  ranks / split_rows / workspace: buffers to reuse
+    (at least P rows / gsr_densify_plan_bytes(P) bytes)."""
+    if not cls.is_cuda:
+        raise RuntimeError("diff_gaussian_rasterization: `cls` must live on the gfx950 device (no CPU fallback)")
+    if cls.dtype != torch.uint8 or cls.dim() != 1 or not cls.is_contiguous():
+        raise ValueError("cls must be a contiguous uint8 vector")
+    P, dev = cls.shape[0], cls.device
+    if ranks is None or ranks.numel() < 4 * P:
+        ranks = torch.empty(4 * max(P, 1), dtype=torch.int32, device=dev)
+    if split_rows is None or split_rows.numel() < P:
+        split_rows = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    if ranks.dtype != torch.int32 or split_rows.dtype != torch.int32 or not ranks.is_contiguous() or \
+            not split_rows.is_contiguous():
+        raise ValueError("ranks / split_rows must be contiguous int32 tensors")
+    nbytes = lib.gsr_densify_plan_bytes(P)
+    if workspace is None or workspace.numel() * workspace.element_size() < nbytes:
+        workspace = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(lib.gsr_densify_plan(P, _ptr(cls), _ptr(ranks), _ptr(split_rows), _ptr(counts), _ptr(workspace),
+                                   workspace.numel() * workspace.element_size(), _stream()), "gsr_densify_plan")
+    return ranks.view(-1)[:4 * P].view(4, P), split_rows[:P], counts
+
+
+def densify_move(cls, ranks, counts, srcs, dsts, roles, alts=None, rotation=None, samples=None, copies=2):
+    """write the result of a densification event for all tensors in ONE launch (include/gsraster.h: gsr_densify_move).
+    cls / ranks: the plan's; counts: its four counts as python ints; srcs[k] [P, ...] -> dsts[k] [>= n_new, ...]
+    (rows contiguous, 4-byte elements, never aliasing), roles[k] one of DENSIFY_ROLE_*; alts[k]: the dense [P,3] child
+    source of a SCALING tensor; rotation [P,4] / samples [copies * n_split, 3]: what the XYZ role computes children
+    from.  Returns n_new = n_orig + n_clone + copies * n_child."""
+    n_orig, n_clone, n_child, n_split = (int(c) for c in counts)
+    n_new = n_orig + n_clone + copies * n_child
+    K, P = len(srcs), cls.shape[0]
+    if K > 32:
+        raise ValueError("densify_move: at most 32 tensors per launch")
+    if K == 0 or P == 0:
+        return n_new
+    alts = list(alts) if alts is not None else [None] * K
+    if tuple(ranks.shape) != (4, P) or ranks.dtype != torch.int32 or not ranks.is_contiguous():
+        raise ValueError("ranks must be the plan's contiguous int32 [4,P]")
+    widths, ss, ds = [], [], []
+    dst_rows = min(d.shape[0] for d in dsts)
+    for s_, d_, a_, role in zip(srcs, dsts, alts, roles):
+        for t, what in ((s_, "source"), (d_, "destination"), (a_, "alternate source")):
+            if t is None:
+                continue
+            if not t.is_cuda:
+                raise RuntimeError(f"diff_gaussian_rasterization: {what} must live on the gfx950 device (no CPU "
+                                   "fallback)")
+            if t.element_size() != 4 or not t.is_contiguous():
+                raise ValueError(f"{what}: dense tensors of 4-byte elements expected")
+        w = 1
+        for d in s_.shape[1:]:
+            w *= d
+        if s_.shape[0] != P or tuple(d_.shape[1:]) != tuple(s_.shape[1:]) or d_.dtype != s_.dtype:
+            raise ValueError("source / destination row shapes differ")
+        if role == DENSIFY_ROLE_SCALING and (a_ is None or tuple(a_.shape) != (P, 3) or w != 3):
+            raise ValueError("a SCALING tensor needs a dense [P,3] alternate source")
+        if role == DENSIFY_ROLE_XYZ and n_child > 0 and (
+                w != 3 or rotation is None or samples is None or tuple(rotation.shape) != (P, 4) or
+                tuple(samples.shape) != (copies * n_split, 3) or not rotation.is_contiguous() or
+                not samples.is_contiguous() or rotation.dtype != torch.float32 or samples.dtype != torch.float32):
+            raise ValueError("an XYZ tensor needs rotation [P,4] and samples [copies * n_split, 3], dense fp32")
+        s0, e0 = s_.data_ptr(), s_.data_ptr() + s_.numel() * 4
+        d0, d1 = d_.data_ptr(), d_.data_ptr() + n_new * w * 4
+        if s0 < d1 and d0 < e0:
+            raise ValueError("densify_move: a source aliases its destination")
+        widths.append(w)
+        ss.append(w)
+        ds.append(w)
+    VP = ctypes.c_void_p * K
+    with _on(cls.device):
+        check(lib.gsr_densify_move(P, _ptr(cls), _ptr(ranks), n_orig, n_clone, n_child, n_split, int(copies), K,
+                                   VP(*[s_.data_ptr() for s_ in srcs]), VP(*[d_.data_ptr() for d_ in dsts]),
+                                   VP(*[a_.data_ptr() if a_ is not None else None for a_ in alts]),
+                                   (ctypes.c_int32 * K)(*widths), (ctypes.c_int32 * K)(*[int(r) for r in roles]),
+                                   (ctypes.c_int64 * K)(*ss), (ctypes.c_int64 * K)(*ds), dst_rows, _ptr(rotation),
+                                   _ptr(samples), _stream()), "gsr_densify_move")
+    return n_new
 
 
 # ------------------------------------------------------------------------------------------ _C

@@ -70,6 +70,10 @@ SIGNATURES = {
                                 c_void_p]),
     "gsr_scatter_rows": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p]),
+    "gsr_densify_plan_bytes": (c_size_t, [c_int64]),
+    "gsr_densify_plan": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gsr_densify_move": (c_int, [c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int] +
+                         [c_void_p] * 7 + [c_int64, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, ctypes.c_double, c_int64, c_float, c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int] + [c_void_p] * 10 + [c_float, c_void_p]),

@@ -517,6 +517,51 @@ int gsr_scatter_rows(int64_t n_in, const int32_t *order, int num_tensors, const 
                      gsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N4  one-pass densification event (new symbols, ABI unchanged).  The reference's densify_and_prune runs clone, split
+ * and prune one after the other, each a boolean-index gather or a cat of every parameter and both Adam moments
+ * (scene/gaussian_model.py:789-921: _prune_optimizer, prune_points, cat_tensors_to_optimizer, densification_postfix;
+ * :922-1044: densify_and_split, densify_and_clone, densify_and_prune).  The result of that sequence is, in terms of the
+ * ORIGINAL P rows,
+ *     [ kept originals | kept clones | first children of the split rows whose children survive | second children ]
+ * with the original order inside each segment, so it can be written in one pass.  The host classifies every row into one
+ * byte (bits below); the plan ranks the rows, the move writes the result.
+ *
+ * gsr_densify_plan: one single-sweep scan (decoupled look-back, no sort) over cls[P].  ranks is int32 [4,P]: ranks[c*P+i]
+ *   = number of rows j < i whose class has the bit of category c, categories in the order kept original, kept clone,
+ *   parent with kept children, split parent.  counts (device int64 [4]) = {n_orig, n_clone, n_child, n_split} in the same
+ *   order; n_child counts PARENTS (the result holds copies * n_child child rows).  split_rows (int32 [P], may be NULL):
+ *   split_rows[ranks[3*P+i]] = i for every split parent, i.e. the first n_split entries list the split rows in order
+ *   (the rows whose scales are the standard deviations of the reference's torch.normal draw, :933-936).
+ *   P == 0 zeroes counts and returns 0.  P <= 2^31 - 1.
+ * gsr_densify_move: one launch writes every destination row of num_tensors <= 32 tensors (4-byte words, strides in
+ *   words, HOST tables as for gsr_gather_rows).  n_* are the plan's counts read back by the caller; dst_rows is the
+ *   number of rows every destination can hold (>= n_orig + n_clone + copies * n_child, GSR_EINVAL otherwise).  Roles:
+ *     COPY    every segment copies the source row (parameters other than xyz / scaling, send_to_gpui_cnt);
+ *     MOMENT  kept originals copy, all new rows are zero (exp_avg / exp_avg_sq: cat_tensors_to_optimizer :854-893);
+ *     XYZ     width 3; child k of parent i is R(rotation[i]) . samples[k * n_split + ranks[3*P+i]] + xyz[i] (:937-939,
+ *             R as utils/general_utils.py:416-439 builds it: a correctly rounded sqrtf, true divisions, every product
+ *             and sum rounded on its own -- the kernel is compiled without FP contraction; the dot is summed left to right);
+ *     SCALING width 3; children take row i of alts[k], a dense [P,3] tensor (log(get_scaling / (0.8 * copies)), :940).
+ *   rotation: dense [P,4]; samples: dense [copies * n_split, 3].  A source never aliases a destination.
+ *   Arguments are validated before any device work; P == 0 returns 0. */
+#define GSR_DENSIFY_KEEP_ORIGINAL 1
+#define GSR_DENSIFY_KEEP_CLONE 2
+#define GSR_DENSIFY_SPLIT_PARENT 4
+#define GSR_DENSIFY_KEEP_CHILDREN 8
+#define GSR_DENSIFY_ROLE_COPY 0
+#define GSR_DENSIFY_ROLE_MOMENT 1
+#define GSR_DENSIFY_ROLE_XYZ 2
+#define GSR_DENSIFY_ROLE_SCALING 3
+size_t gsr_densify_plan_bytes(int64_t P);
+int gsr_densify_plan(int64_t P, const uint8_t *cls, int32_t *ranks, int32_t *split_rows, int64_t *counts,
+                     void *workspace, size_t workspace_bytes, gsr_stream_t stream);
+int gsr_densify_move(int64_t P, const uint8_t *cls, const int32_t *ranks, int64_t n_orig, int64_t n_clone,
+                     int64_t n_child, int64_t n_split, int copies, int num_tensors, const void *const *srcs,
+                     void *const *dsts, const void *const *alts, const int32_t *widths, const int32_t *roles,
+                     const int64_t *src_strides, const int64_t *dst_strides, int64_t dst_rows, const float *rotation,
+                     const float *samples, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1 / K11 on the RAW parameters of GaussianModel (scene/gaussian_model.py:219-242): `scaling` log-scales
  * [P,3], `rotation` un-normalised quaternions [P,4], `opacity` logits [P,1], `features_dc` [P,1,3],
  * `features_rest` [P,sh_coeffs-1,3].  The getters' activations (scene/gaussian_model.py:109-129: exp,
