@@ -1550,6 +1550,270 @@ preprocess_backward_adam_batched_kernel(int P, int B, float *__restrict__ xyz, f
                                                 ad);
 }
 
+// ------------------------------------------------------------------- K11c: camera (pose) gradients
+// dL/d(viewmatrix, projmatrix, campos) of a batch of cameras: per visible Gaussian and camera the 27 sums below,
+// reduced over the whole shard.  The per-Gaussian quantities are K11's own (the same dL_da/db/dc with its
+// 1 / (denom^2 + 1e-7), the same treatment of the Jacobian clamp), so camera and parameter gradients are consistent.
+//   sums  0..11  viewmatrix[r][k], r = 0..3, k = 0..2:  [p,1]_r * dL/dt_k, plus (r < 3) the path through
+//                Wc = viewmatrix[:3,:3]^T in T = J Wc:  [k][0] += J00 dT0_k, [k][1] += J11 dT1_k,
+//                [k][2] += J02 dT0_k + J12 dT1_k   (column 3 of the view matrix is not read by the forward)
+//   sums 12..23  projmatrix[r][c], c in {0, 1, 3}:  [p,1]_r * dL/dp_hom_c  (column 2 only feeds the unused p_proj.z)
+//   sums 24..26  campos:  minus the SH view-direction part of dL/dmean (0 at degree 0 and for clamped channels)
+// A lane walks its rows with a grid stride and accumulates in fp32 registers (the grid grows with P up to KC_RESIDENT
+// workgroups for all cameras: 8 rows per lane and camera at 10^6 Gaussians); from there on every addition is fp64 and in a fixed order -- xor
+// butterfly inside the wave, the workgroup's waves through LDS, one partial row per workgroup and camera into the
+// caller's workspace, and the finalize kernel over the workgroups.  No atomics: bit-identical from run to run.
+// Traffic per visible Gaussian and camera: 4 (radius) + 12 + 24 + 45 * 4 (position, covariance, SH above DC) + 36
+// (gradient record row) + 3 (clamp flags) = 259 B at degree 3.  The DC coefficient does not depend on the view
+// direction: never read.
+constexpr int KC_BLOCK = 256;
+constexpr int KC_WAVES = KC_BLOCK / 64;
+constexpr int KC_NS = 27;            // non-trivial sums per camera
+// workgroups of a launch, all cameras together: what the device holds at once (256 CUs x 2: two waves per SIMD, four
+// per workgroup).  One resident round measured fastest at 10^6 Gaussians (every workgroup ends with 27 fp64 butterflies
+// and a pass through LDS) -- main kernel with one / four cameras, by row blocks per camera: 1024: 70 / 216 us,
+// 512: 63 / 185, 256: 84 / 171, 128: 143 / 164; three waves per SIMD (168 registers, 18 spilled): 74-77 / 202-211
+constexpr int KC_RESIDENT = 512;
+constexpr int KC_FIN_SLICES = 32;                 // the finalize adds the partial rows in this many contiguous slices
+
+// d colour / d (unit view direction), contracted with the colour gradient g3: the `ddir` of K11 without its dsh half
+template <int DEG>
+__device__ __forceinline__ void sh_ddir(const float *__restrict__ sh, float x, float y, float z, const float (&g3)[3],
+                                        float (&ddir)[3]) {
+    ddir[0] = ddir[1] = ddir[2] = 0.f;
+    if (DEG == 0) return;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        float dx = -SH_C1 * sh[3 * 3 + ch];
+        float dy = -SH_C1 * sh[1 * 3 + ch];
+        float dz = SH_C1 * sh[2 * 3 + ch];
+        if (DEG > 1) {
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            dx += SH_C2[0] * y * sh[4 * 3 + ch] + SH_C2[2] * 2.f * -x * sh[6 * 3 + ch] + SH_C2[3] * z * sh[7 * 3 + ch] +
+                  SH_C2[4] * 2.f * x * sh[8 * 3 + ch];
+            dy += SH_C2[0] * x * sh[4 * 3 + ch] + SH_C2[1] * z * sh[5 * 3 + ch] + SH_C2[2] * 2.f * -y * sh[6 * 3 + ch] +
+                  SH_C2[4] * 2.f * -y * sh[8 * 3 + ch];
+            dz += SH_C2[1] * y * sh[5 * 3 + ch] + SH_C2[2] * 2.f * 2.f * z * sh[6 * 3 + ch] +
+                  SH_C2[3] * x * sh[7 * 3 + ch];
+            if (DEG > 2) {
+                dx += SH_C3[0] * sh[9 * 3 + ch] * 3.f * 2.f * xy + SH_C3[1] * sh[10 * 3 + ch] * yz +
+                      SH_C3[2] * sh[11 * 3 + ch] * -2.f * xy + SH_C3[3] * sh[12 * 3 + ch] * -3.f * 2.f * xz +
+                      SH_C3[4] * sh[13 * 3 + ch] * (-3.f * xx + 4.f * zz - yy) + SH_C3[5] * sh[14 * 3 + ch] * 2.f * xz +
+                      SH_C3[6] * sh[15 * 3 + ch] * 3.f * (xx - yy);
+                dy += SH_C3[0] * sh[9 * 3 + ch] * 3.f * (xx - yy) + SH_C3[1] * sh[10 * 3 + ch] * xz +
+                      SH_C3[2] * sh[11 * 3 + ch] * (-3.f * yy + 4.f * zz - xx) +
+                      SH_C3[3] * sh[12 * 3 + ch] * -3.f * 2.f * yz + SH_C3[4] * sh[13 * 3 + ch] * -2.f * xy +
+                      SH_C3[5] * sh[14 * 3 + ch] * -2.f * yz + SH_C3[6] * sh[15 * 3 + ch] * -3.f * 2.f * xy;
+                dz += SH_C3[1] * sh[10 * 3 + ch] * xy + SH_C3[2] * sh[11 * 3 + ch] * 4.f * 2.f * yz +
+                      SH_C3[3] * sh[12 * 3 + ch] * 3.f * (2.f * zz - xx - yy) +
+                      SH_C3[4] * sh[13 * 3 + ch] * 4.f * 2.f * xz + SH_C3[5] * sh[14 * 3 + ch] * (xx - yy);
+            }
+        }
+        ddir[0] += dx * g3[ch];
+        ddir[1] += dy * g3[ch];
+        ddir[2] += dz * g3[ch];
+    }
+}
+
+// one (Gaussian, camera) pair: adds its 27 contributions to acc
+template <int DEG>
+__device__ __forceinline__ void cams_accumulate(float (&acc)[KC_NS], const float *__restrict__ cp, int W, int H,
+                                                const float (&p)[3], const float (&cv)[6],
+                                                const float *__restrict__ sh, const float4 gco, const float2 g2,
+                                                const float (&g3)[3]) {
+    const Cam cam = load_cam_packed(cp);
+    const float tanfovx = cp[35], tanfovy = cp[36];
+    const float fx = W / (2.0f * tanfovx), fy = H / (2.0f * tanfovy);
+    const float ph[4] = {p[0], p[1], p[2], 1.f};
+    // ---- conic -> cov2D -> T = J Wc -> (t, Wc): K11's chain
+    float t[3];
+    t[0] = cam.v[0] * p[0] + cam.v[4] * p[1] + cam.v[8] * p[2] + cam.v[12];
+    t[1] = cam.v[1] * p[0] + cam.v[5] * p[1] + cam.v[9] * p[2] + cam.v[13];
+    t[2] = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
+    float T[2][3], tc[3];
+    bool xin, yin;
+    compute_T(t, cam.v, fx, fy, tanfovx, tanfovy, T, tc, xin, yin);
+    const float S[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
+    float ST0[3], ST1[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        ST0[r] = S[r][0] * T[0][0] + S[r][1] * T[0][1] + S[r][2] * T[0][2];
+        ST1[r] = S[r][0] * T[1][0] + S[r][1] * T[1][1] + S[r][2] * T[1][2];
+    }
+    const float a = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2] + 0.3f;
+    const float b = T[0][0] * ST1[0] + T[0][1] * ST1[1] + T[0][2] * ST1[2];
+    const float c = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2] + 0.3f;
+    const float denom = a * c - b * b;
+    const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+    const float gA = gco.x, gB = gco.y, gC = gco.z;
+    float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
+    if (denom2inv != 0.f) {
+        dL_da = denom2inv * (-c * c * gA + b * c * gB + (denom - a * c) * gC);
+        dL_dc = denom2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
+        dL_db = denom2inv * (2.f * b * c * gA - (denom + 2.f * b * b) * gB + 2.f * a * b * gC);
+    }
+    float dT0[3], dT1[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        dT0[k] = 2.f * ST0[k] * dL_da + ST1[k] * dL_db;
+        dT1[k] = 2.f * ST1[k] * dL_dc + ST0[k] * dL_db;
+    }
+    const float dJ00 = dT0[0] * cam.v[0] + dT0[1] * cam.v[4] + dT0[2] * cam.v[8];
+    const float dJ02 = dT0[0] * cam.v[2] + dT0[1] * cam.v[6] + dT0[2] * cam.v[10];
+    const float dJ11 = dT1[0] * cam.v[1] + dT1[1] * cam.v[5] + dT1[2] * cam.v[9];
+    const float dJ12 = dT1[0] * cam.v[2] + dT1[1] * cam.v[6] + dT1[2] * cam.v[10];
+    const float tz = 1.f / tc[2], tz2 = tz * tz, tz3 = tz2 * tz;
+    float dt[3];
+    dt[0] = (xin ? 1.f : 0.f) * (-fx * tz2 * dJ02);
+    dt[1] = (yin ? 1.f : 0.f) * (-fy * tz2 * dJ12);
+    dt[2] = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.f * fx * tc[0]) * tz3 * dJ02 + (2.f * fy * tc[1]) * tz3 * dJ12;
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) acc[r * 3 + k] += ph[r] * dt[k];
+    const float J00 = fx / tc[2], J02 = -(fx * tc[0]) / (tc[2] * tc[2]);
+    const float J11 = fy / tc[2], J12 = -(fy * tc[1]) / (tc[2] * tc[2]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        acc[k * 3 + 0] += J00 * dT0[k];
+        acc[k * 3 + 1] += J11 * dT1[k];
+        acc[k * 3 + 2] += J02 * dT0[k] + J12 * dT1[k];
+    }
+    // ---- means2D (NDC-scaled) -> p_hom through the perspective divide
+    {
+        const float phx = cam.p[0] * p[0] + cam.p[4] * p[1] + cam.p[8] * p[2] + cam.p[12];
+        const float phy = cam.p[1] * p[0] + cam.p[5] * p[1] + cam.p[9] * p[2] + cam.p[13];
+        const float phw = cam.p[3] * p[0] + cam.p[7] * p[1] + cam.p[11] * p[2] + cam.p[15];
+        const float mw = 1.0f / (phw + 0.0000001f);
+        const float mul1 = phx * mw * mw, mul2 = phy * mw * mw;
+        const float dh[3] = {mw * g2.x, mw * g2.y, -(mul1 * g2.x + mul2 * g2.y)};
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) acc[12 + r * 3 + k] += ph[r] * dh[k];
+    }
+    // ---- colour -> view direction -> campos
+    if constexpr (DEG > 0) {
+        const float dox = p[0] - cam.c[0], doy = p[1] - cam.c[1], doz = p[2] - cam.c[2];
+        const float len = sqrtf(dox * dox + doy * doy + doz * doz);
+        const float x = dox / len, y = doy / len, z = doz / len;
+        float ddir[3];
+        sh_ddir<DEG>(sh, x, y, z, g3, ddir);
+        const float dot = x * ddir[0] + y * ddir[1] + z * ddir[2];
+        acc[24] -= (ddir[0] - x * dot) / len;
+        acc[25] -= (ddir[1] - y * dot) / len;
+        acc[26] -= (ddir[2] - z * dot) / len;
+    }
+}
+
+// One workgroup = one (row block, camera) pair; partials: [nb][B][KC_NS] doubles, every word written (the workspace
+// need not be zero on entry).  27 fp32 accumulators per camera next to K11's chain leave room for one camera per lane
+// (two cameras: 256 registers and spills), so the B cameras of a row block are B workgroups -- numbered so that they
+// follow each other on the SAME XCD (workgroup w runs on XCD w % 8): position, covariance and coefficients of a row
+// come from HBM once and from that XCD's L2 for the other cameras.
+template <int DEG>
+__global__ void __launch_bounds__(KC_BLOCK, 2)
+preprocess_backward_cams_kernel(int P, int B, int nb, const float *__restrict__ means3D,
+                                const float *__restrict__ sh_rest, int rest_stride, const float *__restrict__ cams,
+                                int W, int H, const int32_t *__restrict__ radii, const float *__restrict__ cov3D,
+                                const uint8_t *__restrict__ clamped, const float *__restrict__ dL_dmeans2D,
+                                const float *__restrict__ dL_dconic_opacity, const float *__restrict__ dL_drgb,
+                                int gstride, double *__restrict__ partials) {
+    constexpr int NC = (DEG + 1) * (DEG + 1);
+    const int q = blockIdx.x >> 3;
+    const int rb = (blockIdx.x & 7) + 8 * (q / B), bc = q % B;  // row block, camera
+    if (rb >= nb) return;                                       // (the grid is rounded up to 8 row blocks)
+    const float *cp = cams + (size_t)bc * CAM_STRIDE;
+    float acc[KC_NS];
+#pragma unroll
+    for (int s = 0; s < KC_NS; s++) acc[s] = 0.f;
+    const size_t step = (size_t)nb * KC_BLOCK;
+    for (size_t i = (size_t)rb * KC_BLOCK + threadIdx.x; i < (size_t)P; i += step) {
+        const size_t o = (size_t)bc * P + i;
+        if (radii[o] <= 0) continue;  // culled: contributes nothing, its gradient row is never looked at
+        // every load of the row is issued before the first result is used
+        const float p[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
+        float cv[6];
+#pragma unroll
+        for (int e = 0; e < 6; e++) cv[e] = cov3D[6 * i + e];
+        const float4 gco = grad_ld4(dL_dconic_opacity, o, gstride);
+        const float2 g2 = grad_ld2(dL_dmeans2D, o, gstride);
+        float sh[NC * 3], g3[3] = {0.f, 0.f, 0.f};
+        sh[0] = sh[1] = sh[2] = 0.f;  // (the DC term has no view-direction derivative: never read)
+        if constexpr (DEG > 0) {
+            const float *rp = sh_rest + (size_t)rest_stride * i;
+#pragma unroll
+            for (int k = 3; k < NC * 3; k++) sh[k] = rp[k - 3];
+#pragma unroll
+            for (int e = 0; e < 3; e++)
+                g3[e] = clamped[3 * o + e] ? 0.f : dL_drgb[(size_t)(gstride ? gstride : 3) * o + e];
+        }
+        cams_accumulate<DEG>(acc, cp, W, H, p, cv, sh, gco, g2, g3);
+    }
+    // ---- wave (fp64 butterfly: every lane ends with the same sum), then the workgroup's waves in order
+    __shared__ double s_part[KC_WAVES][KC_NS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int s = 0; s < KC_NS; s++) {
+        double v = (double)acc[s];
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+        if (lane == 0) s_part[wave][s] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < KC_NS) {
+        double v = s_part[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < KC_WAVES; w++) v += s_part[w][threadIdx.x];
+        partials[((size_t)rb * B + bc) * KC_NS + threadIdx.x] = v;
+    }
+}
+
+// one workgroup per camera: the nb partial rows in a fixed order (KC_FIN_SLICES contiguous slices, then the slices), one
+// rounding to fp32, scattered into the 40-word record of `cams` with its structural zeros (nb == 0: all zeros).  32
+// slices of at most 32 rows with the loads unrolled: eight slices of 128 dependent-latency loads took 39 us
+__global__ void __launch_bounds__(KC_FIN_SLICES * 32)
+preprocess_backward_cams_finalize_kernel(int nb, int B, const double *__restrict__ partials,
+                                         float *__restrict__ dL_dcams) {
+    __shared__ double sl[KC_FIN_SLICES][32];
+    const int b = blockIdx.x, j = threadIdx.x & 31, sidx = threadIdx.x >> 5;
+    double v = 0.0;
+    if (j < KC_NS) {
+        const int per = (nb + KC_FIN_SLICES - 1) / KC_FIN_SLICES;
+        const int lo = min(nb, sidx * per), hi = min(nb, lo + per);
+#pragma unroll 8
+        for (int k = lo; k < hi; k++) v += partials[((size_t)k * B + b) * KC_NS + j];
+    }
+    sl[sidx][j] = v;
+    __syncthreads();
+    const int w = threadIdx.x;
+    if (w >= CAM_STRIDE) return;
+    int idx = -1;
+    if (w < 16) {
+        if ((w & 3) < 3) idx = (w >> 2) * 3 + (w & 3);
+    } else if (w < 32) {
+        const int r = (w - 16) >> 2, c = (w - 16) & 3;
+        if (c != 2) idx = 12 + r * 3 + (c == 3 ? 2 : c);
+    } else if (w < 35) {
+        idx = 24 + (w - 32);
+    }
+    float out = 0.f;
+    if (idx >= 0) {
+        double t = sl[0][idx];
+#pragma unroll
+        for (int q = 1; q < KC_FIN_SLICES; q++) t += sl[q][idx];
+        out = (float)t;
+    }
+    dL_dcams[(size_t)b * CAM_STRIDE + w] = out;
+}
+
+// row blocks per camera: KC_RESIDENT workgroups shared by the B cameras (a multiple of 8, one per XCD, at least 8)
+inline int kc_blocks(int P, int B) {
+    const int nb = P <= 0 ? 0 : (int)gsr_div_up(P, KC_BLOCK);
+    int cap = (KC_RESIDENT / (B > 0 ? B : 1) + 7) & ~7;
+    if (cap < 8) cap = 8;
+    return nb < cap ? nb : cap;
+}
+
 // -------------------------------------------------------------------------------------------- K2
 __global__ void __launch_bounds__(GSR_ONE_DIM_BLOCK)
 local2j_kernel(int P, int W, int H, int ws, const float2 *__restrict__ means2D, const int32_t *__restrict__ radii,
@@ -1774,6 +2038,52 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_dyn(
                                         reinterpret_cast<hipStream_t>(stream), P, B, xyz, scaling, scale_modifier,
                                         rotation, features_dc, features_rest, opacity, cams, width, height, radii,
                                         cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride, ad));
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
+// K11c (see the kernels above): dL_dcams [B][40] in the layout of `cams` for the B cameras of a batch.
+extern "C" size_t gsr_preprocess_backward_cams_bytes(int P, int B) {
+    const int nb = kc_blocks(P, 1);  // (the most row blocks any B takes: non-decreasing in P and in B)
+    return (size_t)(nb > 0 ? nb : 1) * (size_t)(B > 0 ? B : 1) * KC_NS * sizeof(double);
+}
+
+extern "C" int gsr_preprocess_backward_cams(int P, int B, int sh_degree, int sh_coeffs, const float *means3D,
+                                            const float *sh_dc, int sh_dc_stride, const float *sh_rest,
+                                            int sh_rest_stride, const float *cams, int width, int height,
+                                            const int32_t *radii, const float *cov3D, const uint8_t *clamped,
+                                            const float *dL_dmeans2D, const float *dL_dconic_opacity,
+                                            const float *dL_drgb, int grad_row_stride, void *workspace,
+                                            size_t workspace_bytes, float *dL_dcams, gsr_stream_t stream) {
+    if (P < 0 || B < 1 || sh_degree < 0 || sh_degree > 3 || sh_coeffs < 1 ||
+        sh_coeffs < (sh_degree + 1) * (sh_degree + 1) || width <= 0 || height <= 0 || sh_dc_stride < 0 ||
+        sh_rest_stride < 0 || grad_row_stride < 0 || (grad_row_stride != 0 && grad_row_stride < 9) || !dL_dcams)
+        return GSR_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) {
+        hipLaunchKernelGGL(preprocess_backward_cams_finalize_kernel, dim3(B), dim3(KC_FIN_SLICES * 32), 0, st, 0, B, nullptr,
+                           dL_dcams);
+        GSR_LAUNCH_CHECK();
+        return 0;
+    }
+    if (!means3D || !sh_dc || (!sh_rest && sh_coeffs > 1) || !cams || !radii || !cov3D || !clamped || !dL_dmeans2D ||
+        !dL_dconic_opacity || !dL_drgb || !workspace || ((uintptr_t)workspace & 7))
+        return GSR_EINVAL;
+    if (grad_row_stride == 0 && (((uintptr_t)dL_dmeans2D & 7) || ((uintptr_t)dL_dconic_opacity & 15)))
+        return GSR_EINVAL;  // dense gradients are read with 8- / 16-byte loads
+    if (sh_rest_stride < 3 * ((sh_degree + 1) * (sh_degree + 1) - 1))
+        return GSR_EINVAL;  // a row of sh_rest holds less than the degree reads
+    if (workspace_bytes < gsr_preprocess_backward_cams_bytes(P, B)) return GSR_ENOSPACE;
+    const int nb = kc_blocks(P, B);
+    double *partials = static_cast<double *>(workspace);
+    const dim3 grid(8u * (unsigned)gsr_div_up(nb, 8) * (unsigned)B), block(KC_BLOCK);
+    GSR_DISPATCH_DEG(sh_degree,
+                     hipLaunchKernelGGL(preprocess_backward_cams_kernel<DEG>, grid, block, 0, st, P, B, nb, means3D,
+                                        sh_rest, sh_rest_stride, cams, width, height, radii, cov3D, clamped,
+                                        dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride, partials));
+    GSR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(preprocess_backward_cams_finalize_kernel, dim3(B), dim3(KC_FIN_SLICES * 32), 0, st, nb, B, partials,
+                       dL_dcams);
     GSR_LAUNCH_CHECK();
     return 0;
 }

@@ -396,12 +396,128 @@ class _PreprocessGaussiansRaw(torch.autograd.Function):
 
 
 def pack_camera(raster_settings):
-    """[40] float tensor { viewmatrix, projmatrix, campos, tanfovx, tanfovy, 0, 0, 0 } of one camera (device)"""
+    """[40] float tensor { viewmatrix, projmatrix, campos, tanfovx, tanfovy, 0, 0, 0 } of one camera (device).
+    Only `cat` and `float`: differentiable, so the gradient of a record ([B,40], slot `cams` of
+    preprocess_gaussians_raw_batched) flows back into viewmatrix / projmatrix / campos tensors that require grad."""
     rs = raster_settings
     dev = rs.viewmatrix.device
     tail = torch.tensor([float(rs.tanfovx), float(rs.tanfovy), 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
     return torch.cat([rs.viewmatrix.reshape(16).float(), rs.projmatrix.reshape(16).float(),
                       rs.campos.reshape(3).float(), tail]).contiguous()
+
+
+# ---- camera (pose) gradients: dL/d(viewmatrix, projmatrix, campos) --------------------------------------------------
+def preprocess_backward_cameras(means3D, sh, cams, width, height, sh_degree, radii, cov3D, clamped, g_means2D,
+                                g_conic_opacity, g_rgb, gstride=0, workspace=None):
+    """-> dL_dcams [B,40] in the layout of `cams` (include/gsraster.h: gsr_preprocess_backward_cams; words 35..39 are
+    zero: no tanfov gradients).  `sh`: the activated shs [P,M,3], or the raw pair (features_dc [P,1,3], features_rest
+    [P,M-1,3]).  radii [B,P] / clamped [B,P,3] / cov3D [P,6] as saved by the forward; the incoming gradients are
+    camera-major, dense (gstride 0) or column views of one [B*P,9] record (gstride 9).  Launched only when a camera
+    tensor requires grad; `workspace`: optional uint8 / any tensor of gsr_preprocess_backward_cams_bytes(P, B) bytes."""
+    P, B = means3D.shape[0], cams.shape[0]
+    dev = means3D.device
+    # the kernel addresses every argument by pointer + row stride: anything else would give wrong sums silently
+    f32 = [("means3D", means3D, (P, 3)), ("cams", cams, (B, 40)), ("cov3D", cov3D, (P, 6))]
+    f32 += [(f"sh[{k}]", t, None) for k, t in enumerate(sh)] if isinstance(sh, (tuple, list)) else [("sh", sh, None)]
+    for name, t, shape in f32 + [("radii", radii, (B, P)), ("clamped", clamped, (B, P, 3))]:
+        want = {"radii": torch.int32, "clamped": torch.uint8}.get(name, torch.float32)
+        if t.dtype != want or not t.is_contiguous() or t.device != dev or (shape and tuple(t.shape) != shape):
+            raise ValueError(f"preprocess_backward_cameras: {name} must be a contiguous {want} tensor"
+                             f"{' of shape ' + str(shape) if shape else ''} on {dev}")
+    for name, t, k in (("g_means2D", g_means2D, 2), ("g_conic_opacity", g_conic_opacity, 4), ("g_rgb", g_rgb, 3)):
+        # (may be the first camera's [P,k] slice of one dense [B,P,k] block: the row layout is checked, not the extent)
+        if gstride == 0:
+            ok = t.is_contiguous()
+        else:
+            ok = t.dim() == 2 and t.shape[1] == k and (t.shape[0] <= 1 or t.stride() == (gstride, 1))
+        if t.dtype != torch.float32 or t.device != dev or not ok:
+            raise ValueError(f"preprocess_backward_cameras: {name} must be float32 on {dev}, dense (gstride 0) or "
+                             f"[rows,{k}] column views with row stride gstride = {gstride}")
+    if isinstance(sh, (tuple, list)):
+        f_dc, f_rest = sh
+        M = 1 + f_rest.shape[1]
+        dc_ptr, dc_stride, rest_ptr, rest_stride = _ptr(f_dc), 3, (_ptr(f_rest) if M > 1 else None), 3 * (M - 1)
+    else:
+        M = sh.shape[1]
+        dc_ptr, dc_stride = _ptr(sh), 3 * M
+        rest_ptr, rest_stride = (ctypes.c_void_p(sh.data_ptr() + 12) if M > 1 else None), 3 * M
+    nbytes = int(lib.gsr_preprocess_backward_cams_bytes(P, B))
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    d_cams = torch.empty((B, 40), dtype=torch.float32, device=dev)
+    with _on(dev), kernel_timer.range("preprocess_backward_camera", N=P, B=B, M=M):
+        check(lib.gsr_preprocess_backward_cams(
+            P, B, int(sh_degree), M, _ptr(means3D), dc_ptr, dc_stride, rest_ptr, rest_stride, _ptr(cams), int(width),
+            int(height), _ptr(radii), _ptr(cov3D), _ptr(clamped), _ptr(g_means2D), _ptr(g_conic_opacity), _ptr(g_rgb),
+            int(gstride), _ptr(workspace), workspace.numel() * workspace.element_size(), _ptr(d_cams), _stream()),
+            "gsr_preprocess_backward_cams")
+    return d_cams
+
+
+def _camera_requires_grad(rs):
+    return any(torch.is_tensor(t) and t.requires_grad for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
+
+
+def _single_camera_grads(ctx, means3D, sh, view, proj, campos, radii, cov3D, clamped, g_means2D, g_conic_opacity,
+                         g_rgb, gstride):
+    """the three camera gradients of a one-camera preprocess node ([4,4], [4,4], [3]; None where not needed)"""
+    rs = ctx.raster_settings
+    need = ctx.needs_input_grad[ctx.cam_slot:ctx.cam_slot + 3]
+    if not any(need):
+        return None, None, None
+    P = means3D.shape[0]
+    cams = pack_camera(rs._replace(viewmatrix=view, projmatrix=proj, campos=campos)).view(1, 40)
+    d = preprocess_backward_cameras(means3D, sh, cams, rs.image_width, rs.image_height, rs.sh_degree,
+                                    radii.view(1, P), cov3D, clamped.view(1, P, 3), g_means2D, g_conic_opacity, g_rgb,
+                                    gstride)[0]
+    outs = (d[0:16].view(4, 4), d[16:32].view(4, 4), d[32:35])
+    return tuple(o.to(dt).reshape(shape) if n else None for o, n, (dt, shape) in zip(outs, need, ctx.cam_like))
+
+
+class _PreprocessGaussiansCam(torch.autograd.Function):
+    """_PreprocessGaussians with viewmatrix / projmatrix / campos as differentiable tensor inputs (used only when one of
+    them requires grad): the same two launches plus gsr_preprocess_backward_cams in the backward."""
+
+    @staticmethod
+    def forward(ctx, means3D, scales, rotations, shs, opacities, viewmatrix, projmatrix, campos, raster_settings,
+                cuda_args):
+        ctx.cam_slot = 5
+        ctx.cam_like = [(t.dtype, t.shape) for t in (viewmatrix, projmatrix, campos)]
+        rs = raster_settings._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
+        return _PreprocessGaussians.forward(ctx, means3D, scales, rotations, shs, opacities, rs, cuda_args)
+
+    @staticmethod
+    def backward(ctx, g_means2D, g_rgb, g_conic_opacity, g_radii, g_depths):
+        means3D, scales, rotations, shs, view, proj, campos, radii, cov3D, clamped = ctx.saved_tensors
+        g_means2D, g_rgb, g_conic_opacity, gstride = _grad_triple(g_means2D, g_rgb, g_conic_opacity,
+                                                                  means3D.shape[0], means3D.device)
+        d_cam = _single_camera_grads(ctx, means3D, shs, view, proj, campos, radii, cov3D, clamped, g_means2D,
+                                     g_conic_opacity, g_rgb, gstride)
+        return _PreprocessGaussians.backward(ctx, g_means2D, g_rgb, g_conic_opacity, g_radii, g_depths)[:5] + \
+            d_cam + (None, None)
+
+
+class _PreprocessGaussiansRawCam(torch.autograd.Function):
+    """_PreprocessGaussiansRaw with differentiable camera tensors (see _PreprocessGaussiansCam)."""
+
+    @staticmethod
+    def forward(ctx, xyz, scaling, rotation, features_dc, features_rest, opacity, viewmatrix, projmatrix, campos,
+                raster_settings, cuda_args):
+        ctx.cam_slot = 6
+        ctx.cam_like = [(t.dtype, t.shape) for t in (viewmatrix, projmatrix, campos)]
+        rs = raster_settings._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
+        return _PreprocessGaussiansRaw.forward(ctx, xyz, scaling, rotation, features_dc, features_rest, opacity, rs,
+                                               cuda_args)
+
+    @staticmethod
+    def backward(ctx, g_means2D, g_rgb, g_conic_opacity, g_radii, g_depths):
+        xyz, scaling, rotation, f_dc, f_rest, opacity, view, proj, campos, radii, cov3D, clamped = ctx.saved_tensors
+        g_means2D, g_rgb, g_conic_opacity, gstride = _grad_triple(g_means2D, g_rgb, g_conic_opacity, xyz.shape[0],
+                                                                  xyz.device)
+        d_cam = _single_camera_grads(ctx, xyz, (f_dc, f_rest), view, proj, campos, radii, cov3D, clamped, g_means2D,
+                                     g_conic_opacity, g_rgb, gstride)
+        return _PreprocessGaussiansRaw.backward(ctx, g_means2D, g_rgb, g_conic_opacity, g_radii, g_depths)[:6] + \
+            d_cam + (None, None)
 
 
 def _batched_record(grads, B, P):
@@ -614,14 +730,18 @@ class _PreprocessGaussiansRawBatched(torch.autograd.Function):
             else:
                 g_means2D, g_rgb, g_conic_opacity, gstride = assemble(0, 2), assemble(1, 3), assemble(2, 4), 0
         params = (xyz, scaling, rotation, f_dc, f_rest, opacity)
+        d_cams = None
+        if ctx.needs_input_grad[6]:  # pose refinement: dL/dcams [B,40], before K11 is launched or handed on
+            d_cams = preprocess_backward_cameras(xyz, (f_dc, f_rest), cams, W, H, deg, radii, cov3D, clamped,
+                                                 g_means2D, g_conic_opacity, g_rgb, gstride)
         sink = deferred_backward_sink()
         if sink is not None and M == 16 and sink.accepts(params):
             # K11 runs inside the optimizer's step (fused with Adam); `.grad` of the six parameters stays None
             sink.offer(PendingProjectionBackward(params, cams, radii, cov3D, clamped, g_means2D, g_conic_opacity,
                                                  g_rgb, gstride, ctx.meta, ctx.tanfov0))
-            return (None,) * 13
+            return (None,) * 6 + (d_cams,) + (None,) * 6
         return _launch_k11(params, cams, radii, cov3D, clamped, g_means2D, g_conic_opacity, g_rgb, gstride, ctx.meta,
-                           ctx.tanfov0, ctx.cuda_args_list) + (None,) * 7
+                           ctx.tanfov0, ctx.cuda_args_list) + (d_cams,) + (None,) * 6
 
 
 def preprocess_gaussians_raw_batched(xyz, scaling, rotation, features_dc, features_rest, opacity, cams, sh_degree,
@@ -1170,13 +1290,23 @@ class GaussianRasterizer(nn.Module):
         """-> (means2D [N,2], rgb [N,3], conic_opacity [N,4], radii int32 [N], depths [N]);
         radii == 0 <=> culled.  means2D supports .retain_grad(); its gradient is in NDC-scaled units
         (pixel gradient x (W/2, H/2)), the convention densification thresholds against
-        (scene/gaussian_model.py:1046-1064)."""
+        (scene/gaussian_model.py:1046-1064).  When raster_settings.viewmatrix / projmatrix / campos require grad
+        they receive their gradients too (pose refinement; one more launch in the backward, only then)."""
+        rs = self.raster_settings
+        if _camera_requires_grad(rs):
+            return _PreprocessGaussiansCam.apply(means3D, scales, rotations, shs, opacities, rs.viewmatrix,
+                                                 rs.projmatrix, rs.campos, rs, cuda_args)
         return _PreprocessGaussians.apply(means3D, scales, rotations, shs, opacities, self.raster_settings, cuda_args)
 
     def preprocess_gaussians_raw(self, xyz, scaling, rotation, features_dc, features_rest, opacity, cuda_args=None):
         """same outputs as preprocess_gaussians, from GaussianModel's RAW parameters (_xyz, _scaling, _rotation,
         _features_dc, _features_rest, _opacity): the getters' exp / normalize / sigmoid / cat are fused into the
-        kernels.  Extension of this build (the reference's op takes activated tensors)."""
+        kernels.  Extension of this build (the reference's op takes activated tensors).  Camera tensors that require
+        grad receive their gradients as in preprocess_gaussians."""
+        rs = self.raster_settings
+        if _camera_requires_grad(rs):
+            return _PreprocessGaussiansRawCam.apply(xyz, scaling, rotation, features_dc, features_rest, opacity,
+                                                    rs.viewmatrix, rs.projmatrix, rs.campos, rs, cuda_args)
         return _PreprocessGaussiansRaw.apply(xyz, scaling, rotation, features_dc, features_rest, opacity,
                                              self.raster_settings, cuda_args)
 

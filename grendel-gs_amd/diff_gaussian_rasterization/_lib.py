@@ -92,6 +92,10 @@ SIGNATURES = {
     "gsr_preprocess_backward_adam_raw_batched_dyn": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float] +
                                                      [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 6 + [c_int] +
                                                      [c_void_p] * 7 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_preprocess_backward_cams_bytes": (c_size_t, [c_int, c_int]),
+    "gsr_preprocess_backward_cams": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                             c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_size_t,
+                                                                                         c_void_p, c_void_p]),
     "gsr_bin_total_offset": (c_size_t, [c_int, c_int, c_int]),
     "gsr_bin_segments_offset": (c_size_t, [c_int, c_int, c_int]),
     "gsr_bin_speculative": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

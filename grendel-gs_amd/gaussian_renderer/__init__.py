@@ -701,7 +701,13 @@ def _batched_exchange_final(m2_views, rgb_views, co_views, radii_views, depths_v
 def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, pipe, bg_color, scaling_modifier=1.0,
                                                  batched_strategies=None, mode="train", _legacy=False):
     """every rank projects ITS shard of Gaussians for EVERY camera of the batch (K1), then the sparse
-    exchange hands each rank the Gaussians touching the bands it renders.  (`_legacy`: set by the legacy single-camera
+    exchange hands each rank the Gaussians touching the bands it renders.
+
+    Pose refinement: when a camera's world_view_transform / full_proj_transform / camera_center requires grad, its
+    packed record is rebuilt on every call (no per-camera or per-batch cache) and `loss.backward()` leaves the gradient
+    in the three tensors' `.grad` (or in whatever leaves they were computed from).  At world size W > 1 every rank
+    obtains the PARTIAL sum over its own shard of Gaussians -- the camera gradient is linear in them -- and the caller
+    all-reduces (SUM) the camera gradients across ranks.  (`_legacy`: set by the legacy single-camera
     wrapper below, whose render() has no verification / stream hand-over: exact sizes, one exchange, current stream.)"""
     timers = utils.get_timers()
     args = utils.get_args()
@@ -755,7 +761,12 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
                          "utils/general_utils.py:89-93, set from the first training camera, scene/__init__.py:93-97)")
     # ONE launch for the whole batch: parameters read once, per-camera outputs camera-major
     packed = []
+    pose_grad = False  # a camera tensor requires grad (pose refinement): no cached record -- it would keep a stale graph
     for camera, rast in zip(batched_viewpoint_cameras, rasterizers):
+        if _dgr._camera_requires_grad(rast.raster_settings):
+            pose_grad = True
+            packed.append(_dgr.pack_camera(rast.raster_settings))  # differentiable: cat + float
+            continue
         # the packed record is valid as long as the camera's tensors are the same objects with the same contents:
         # data_ptr + in-place version counter of each matrix (pose refinement / test-time edits repack)
         rs_k = rast.raster_settings
@@ -772,7 +783,7 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
     rs0 = rasterizers[0].raster_settings
     if len(packed) == 1:
         cams_block = packed[0].view(1, -1)
-    elif _dgr.capturing() is not None:
+    elif pose_grad or _dgr.capturing() is not None:
         cams_block = torch.stack(packed)  # (a hipGraph capture: the records are slices of a block refreshed per replay)
     else:
         # the [B,40] block of a batch that has been seen before (the records themselves are cached per camera): the

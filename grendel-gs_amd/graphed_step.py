@@ -556,6 +556,13 @@ class GraphedIteration:
         if not self.enabled:
             self.stats["eager"] += 1
             return self.body(cameras, strategies, tasks)
+        for camera in cameras:
+            if any(torch.is_tensor(t) and t.requires_grad for t in
+                   (camera.world_view_transform, camera.full_proj_transform, camera.camera_center)):
+                # a replay reads the cameras from a device block refreshed by copies: no autograd path to the pose
+                raise ValueError("GraphedIteration: a camera's world_view_transform / full_proj_transform / "
+                                 "camera_center requires grad; the camera-gradient launch is not captured -- run pose "
+                                 "refinement eagerly (GraphedIteration(..., enabled=False) or call the body directly)")
         key = self._key(cameras, strategies)
         entry = self.entries.get(key)
         if entry is not None and not self._usable(entry, cameras, strategies):

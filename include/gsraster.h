@@ -604,6 +604,35 @@ int gsr_preprocess_backward_raw_batched(int P, int B, int sh_degree, int sh_coef
                                         float *dL_dscaling, float *dL_drotation, float *dL_dfeatures_dc,
                                         float *dL_dfeatures_rest, float *dL_dopacity, gsr_stream_t stream);
 
+/* Camera (pose) gradients of K11: dL_dcams [B][40] in the layout of `cams` -- [0:16] dL/dviewmatrix (4x4 row-major,
+ * row-vector convention), [16:32] dL/dprojmatrix, [32:35] dL/dcampos, [35:40] zeros (gradients with respect to tanfovx /
+ * tanfovy are NOT provided).  Per visible Gaussian (radii > 0) and camera, with t = [p,1] viewmatrix[:, :3] and
+ * p_hom = [p,1] projmatrix:
+ *   viewmatrix[:, :3] += [p,1]^T (x) dL/dt, dL/dt from cov2D through the Jacobian exactly as K11 computes it (the same
+ *     dL_da/db/dc with 1 / (denom^2 + 1e-7); a t.x / t.y clamped to +-1.3 tanfov is a constant);
+ *   viewmatrix[:3, :3] += the gradient through Wc in cov2D = (J Wc) Sigma (J Wc)^T;  column 3 is exactly 0 (unused);
+ *   projmatrix += [p,1]^T (x) dL/dp_hom from means2D (incoming gradient in K11's NDC-scaled convention); column 2 is
+ *     exactly 0, column 3 (w) is not;
+ *   campos -= the SH view-direction part of dL/dmean (clamped channels contribute 0; exactly 0 at sh_degree 0).
+ * The reference's rasterizer has no camera gradient, so there is no reference call site for this entry point: the
+ * formulas are the derivatives of its forward and oracle/torch_oracle.py's autograd is the arbiter.
+ * SH coefficients: coefficient 0 at sh_dc + i * sh_dc_stride, coefficients 1.. at sh_rest + i * sh_rest_stride (strides
+ * in floats) -- activated shs [P,M,3]: (shs, 3M, shs + 3, 3M); raw: (features_dc, 3, features_rest, 3(M-1)); sh_rest may
+ * be NULL when sh_coeffs == 1; sh_rest_stride >= 3 ((sh_degree + 1)^2 - 1) (GSR_EINVAL otherwise).  sh_dc must not be
+ * NULL but is never read (reserved): coefficient 0 does not depend on the view direction, so it has no camera gradient.  radii [B,P], clamped [B,P,3], cov3D [P,6] as saved by the forward; the three incoming
+ * gradients are camera-major with the grad_row_stride convention of gsr_preprocess_backward (0 dense, 9 = column views
+ * of a [B*P,9] record).  Rows with radii <= 0 contribute nothing and their gradient rows are never read.  The sums are
+ * reduced without atomics (per-workgroup fp64 partial rows in `workspace`, which need not be zeroed, then a fixed-order
+ * fp64 finalize): bit-identical from run to run.  workspace: 8-byte aligned, >= gsr_preprocess_backward_cams_bytes(P, B)
+ * (GSR_ENOSPACE otherwise).  P == 0 writes zeros. */
+size_t gsr_preprocess_backward_cams_bytes(int P, int B);
+int gsr_preprocess_backward_cams(int P, int B, int sh_degree, int sh_coeffs, const float *means3D, const float *sh_dc,
+                                 int sh_dc_stride, const float *sh_rest, int sh_rest_stride, const float *cams,
+                                 int width, int height, const int32_t *radii, const float *cov3D,
+                                 const uint8_t *clamped, const float *dL_dmeans2D, const float *dL_dconic_opacity,
+                                 const float *dL_drgb, int grad_row_stride, void *workspace, size_t workspace_bytes,
+                                 float *dL_dcams, gsr_stream_t stream);
+
 /* K11 of a batch FUSED with the optimizer step of the six tensors it differentiates (N3 inside a9's neighbour: the
  * reference runs `loss.backward()` and then `gaussians.optimizer.step()` over the same 59 floats per Gaussian,
  * train_internal.py:195 and :316-328, scene/gaussian_model.py:292).  A Gaussian's gradient is complete when its lane

@@ -30,6 +30,8 @@ GROUPS = [  # (group, substrings of the kernel symbol, substring that marks ONE 
     ("composite_backward", ["composite_backward_kernel"], "composite_backward_kernel"),
     ("preprocess_forward", ["preprocess_forward"], "preprocess_forward"),
     ("preprocess_backward_adam", ["preprocess_backward_adam"], "preprocess_backward_adam"),  # fused K11 + Adam (first)
+    # camera pose gradients (only launched when a camera tensor requires grad; before K11's catch-all substring)
+    ("preprocess_backward_camera", ["preprocess_backward_cams"], "preprocess_backward_cams_kernel"),
     ("preprocess_backward", ["preprocess_backward"], "preprocess_backward"),
     # (one call = one K3: the look-back pipeline's touch_count_kernel or the persistent prepare kernel of round 5)
     ("binning", ["touch_count_kernel", "radix_onesweep_kernel", "scan_gather_lookback_kernel", "emit_scatter_kernel",
