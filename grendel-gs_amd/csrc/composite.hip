@@ -484,7 +484,7 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
                            const uint8_t *__restrict__ compute_locally, const float *__restrict__ bg,
                            const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
                            const float *__restrict__ dL_dpixels, Acc *__restrict__ dL_record,
-                           const float *__restrict__ out_color, const SegWs &seg) {
+                           const float *__restrict__ out_color, const SegWs &seg, uint8_t *__restrict__ touched) {
     if (!compute_locally[tile]) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tx = tile % gx, ty = tile / gx;
@@ -542,15 +542,41 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
     // four quadrant waves add into one table), 6-8 the pixel's dL/dcolour.  Rows 0-7 x columns 0-5 are the q moments,
     // rows 8-15 x columns 6-8 the colour gradients; the other products are not used.
     const int kq = lane >> 4, j = lane & 15;
+    // With p = 4 t + kq the pixel of K-step t is column xt = xl + 4 (t & 1), row yt = yl + (t >> 1) of the tile, and every
+    // one of the six monomials is a product X(xt) Y(yt) with X in {1, x, x^2}, Y in {1, y, y^2}: two values of X and eight
+    // of Y per lane, from coefficients chosen ONCE by j (integers <= 15, products <= 225: exact, whatever the
+    // association).  Columns 6-8 load all sixteen values from clamped addresses under one branch (so that they are in
+    // flight together) and select by the bounds afterwards.
     float Bop[16];
+    {
+        const bool isg = j >= 6 && j < 9;
+        // X(x) = xa + x (xb1 + xc x), Y(y) likewise; j >= 6: X = 0
+        const float xa = (j == 0 || j == 2 || j == 5) ? 1.f : 0.f, xb1 = (j == 1 || j == 4) ? 1.f : 0.f, xc = j == 3 ? 1.f : 0.f;
+        const float ya = (j == 0 || j == 1 || j == 3) ? 1.f : 0.f, yb1 = (j == 2 || j == 4) ? 1.f : 0.f, yc = j == 5 ? 1.f : 0.f;
+        const float xl = (float)((wave & 1) * 8 + kq);
+        float X[2];
 #pragma unroll
-    for (int t = 0; t < 16; t++) {
-        const int p = 4 * t + kq;
-        const float xt = (float)((wave & 1) * 8 + (p & 7)), yt = (float)((wave >> 1) * 8 + (p >> 3));
-        const int gxp = qx0 + (p & 7), gyp = qy0 + (p >> 3);
-        float v = j == 0 ? 1.f : j == 1 ? xt : j == 2 ? yt : j == 3 ? xt * xt : j == 4 ? xt * yt : j == 5 ? yt * yt : 0.f;
-        if (j >= 6 && j < 9 && gxp < W && gyp < H) v = dL_dpixels[(size_t)(j - 6) * HW + (size_t)gyp * W + gxp];
-        Bop[t] = v;
+        for (int h = 0; h < 2; h++) {
+            const float x = xl + 4.f * h;
+            X[h] = fmaf(x, fmaf(xc, x, xb1), xa);
+        }
+        const int gx0 = qx0 + kq;
+        const int cx0 = min(gx0, W - 1), cx1 = min(gx0 + 4, W - 1);
+        const float *gb = dL_dpixels + (size_t)(isg ? j - 6 : 0) * HW;
+        float G[16];
+#pragma unroll
+        for (int t = 0; t < 16; t++) G[t] = 0.f;
+        if (isg) {
+#pragma unroll
+            for (int t = 0; t < 16; t++) G[t] = gb[(size_t)min(qy0 + (t >> 1), H - 1) * W + ((t & 1) ? cx1 : cx0)];
+        }
+#pragma unroll
+        for (int t = 0; t < 16; t++) {
+            const float y = (float)((wave >> 1) * 8 + (t >> 1));
+            const float Y = fmaf(y, fmaf(yc, y, yb1), ya);
+            const bool inb = ((t & 1) ? gx0 + 4 : gx0) < W && qy0 + (t >> 1) < H;
+            Bop[t] = isg ? (inb ? G[t] : 0.f) : X[t & 1] * Y;
+        }
     }
     // A operand of K-step t: component (i >> 3) of element [slot i & 7][pixel 4 t + kq]
     const float *arow = reinterpret_cast<const float *>(&smat[wave][(j & 7) * MSTR + kq]) + (j >> 3);
@@ -739,7 +765,12 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
             if (idx < 576) {
                 const float val = sout[10 * e + col];
 #ifndef GSR_ABL_NOATOMIC
-                if (val != 0.f) atomicAdd(dL_record + 9 * (size_t)__float_as_uint(sout[10 * e + 9]) + col, (Acc)val);
+                if (val != 0.f) {
+                    const uint32_t id = __float_as_uint(sout[10 * e + 9]);
+                    atomicAdd(dL_record + 9 * (size_t)id + col, (Acc)val);
+                    // the rows that received anything (gsr_render_backward_seg_t): every writer stores the same byte
+                    if (touched) touched[id] = 1;
+                }
 #else
                 asm volatile("" ::"v"(val));
 #endif
@@ -763,7 +794,8 @@ composite_backward_kernel(int W, int H, int gx, int tiles, const int2 *__restric
                           const uint8_t *__restrict__ compute_locally, const float *__restrict__ bg,
                           const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
                           const float *__restrict__ dL_dpixels, Acc *__restrict__ dL_record,
-                          const float *__restrict__ out_color, const SegWs seg, int band_first, int band_tiles) {
+                          const float *__restrict__ out_color, const SegWs seg, int band_first, int band_tiles,
+                          uint8_t *__restrict__ touched) {
     // workgroups [0, nstatic): segment 0 of every tile (of the band, when the caller named it: see K8), XCD-contiguous
     // spans.  The others are persistent workers: they take the segments K8 queued (their number is only known on the
     // device) by atomic ticket.
@@ -795,7 +827,7 @@ composite_backward_kernel(int W, int H, int gx, int tiles, const int2 *__restric
                                   : composite_tile_of_block(ranges, gx, tiles);
         }
         composite_backward_segment(tile, sidx, W, H, gx, ranges, point_list, means2D, conic_opacity, rgb,
-                                   compute_locally, bg, final_T, n_contrib, dL_dpixels, dL_record, out_color, seg);
+                                   compute_locally, bg, final_T, n_contrib, dL_dpixels, dL_record, out_color, seg, touched);
         if (!worker) return;
     }
 }
@@ -868,14 +900,33 @@ __global__ void record_from_f64_kernel(const double *__restrict__ acc, float *__
     if (i < n) rec[i] = (float)acc[i];
 }
 
+// the same for the rows K10 touched only (gsr_render_backward_seg_t): lane = row.  K10 set touched[row] wherever it added
+// into the row; the forward's composite kernel left every other row of the record at 0.0f and of the sums at 0.0, which
+// is what the full pass would round them to, so those rows are neither read nor written: P bytes of flags plus 108
+// bytes per touched row.
+__global__ void record_from_f64_touched_kernel(const double *__restrict__ acc, float *__restrict__ rec,
+                                               const uint8_t *__restrict__ touched, int P) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= P || !touched[i]) return;
+    const double *a = acc + 9 * (size_t)i;
+    float *r = rec + 9 * (size_t)i;
+    double v[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) v[k] = a[k];
+#pragma unroll
+    for (int k = 0; k < 9; k++) r[k] = (float)v[k];
+}
+
 int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
                                   const float *means2D, const float *conic_opacity, const float *rgb,
                                   const uint8_t *compute_locally, const float *bg, const float *final_T,
                                   const int32_t *n_contrib, const float *dL_dpixels, float *dL_record,
                                   const float *out_color, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
-                                  int record_is_zero, hipStream_t stream, double *acc64) {
+                                  int record_is_zero, hipStream_t stream, double *acc64, uint8_t *touched) {
     // (record_is_zero: the forward launch cleared the buffer K10 adds into -- the record, or acc64 when given --
-    // gsr_render_forward_seg_z; acc64: [P,9] fp64 sums, rounded once to the record afterwards, which is written whole)
+    // gsr_render_forward_seg_z; acc64: [P,9] fp64 sums, rounded once to the record afterwards, which is written whole;
+    // touched: [P] row flags -- the forward cleared sums, record AND flags, only the rows K10 flags are rounded)
+    if (!record_is_zero || !acc64) touched = nullptr;
     if (!record_is_zero) {
         if (acc64) GSR_HIP(hipMemsetAsync(acc64, 0, sizeof(double) * 9 * (size_t)P, stream));
         else GSR_HIP(hipMemsetAsync(dL_record, 0, sizeof(float) * 9 * (size_t)P, stream));
@@ -898,16 +949,21 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
         hipLaunchKernelGGL(composite_backward_kernel<double>, grid, dim3(256), 0, stream, W, H, gx, gx * gy,
                            reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
                            reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
-                           dL_dpixels, acc64, out_color, seg, band_first, band_tiles);
+                           dL_dpixels, acc64, out_color, seg, band_first, band_tiles, touched);
         GSR_LAUNCH_CHECK();
         const size_t n = 9 * (size_t)P;
-        hipLaunchKernelGGL(record_from_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, acc64,
-                           dL_record, n);
+        if (touched)
+            hipLaunchKernelGGL(record_from_f64_touched_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream,
+                               acc64, dL_record, touched, P);
+        else
+            hipLaunchKernelGGL(record_from_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, acc64,
+                               dL_record, n);
     } else {
         hipLaunchKernelGGL(composite_backward_kernel<float>, grid, dim3(256), 0, stream, W, H, gx, gx * gy,
                            reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
                            reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
-                           dL_dpixels, dL_record, out_color, seg, band_first, band_tiles);
+                           dL_dpixels, dL_record, out_color, seg, band_first, band_tiles,
+                           static_cast<uint8_t *>(nullptr));
     }
     GSR_LAUNCH_CHECK();
     return 0;

@@ -795,6 +795,8 @@ _SPECULATIVE_SORT = [os.environ.get("GSR_SPECULATIVE_SORT", "1") != "0"]  # env:
 _SEGMENTS = [{"0": False, "always": "always"}.get(os.environ.get("GSR_SEGMENTS", "1"), True)]  # env: A/B only
 _BAND_GRID = [os.environ.get("GSR_BAND_GRID", "1") != "0"]  # env: A/B measurements only
 _ZERO_IN_FORWARD = [os.environ.get("GSR_ZERO_IN_FORWARD", "1") != "0"]  # env: A/B measurements only
+_KEEP_BACKWARD_BUFFERS = [None]  # tests: a list here receives every composite backward's (record, fp64 sums, row flags)
+_TOUCHED_ROWS = [os.environ.get("GSR_TOUCHED_ROWS", "1") != "0"]  # env: A/B measurements only (0: the full rounding pass)
 
 
 def set_list_segments(on):
@@ -1151,12 +1153,24 @@ class _RenderGaussians(torch.autograd.Function):
             # K10's [P,9] gradient record (means2D 0:2, rgb 2:5, conic_opacity 5:9) and the [P,9] fp64 sums it is rounded
             # from are allocated HERE when a backward can follow; the sums are cleared by K8's own workgroups
             # (include/gsraster.h: gsr_render_forward_seg_z) instead of by a 72 MB fill launch at the head of the
-            # backward, and the record is written whole by the backward
-            record = acc64 = None
+            # backward.  With them, in the same buffer, go the record's own rows and one byte per row that K10 sets
+            # where it adds into the row (gsr_render_backward_seg_t): [72 P | 36 P | P, padded to 16] bytes, all cleared
+            # here, so that the backward rounds only the rows K10 touched and every other row of the record is the 0.0f
+            # the forward left
+            record = acc64 = touched = None
+            zero_buf, zero_bytes = None, 0
             if any(ctx.needs_input_grad[:3]) and P > 0 and _ZERO_IN_FORWARD[0]:
-                record = torch.empty((P, 9), dtype=torch.float32, device=dev)
-                acc64 = torch.empty((P, 9), dtype=torch.float64, device=dev)
-            ctx.record = (record, acc64) if record is not None else None
+                if _TOUCHED_ROWS[0]:
+                    zero_bytes = 108 * P + ((P + 15) & ~15)
+                    zero_buf = torch.empty((zero_bytes,), dtype=torch.uint8, device=dev)
+                    acc64 = zero_buf[:72 * P].view(torch.float64).view(P, 9)
+                    record = zero_buf[72 * P:108 * P].view(torch.float32).view(P, 9)
+                    touched = zero_buf[108 * P:109 * P]
+                else:
+                    record = torch.empty((P, 9), dtype=torch.float32, device=dev)
+                    zero_buf = acc64 = torch.empty((P, 9), dtype=torch.float64, device=dev)
+                    zero_bytes = 72 * P
+            ctx.record = (record, acc64, touched) if record is not None else None
 
             def launch_k8(meta_D):
                 with kernel_timer.range("composite_forward", P=P, D=meta_D, **ctx.px_meta) as k8t, \
@@ -1164,7 +1178,7 @@ class _RenderGaussians(torch.autograd.Function):
                     check(lib.gsr_render_forward_seg_z(P, W, H, _ptr(ranges), _ptr(lists[0]), _ptr(means2D),
                                                        _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(out),
                                                        _ptr(final_T), _ptr(n_contrib), _ptr(seg_ws), seg_bytes, row_lo,
-                                                       row_hi, _ptr(acc64), 72 * P if acc64 is not None else 0,
+                                                       row_hi, _ptr(zero_buf), zero_bytes,
                                                        _stream()), "gsr_render_forward_seg_z")
                 return k8t
 
@@ -1231,10 +1245,12 @@ class _RenderGaussians(torch.autograd.Function):
         # reproducible from run to run in practice (fp32 atomic adds made it depend on the order the tiles finished)
         pair, ctx.record = ctx.record, None
         record_is_zero = pair is not None
-        if pair is None:
+        if pair is None:  # (no flags: every row is rounded)
             pair = (torch.empty((P, 9), dtype=torch.float32, device=dev),
-                    torch.empty((P, 9), dtype=torch.float64, device=dev))
-        record, acc64 = pair
+                    torch.empty((P, 9), dtype=torch.float64, device=dev), None)
+        record, acc64, touched = pair
+        if _KEEP_BACKWARD_BUFFERS[0] is not None:
+            _KEEP_BACKWARD_BUFFERS[0].append(pair)
         d_means2D, d_rgb, d_conic_opacity = record[:, 0:2], record[:, 2:5], record[:, 5:9]
         timing = ctx.timing
         with _on(dev):
@@ -1248,11 +1264,11 @@ class _RenderGaussians(torch.autograd.Function):
             with kernel_timer.range("composite_backward", P=P, D=ctx.num_rendered, **ctx.px_meta), \
                     zhx_range(ctx.cuda_args, "b10 render time"):
                 seg_ws, seg_bytes, row_lo, row_hi = ctx.seg
-                check(lib.gsr_render_backward_seg_d(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                check(lib.gsr_render_backward_seg_t(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
                                                     _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(final_T),
                                                     _ptr(n_contrib), _ptr(g_out), _ptr(record), _ptr(out_img),
                                                     _ptr(seg_ws), seg_bytes, row_lo, row_hi, 1 if record_is_zero else 0,
-                                                    _ptr(acc64), _stream()), "gsr_render_backward_seg_d")
+                                                    _ptr(acc64), _ptr(touched), _stream()), "gsr_render_backward_seg_t")
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("bwd1", id(cap_stats))
             if timing != "off":

@@ -336,6 +336,20 @@ int gsr_render_backward_seg_d(int P, int width, int height, const int32_t *range
                               const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
                               void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero,
                               double *acc64, gsr_stream_t stream);
+/* gsr_render_backward_seg_t (the training backward; a new symbol, the ABI version stays): gsr_render_backward_seg_d plus
+ * `touched`, [P] bytes.  K10 sets touched[row] = 1 wherever it adds into a row of acc64, and only those rows are rounded
+ * into the record (K10 reaches about a tenth of the rows of a 10^6-Gaussian scene; the full pass reads 72 and writes
+ * 36 bytes for every row).  For that the FORWARD must have cleared the sums, the record and the flags: the caller lays
+ * them out as one buffer, [72 P | 36 P | P, padded to 16] bytes = acc64, record, touched, and passes all of it as
+ * (zero_ptr, zero_bytes) of gsr_render_forward_seg_z; record_is_zero = 1 says so.  The record is then complete when the
+ * call returns, exactly as after gsr_render_backward_seg_d, bit for bit.  touched == NULL or record_is_zero == 0:
+ * gsr_render_backward_seg_d itself (the full pass). */
+int gsr_render_backward_seg_t(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                              const float *means2D, const float *conic_opacity, const float *rgb,
+                              const uint8_t *compute_locally, const float *bg, const float *final_T,
+                              const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
+                              void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero,
+                              double *acc64, uint8_t *touched, gsr_stream_t stream);
 /* Measurement aid (bench.py's roofline leg; the reference has nothing to bind here): list entries the composite kernels
  * WALKED since the last reset, summed over launches -- out2[0] K8, out2[1] K10; per tile the entries its longest-walking
  * quadrant goes through (K8: up to the chunk in which the last pixel saturates; K10: the largest n_contrib of the
