@@ -1,6 +1,7 @@
 // preprocess.hip -- K1 (per-Gaussian projection + SH colour) and K11 (its backward) for gfx950.
 //
-// One lane per Gaussian, 256-thread workgroups (4 waves).  Both kernels are pure HBM streaming:
+// One lane per Gaussian: 256-thread workgroups (4 waves) forward, 128-thread workgroups (K11_BLOCK, 2 waves) backward.
+// Both kernels are pure HBM streaming:
 // 236 B in / 44+31 B out per Gaussian forward, 552 B per Gaussian backward.
 // Camera matrices are wave-uniform and are read through the scalar cache into SGPRs.
 //
@@ -8,8 +9,6 @@
 // gaussian_renderer/__init__.py:949-960).  The forward geometry is compiled with FP contraction
 // off so that integer outputs (radii, tile rects) are reproducible against a plain C evaluation.
 #include "common.h"
-
-#include <cstdlib>
 
 // no FMA contraction in this file: see the header comment (memory-bound kernels, no cost)
 #pragma clang fp contract(off)
@@ -101,6 +100,348 @@ __device__ __forceinline__ void eval_sh(const float *__restrict__ sh, float x, f
     }
 }
 
+// ------------------------------------------------------------------- the projection math, one copy
+// Every kernel below is built from these pieces.  They only compute: what is loaded where, what is stored where and in
+// which order partial gradients are added stays with the kernels (with contraction off the same expression gives the
+// same bits wherever it is inlined, so the fused, batched and camera-gradient kernels agree with K11 exactly).
+
+// t = [p, 1] * viewmatrix: the position in camera space
+__device__ __forceinline__ void view_transform(const float *v, const float (&p)[3], float (&t)[3]) {
+    t[0] = v[0] * p[0] + v[4] * p[1] + v[8] * p[2] + v[12];
+    t[1] = v[1] * p[0] + v[5] * p[1] + v[9] * p[2] + v[13];
+    t[2] = v[2] * p[0] + v[6] * p[1] + v[10] * p[2] + v[14];
+}
+
+// [p, 1] * projmatrix: x, y and mw = 1 / (w + 1e-7)
+__device__ __forceinline__ void project_hom(const float *pm, const float (&p)[3], float &phx, float &phy, float &mw) {
+    phx = pm[0] * p[0] + pm[4] * p[1] + pm[8] * p[2] + pm[12];
+    phy = pm[1] * p[0] + pm[5] * p[1] + pm[9] * p[2] + pm[13];
+    const float phw = pm[3] * p[0] + pm[7] * p[1] + pm[11] * p[2] + pm[15];
+    mw = 1.0f / (phw + 0.0000001f);
+}
+
+// the getters' activations of the raw parameters (scene/gaussian_model.py:109-129)
+__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float4 quat_normalize(const float4 q, float &qnr, float &qn) {
+    qnr = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    qn = fmaxf(qnr, 1e-12f);
+    return make_float4(q.x / qn, q.y / qn, q.z / qn, q.w / qn);
+}
+
+// Sigma = R S S R^T from the ACTIVATED quaternion and scales (s includes the scale modifier)
+__device__ __forceinline__ void cov3d_from_scale_rot(const float4 q, const float (&s)[3], float (&S)[3][3]) {
+    float R[3][3];
+    quat_to_R(q, R);
+    float L[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) L[a][b] = R[a][b] * s[b];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) S[a][b] = L[a][0] * L[b][0] + L[a][1] * L[b][1] + L[a][2] * L[b][2];
+}
+// the six stored words of Sigma (upper triangle) as the full matrix
+__device__ __forceinline__ void cov3d_unpack(const float *cv, float (&S)[3][3]) {
+    S[0][0] = cv[0]; S[0][1] = cv[1]; S[0][2] = cv[2];
+    S[1][0] = cv[1]; S[1][1] = cv[3]; S[1][2] = cv[4];
+    S[2][0] = cv[2]; S[2][1] = cv[4]; S[2][2] = cv[5];
+}
+
+// cov2D = T Sigma T^T + 0.3 I = [[a, b], [b, c]]; ST0 / ST1 = Sigma T^T's columns, which the backward needs again
+__device__ __forceinline__ void cov2d_abc(const float (&S)[3][3], const float (&T)[2][3], float (&ST0)[3],
+                                          float (&ST1)[3], float &a, float &b, float &c) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        ST0[r] = S[r][0] * T[0][0] + S[r][1] * T[0][1] + S[r][2] * T[0][2];
+        ST1[r] = S[r][0] * T[1][0] + S[r][1] * T[1][1] + S[r][2] * T[1][2];
+    }
+    a = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2] + 0.3f;
+    b = T[0][0] * ST1[0] + T[0][1] * ST1[1] + T[0][2] * ST1[2];
+    c = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2] + 0.3f;
+}
+
+// The geometry of one (Gaussian, camera) pair in front of the near plane (the caller culls t[2] <= 0.2 BEFORE it loads
+// what Sigma is made of): conic, radius and pixel centre.  false: culled (singular cov2D, or a rect of no tiles); g is
+// then not to be used.  Straight-line on purpose, with ONE test at the end: with a return after each of the two culls
+// the camera-batched forward needed 4-6 registers more and lost a wave per SIMD at degrees 0 and 1.
+struct Geom2D {
+    int rad;
+    float2 xy;
+    float conic[3];
+};
+__device__ __forceinline__ bool project_geometry(const Cam &cam, float tanfovx, float tanfovy, float fx, float fy, int W,
+                                                 int H, int gx, int gy, const float (&p)[3], const float (&t)[3],
+                                                 const float (&S)[3][3], Geom2D &g) {
+    float phx, phy, pw;
+    project_hom(cam.p, p, phx, phy, pw);
+    const float pprojx = phx * pw, pprojy = phy * pw;
+    float T[2][3], tc[3];
+    bool xin, yin;
+    compute_T(t, cam.v, fx, fy, tanfovx, tanfovy, T, tc, xin, yin);
+    float ST0[3], ST1[3], a, b, c;
+    cov2d_abc(S, T, ST0, ST1, a, b, c);
+    const float det = a * c - b * b;
+    const float det_inv = 1.f / det;
+    const float mid = 0.5f * (a + c);
+    const float lam = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
+    g.rad = (int)ceilf(3.f * sqrtf(lam));
+    const float px = ((pprojx + 1.0f) * W - 1.0f) * 0.5f;
+    const float py = ((pprojy + 1.0f) * H - 1.0f) * 0.5f;
+    int minx, miny, maxx, maxy;
+    gsr_get_rect(px, py, g.rad, gx, gy, minx, miny, maxx, maxy);
+    g.xy = make_float2(px, py);
+    g.conic[0] = c * det_inv;
+    g.conic[1] = -b * det_inv;
+    g.conic[2] = a * det_inv;
+    return det != 0.0f && (maxx - minx) * (maxy - miny) != 0;
+}
+
+// colour from SH along the world-space view direction, +0.5, clamped at 0 (cl: which channels clamped)
+template <int DEG>
+__device__ __forceinline__ void shade(const float (&campos)[3], const float (&p)[3], const float *__restrict__ sh,
+                                      float (&col)[3], bool (&cl)[3]) {
+    float d[3] = {p[0] - campos[0], p[1] - campos[1], p[2] - campos[2]};
+    const float inv = 1.0f / sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    d[0] *= inv;
+    d[1] *= inv;
+    d[2] *= inv;
+    eval_sh<DEG>(sh, d[0], d[1], d[2], col);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        col[k] += 0.5f;
+        cl[k] = col[k] < 0.f;
+        col[k] = fmaxf(col[k], 0.f);
+    }
+}
+
+// conic gradient (gA, gB, gC) -> cov2D -> T = J Wc -> (Sigma, t) of one (Gaussian, camera) pair
+struct Cov2DGrad {
+    bool live;       // 1 / (denom^2 + 1e-7) != 0: otherwise dL/d(a, b, c) and dcov are zero
+    float dcov[6];   // this pair's dL/dSigma, upper triangle (off-diagonal entries count both halves)
+    float dT0[3], dT1[3];
+    float dt[3], tc[3];  // dL/dt, and t with the Jacobian's clamp
+    float dmean[3];      // dt through the view matrix: the pair's cov2D part of dL/dmean
+};
+__device__ __forceinline__ Cov2DGrad cov2d_backward(const float *v, float fx, float fy, float tanfovx, float tanfovy,
+                                                    const float (&p)[3], const float (&S)[3][3], float gA, float gB,
+                                                    float gC) {
+    Cov2DGrad o;
+    float t[3];
+    view_transform(v, p, t);
+    float T[2][3];
+    bool xin, yin;
+    compute_T(t, v, fx, fy, tanfovx, tanfovy, T, o.tc, xin, yin);
+    float ST0[3], ST1[3], a, b, c;
+    cov2d_abc(S, T, ST0, ST1, a, b, c);
+    const float denom = a * c - b * b;
+    const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+    float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
+#pragma unroll
+    for (int e = 0; e < 6; e++) o.dcov[e] = 0.f;
+    o.live = denom2inv != 0.f;
+    if (o.live) {
+        dL_da = denom2inv * (-c * c * gA + b * c * gB + (denom - a * c) * gC);
+        dL_dc = denom2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
+        dL_db = denom2inv * (2.f * b * c * gA - (denom + 2.f * b * b) * gB + 2.f * a * b * gC);
+        o.dcov[0] = T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc;
+        o.dcov[3] = T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc;
+        o.dcov[5] = T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc;
+        o.dcov[1] = 2.f * T[0][0] * T[0][1] * dL_da + (T[0][0] * T[1][1] + T[0][1] * T[1][0]) * dL_db +
+                    2.f * T[1][0] * T[1][1] * dL_dc;
+        o.dcov[2] = 2.f * T[0][0] * T[0][2] * dL_da + (T[0][0] * T[1][2] + T[0][2] * T[1][0]) * dL_db +
+                    2.f * T[1][0] * T[1][2] * dL_dc;
+        o.dcov[4] = 2.f * T[0][2] * T[0][1] * dL_da + (T[0][1] * T[1][2] + T[0][2] * T[1][1]) * dL_db +
+                    2.f * T[1][1] * T[1][2] * dL_dc;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        o.dT0[k] = 2.f * ST0[k] * dL_da + ST1[k] * dL_db;
+        o.dT1[k] = 2.f * ST1[k] * dL_dc + ST0[k] * dL_db;
+    }
+    const float dJ00 = o.dT0[0] * v[0] + o.dT0[1] * v[4] + o.dT0[2] * v[8];
+    const float dJ02 = o.dT0[0] * v[2] + o.dT0[1] * v[6] + o.dT0[2] * v[10];
+    const float dJ11 = o.dT1[0] * v[1] + o.dT1[1] * v[5] + o.dT1[2] * v[9];
+    const float dJ12 = o.dT1[0] * v[2] + o.dT1[1] * v[6] + o.dT1[2] * v[10];
+    const float tz = 1.f / o.tc[2], tz2 = tz * tz, tz3 = tz2 * tz;
+    o.dt[0] = (xin ? 1.f : 0.f) * (-fx * tz2 * dJ02);
+    o.dt[1] = (yin ? 1.f : 0.f) * (-fy * tz2 * dJ12);
+    o.dt[2] = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.f * fx * o.tc[0]) * tz3 * dJ02 + (2.f * fy * o.tc[1]) * tz3 * dJ12;
+#pragma unroll
+    for (int k = 0; k < 3; k++) o.dmean[k] = v[k * 4 + 0] * o.dt[0] + v[k * 4 + 1] * o.dt[1] + v[k * 4 + 2] * o.dt[2];
+    return o;
+}
+
+// the perspective divide of means2D (NDC-scaled): mw = 1 / (w + 1e-7), mul1 = x mw^2, mul2 = y mw^2
+__device__ __forceinline__ void perspective_backward(const float *pm, const float (&p)[3], float &mw, float &mul1,
+                                                     float &mul2) {
+    float phx, phy;
+    project_hom(pm, p, phx, phy, mw);
+    mul1 = phx * mw * mw;
+    mul2 = phy * mw * mw;
+}
+// ... and the means2D part of dL/dmean that K11 forms from it
+__device__ __forceinline__ void means2d_to_mean(const float *pm, const float (&p)[3], const float2 g2, float (&dm)[3]) {
+    float mw, mul1, mul2;
+    perspective_backward(pm, p, mw, mul1, mul2);
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        dm[k] = (pm[k * 4 + 0] * mw - pm[k * 4 + 3] * mul1) * g2.x + (pm[k * 4 + 1] * mw - pm[k * 4 + 3] * mul2) * g2.y;
+}
+
+// the accessors and sinks of sh_backward below (named functors: hipcc 7.2 crashes in its inliner on closures here)
+struct ShRegs {  // coefficients in registers, [k][ch]
+    const float *sh;
+    __device__ __forceinline__ float operator()(int k, int ch) const { return sh[k * 3 + ch]; }
+};
+struct ShStagedOrRegs {  // the batched kernel: the coefficients above DC in the LDS stage, or all of them in registers
+    bool staged;
+    const float *lds, *sh;
+    __device__ __forceinline__ float operator()(int k, int ch) const { return staged ? lds[k * 3 + ch - 3] : sh[k * 3 + ch]; }
+};
+struct DshAssign {
+    float *dsh;
+    __device__ __forceinline__ void operator()(int k, int ch, float v) const { dsh[k * 3 + ch] = v; }
+};
+struct DshAdd {
+    float *dsh;
+    __device__ __forceinline__ void operator()(int k, int ch, float v) const { dsh[k * 3 + ch] += v; }
+};
+struct DshDrop {
+    __device__ __forceinline__ void operator()(int, int, float) const {}
+};
+
+// Colour gradient g (0 for a clamped channel) -> SH coefficients and unit view direction (x, y, z).
+//   sh(k, ch):        coefficient k >= 1 of channel ch -- registers, or the LDS stage of the batched kernel
+//   dsh(k, ch, v):    receives dL/d(coefficient k of channel ch) -- assigned by the one-camera body, accumulated over
+//                     the cameras by the batched one, dropped by K11c
+//   ddir:             d colour / d direction contracted with g
+template <int DEG, typename SH, typename DSH>
+__device__ __forceinline__ void sh_backward(const SH &sh, float x, float y, float z, const float (&g3)[3],
+                                            const DSH &dsh, float (&ddir)[3]) {
+    ddir[0] = ddir[1] = ddir[2] = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const float g = g3[ch];
+        float dx = 0.f, dy = 0.f, dz = 0.f;
+        dsh(0, ch, SH_C0 * g);
+        if (DEG > 0) {
+            dsh(1, ch, -SH_C1 * y * g);
+            dsh(2, ch, SH_C1 * z * g);
+            dsh(3, ch, -SH_C1 * x * g);
+            dx = -SH_C1 * sh(3, ch);
+            dy = -SH_C1 * sh(1, ch);
+            dz = SH_C1 * sh(2, ch);
+            if (DEG > 1) {
+                const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+                dsh(4, ch, SH_C2[0] * xy * g);
+                dsh(5, ch, SH_C2[1] * yz * g);
+                dsh(6, ch, SH_C2[2] * (2.f * zz - xx - yy) * g);
+                dsh(7, ch, SH_C2[3] * xz * g);
+                dsh(8, ch, SH_C2[4] * (xx - yy) * g);
+                dx += SH_C2[0] * y * sh(4, ch) + SH_C2[2] * 2.f * -x * sh(6, ch) + SH_C2[3] * z * sh(7, ch) +
+                      SH_C2[4] * 2.f * x * sh(8, ch);
+                dy += SH_C2[0] * x * sh(4, ch) + SH_C2[1] * z * sh(5, ch) + SH_C2[2] * 2.f * -y * sh(6, ch) +
+                      SH_C2[4] * 2.f * -y * sh(8, ch);
+                dz += SH_C2[1] * y * sh(5, ch) + SH_C2[2] * 2.f * 2.f * z * sh(6, ch) + SH_C2[3] * x * sh(7, ch);
+                if (DEG > 2) {
+                    dsh(9, ch, SH_C3[0] * y * (3.f * xx - yy) * g);
+                    dsh(10, ch, SH_C3[1] * xy * z * g);
+                    dsh(11, ch, SH_C3[2] * y * (4.f * zz - xx - yy) * g);
+                    dsh(12, ch, SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * g);
+                    dsh(13, ch, SH_C3[4] * x * (4.f * zz - xx - yy) * g);
+                    dsh(14, ch, SH_C3[5] * z * (xx - yy) * g);
+                    dsh(15, ch, SH_C3[6] * x * (xx - 3.f * yy) * g);
+                    dx += SH_C3[0] * sh(9, ch) * 3.f * 2.f * xy + SH_C3[1] * sh(10, ch) * yz +
+                          SH_C3[2] * sh(11, ch) * -2.f * xy + SH_C3[3] * sh(12, ch) * -3.f * 2.f * xz +
+                          SH_C3[4] * sh(13, ch) * (-3.f * xx + 4.f * zz - yy) + SH_C3[5] * sh(14, ch) * 2.f * xz +
+                          SH_C3[6] * sh(15, ch) * 3.f * (xx - yy);
+                    dy += SH_C3[0] * sh(9, ch) * 3.f * (xx - yy) + SH_C3[1] * sh(10, ch) * xz +
+                          SH_C3[2] * sh(11, ch) * (-3.f * yy + 4.f * zz - xx) + SH_C3[3] * sh(12, ch) * -3.f * 2.f * yz +
+                          SH_C3[4] * sh(13, ch) * -2.f * xy + SH_C3[5] * sh(14, ch) * -2.f * yz +
+                          SH_C3[6] * sh(15, ch) * -3.f * 2.f * xy;
+                    dz += SH_C3[1] * sh(10, ch) * xy + SH_C3[2] * sh(11, ch) * 4.f * 2.f * yz +
+                          SH_C3[3] * sh(12, ch) * 3.f * (2.f * zz - xx - yy) + SH_C3[4] * sh(13, ch) * 4.f * 2.f * xz +
+                          SH_C3[5] * sh(14, ch) * (xx - yy);
+                }
+            }
+        }
+        ddir[0] += dx * g;
+        ddir[1] += dy * g;
+        ddir[2] += dz * g;
+    }
+}
+// ... with the direction formed from p - campos in front and carried back to the position behind: dm is the pair's
+// view-direction part of dL/dmean (and minus its part of dL/dcampos)
+template <int DEG, typename SH, typename DSH>
+__device__ __forceinline__ void viewdir_backward(const float (&campos)[3], const float (&p)[3], const SH &sh,
+                                                 const float (&g3)[3], const DSH &dsh, float (&dm)[3]) {
+    const float dox = p[0] - campos[0], doy = p[1] - campos[1], doz = p[2] - campos[2];
+    const float len = sqrtf(dox * dox + doy * doy + doz * doz);
+    const float x = dox / len, y = doy / len, z = doz / len;
+    float ddir[3];
+    sh_backward<DEG>(sh, x, y, z, g3, dsh, ddir);
+    const float dot = x * ddir[0] + y * ddir[1] + z * ddir[2];
+    dm[0] = (ddir[0] - x * dot) / len;
+    dm[1] = (ddir[1] - y * dot) / len;
+    dm[2] = (ddir[2] - z * dot) / len;
+}
+
+// dL/dSigma (dcov, as Cov2DGrad's) -> scales and quaternion.  Sigma = M^T M, M = S R^T.  RAW: q and sc are the raw
+// parameters and the gradients go through their activations (normalize, exp) as well.
+template <bool RAW>
+__device__ __forceinline__ void cov3d_backward(const float4 qraw, const float (&scraw)[3], float scale_modifier,
+                                               const float (&dcov)[6], float (&gsc)[3], float4 &dq) {
+    float4 q = qraw;
+    float sc[3] = {scraw[0], scraw[1], scraw[2]};
+    float qn = 1.f, qnr = 1.f;
+    if (RAW) {
+        q = quat_normalize(qraw, qnr, qn);
+        sc[0] = expf(sc[0]);
+        sc[1] = expf(sc[1]);
+        sc[2] = expf(sc[2]);
+    }
+    float R[3][3];
+    quat_to_R(q, R);
+    const float s[3] = {scale_modifier * sc[0], scale_modifier * sc[1], scale_modifier * sc[2]};
+    float Mm[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int cc = 0; cc < 3; cc++) Mm[r][cc] = s[r] * R[cc][r];
+    const float dS[3][3] = {{dcov[0], 0.5f * dcov[1], 0.5f * dcov[2]},
+                            {0.5f * dcov[1], dcov[3], 0.5f * dcov[4]},
+                            {0.5f * dcov[2], 0.5f * dcov[4], dcov[5]}};
+    float dM[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int cc = 0; cc < 3; cc++)
+            dM[r][cc] = 2.f * (Mm[r][0] * dS[0][cc] + Mm[r][1] * dS[1][cc] + Mm[r][2] * dS[2][cc]);
+    float dR[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        gsc[r] = (RAW ? sc[r] : 1.f) *  // d exp(x) = exp(x) dx
+                 scale_modifier * (R[0][r] * dM[r][0] + R[1][r] * dM[r][1] + R[2][r] * dM[r][2]);
+#pragma unroll
+        for (int j = 0; j < 3; j++) dR[j][r] = s[r] * dM[r][j];
+    }
+    const float r_ = q.x, x = q.y, y = q.z, z = q.w;
+    dq.x = 2.f * (-z * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
+    dq.y = 2.f * (y * dR[0][1] + z * dR[0][2] + y * dR[1][0] - 2.f * x * dR[1][1] - r_ * dR[1][2] + z * dR[2][0] +
+                  r_ * dR[2][1] - 2.f * x * dR[2][2]);
+    dq.z = 2.f * (-2.f * y * dR[0][0] + x * dR[0][1] + r_ * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r_ * dR[2][0] +
+                  z * dR[2][1] - 2.f * y * dR[2][2]);
+    dq.w = 2.f * (-2.f * z * dR[0][0] - r_ * dR[0][1] + x * dR[0][2] + r_ * dR[1][0] - 2.f * z * dR[1][1] +
+                  y * dR[1][2] + x * dR[2][0] + y * dR[2][1]);
+    if (RAW) {  // through q = x / max(|x|, 1e-12)
+        const float dot = qnr > 1e-12f ? (q.x * dq.x + q.y * dq.y + q.z * dq.z + q.w * dq.w) : 0.f;
+        dq = make_float4((dq.x - q.x * dot) / qn, (dq.y - q.y * dot) / qn, (dq.z - q.z * dot) / qn,
+                         (dq.w - q.w * dot) / qn);
+    }
+}
+
 // ------------------------------------------------------------------------------------------- K1
 // RAW = true: the inputs are the RAW parameters of GaussianModel (log-scales, un-normalised quaternions,
 // opacity logits, SH split into _features_dc [N,1,3] = `shs` and _features_rest [N,M-1,3] = `shs_rest`) and the
@@ -131,70 +472,24 @@ preprocess_forward_kernel(int P, int M, const float *__restrict__ means3D, const
 
     const float p[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
     float t[3];
-    t[0] = cam.v[0] * p[0] + cam.v[4] * p[1] + cam.v[8] * p[2] + cam.v[12];
-    t[1] = cam.v[1] * p[0] + cam.v[5] * p[1] + cam.v[9] * p[2] + cam.v[13];
-    t[2] = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
+    view_transform(cam.v, p, t);
     do {
         if (t[2] <= 0.2f) break;  // near-plane cull
-        const float phx = cam.p[0] * p[0] + cam.p[4] * p[1] + cam.p[8] * p[2] + cam.p[12];
-        const float phy = cam.p[1] * p[0] + cam.p[5] * p[1] + cam.p[9] * p[2] + cam.p[13];
-        const float phw = cam.p[3] * p[0] + cam.p[7] * p[1] + cam.p[11] * p[2] + cam.p[15];
-        const float pw = 1.0f / (phw + 0.0000001f);
-        const float pprojx = phx * pw, pprojy = phy * pw;
-
-        // Sigma = R S S R^T
-        float R[3][3];
         float4 q = *reinterpret_cast<const float4 *>(rotations + 4 * (size_t)i);
         float sc[3] = {scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]};
         if (RAW) {
-            const float qn = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f);
-            q = make_float4(q.x / qn, q.y / qn, q.z / qn, q.w / qn);
+            float qnr, qn;
+            q = quat_normalize(q, qnr, qn);
             sc[0] = expf(sc[0]);
             sc[1] = expf(sc[1]);
             sc[2] = expf(sc[2]);
         }
-        quat_to_R(q, R);
         const float s[3] = {scale_modifier * sc[0], scale_modifier * sc[1], scale_modifier * sc[2]};
-        float L[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++) L[a][b] = R[a][b] * s[b];
         float S[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++) S[a][b] = L[a][0] * L[b][0] + L[a][1] * L[b][1] + L[a][2] * L[b][2];
-        float T[2][3], tc[3];
-        bool xin, yin;
-        compute_T(t, cam.v, fx, fy, tanfovx, tanfovy, T, tc, xin, yin);
-        float ST0[3], ST1[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            ST0[r] = S[r][0] * T[0][0] + S[r][1] * T[0][1] + S[r][2] * T[0][2];
-            ST1[r] = S[r][0] * T[1][0] + S[r][1] * T[1][1] + S[r][2] * T[1][2];
-        }
-        const float a = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2] + 0.3f;
-        const float b = T[0][0] * ST1[0] + T[0][1] * ST1[1] + T[0][2] * ST1[2];
-        const float c = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2] + 0.3f;
-        const float det = a * c - b * b;
-        if (det == 0.0f) break;
-        const float det_inv = 1.f / det;
-        const float mid = 0.5f * (a + c);
-        const float lam = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
-        const int rad = (int)ceilf(3.f * sqrtf(lam));
-        const float px = ((pprojx + 1.0f) * W - 1.0f) * 0.5f;
-        const float py = ((pprojy + 1.0f) * H - 1.0f) * 0.5f;
-        int minx, miny, maxx, maxy;
-        gsr_get_rect(px, py, rad, gx, gy, minx, miny, maxx, maxy);
-        if ((maxx - minx) * (maxy - miny) == 0) break;
+        cov3d_from_scale_rot(q, s, S);
+        Geom2D g;
+        if (!project_geometry(cam, tanfovx, tanfovy, fx, fy, W, H, gx, gy, p, t, S, g)) break;
 
-        // colour from SH, view direction in world space
-        float d[3] = {p[0] - cam.c[0], p[1] - cam.c[1], p[2] - cam.c[2]};
-        const float inv = 1.0f / sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        d[0] *= inv;
-        d[1] *= inv;
-        d[2] *= inv;
         float shl[(DEG + 1) * (DEG + 1) * 3];
         const float *shp = shs + (size_t)i * M * 3;
         if (RAW) {
@@ -218,20 +513,13 @@ preprocess_forward_kernel(int P, int M, const float *__restrict__ means3D, const
 #pragma unroll
             for (int k = 0; k < (DEG + 1) * (DEG + 1) * 3; k++) shl[k] = shp[k];
         }
-        eval_sh<DEG>(shl, d[0], d[1], d[2], col);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            col[k] += 0.5f;
-            cl[k] = col[k] < 0.f;
-            col[k] = fmaxf(col[k], 0.f);
-        }
-        radius = rad;
-        xy = make_float2(px, py);
+        shade<DEG>(cam.c, p, shl, col, cl);
+        radius = g.rad;
+        xy = g.xy;
         depth = t[2];
         cov[0] = S[0][0]; cov[1] = S[0][1]; cov[2] = S[0][2];
         cov[3] = S[1][1]; cov[4] = S[1][2]; cov[5] = S[2][2];
-        co = make_float4(c * det_inv, -b * det_inv, a * det_inv,
-                         RAW ? 1.0f / (1.0f + expf(-opacities[i])) : opacities[i]);
+        co = make_float4(g.conic[0], g.conic[1], g.conic[2], RAW ? sigmoidf(opacities[i]) : opacities[i]);
     } while (false);
 
     radii[i] = radius;
@@ -365,45 +653,15 @@ __device__ __forceinline__ K11Adam k11_adam_resolve(const K11Adam &in) {
 }
 
 // The 14 per-lane values (xyz 0-2, scaling 3-5, rotation 6-9, features_dc 10-12, opacity 13) are updated together at
-// the END of the lane's work: their 28 moment loads are then in flight at once (one exposed latency instead of five --
-// the first version updated each tensor where its gradient fell out and ran 0.50 ms against 0.355 ms for the two
-// kernels it replaces).  Plain (cacheable) accesses: a lane touches 4-byte pieces of 12 / 16 byte rows, neighbouring
-// lanes the rest of the line -- measured: streaming loads cost the kernel +0.027 ms (the line is fetched again for the
-// next piece), streaming stores alone +0.010 ms.
-__device__ __forceinline__ void k11_adam_small(const K11Adam &ad, size_t i, float *__restrict__ xyz,
-                                               float *__restrict__ scaling, float *__restrict__ rotation,
-                                               float *__restrict__ f_dc, float *__restrict__ opacity,
-                                               const float (&pv)[14], const float (&g)[14]) {
-    constexpr int T[14] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 5};
-    constexpr int K[14] = {3, 3, 3, 3, 3, 3, 4, 4, 4, 4, 3, 3, 3, 1};
-    constexpr int C[14] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 0};
-    float *const base[6] = {xyz, scaling, rotation, f_dc, nullptr, opacity};
-    float m[14], v[14];
-#pragma unroll
-    for (int e = 0; e < 14; e++) {
-        m[e] = ad.m[T[e]][i * K[e] + C[e]];
-        v[e] = ad.v[T[e]][i * K[e] + C[e]];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int e = 0; e < 14; e++) {
-        const int t = T[e];
-        float p = pv[e];
-        gsr_adam1(p, __fmul_rn(g[e], ad.grad_scale), m[e], v[e], ad.lr_c[t], ad.b1[t], ad.b2[t], ad.omb1[t],
-                  ad.omb2[t], ad.inv_sqrt_bc2[t], ad.eps[t]);
-        base[t][i * K[e] + C[e]] = p;
-        ad.m[t][i * K[e] + C[e]] = m[e];
-        ad.v[t][i * K[e] + C[e]] = v[e];
-    }
-}
-
-// The same update with the moments of the five small tensors moved through LDS (the one-camera fused kernel, after its
-// stage-out, when the _features_rest stage is free): every (tensor, moment) chunk of the workgroup -- K11_BLOCK rows of
-// 12 / 16 / 4 bytes, contiguous -- is read and written as ONE 16-byte streaming access per lane, and a lane picks its
-// 14 + 14 values out of LDS.  The per-lane 4-byte accesses of k11_adam_small have to stay cacheable (a streaming load
-// drops the line between a lane's pieces: +0.027 ms measured), and 224 MB of cacheable moment traffic per 10^6
-// Gaussians pushes the PARAMETERS out of the 256 MB memory-side cache -- the next iteration's K1 then reads them from
-// HBM (0.057 -> 0.075 ms).  Through LDS the moments stream past the cache like the optimizer kernel's.
+// the END of the lane's work (the first version updated each tensor where its gradient fell out, five exposed moment
+// latencies, and ran 0.50 ms against 0.355 ms for the two kernels it replaces), after the stage-out, when the
+// _features_rest stage is free, with the moments of the five small tensors moved through LDS: every (tensor, moment)
+// chunk of the workgroup -- K11_BLOCK rows of 12 / 16 / 4 bytes, contiguous -- is read and written as ONE 16-byte
+// streaming access per lane, and a lane picks its 14 + 14 values out of LDS.  Per-lane 4-byte accesses to the moments
+// (the version before this one) have to stay cacheable (a streaming load drops the line between a lane's pieces:
+// +0.027 ms measured, streaming stores alone +0.010 ms), and 224 MB of cacheable moment traffic per 10^6 Gaussians
+// pushes the PARAMETERS out of the 256 MB memory-side cache -- the next iteration's K1 then reads them from HBM
+// (0.057 -> 0.075 ms).  Through LDS the moments stream past the cache like the optimizer kernel's.
 __device__ __forceinline__ void k11_adam_small_lds(float *__restrict__ lds, const K11Adam &ad, int P, int i,
                                                    float *__restrict__ xyz, float *__restrict__ scaling,
                                                    float *__restrict__ rotation, float *__restrict__ f_dc,
@@ -575,17 +833,13 @@ __device__ __forceinline__ K11In k11_load(size_t i, const float *__restrict__ me
 
 template <int DEG, bool RAW, bool ADAM = false>
 __device__ __forceinline__ void
-preprocess_backward_body(const K11In &in, float (&sp)[14], float (&sg)[14], const int i, const float *__restrict__ rest_in, float *__restrict__ rest_out, int P, int M, const float *__restrict__ means3D, const float *__restrict__ scales,
-                           float scale_modifier, const float *__restrict__ rotations, const float *__restrict__ shs,
-                           const float *__restrict__ shs_rest, const float *__restrict__ opacities_raw,
-                           const float *__restrict__ view, const float *__restrict__ proj,
-                           const float *__restrict__ campos, int W, int H, float tanfovx, float tanfovy,
-                           const int32_t *__restrict__ radii, const float *__restrict__ cov3D,
-                           const uint8_t *__restrict__ clamped, const float *__restrict__ dL_dmeans2D,
-                           const float *__restrict__ dL_dconic_opacity, const float *__restrict__ dL_drgb, int gstride,
-                           float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dscales,
-                           float4 *__restrict__ dL_drotations, float *__restrict__ dL_dshs,
-                           float *__restrict__ dL_dshs_rest, float *__restrict__ dL_dopacities) {
+preprocess_backward_body(const K11In &in, float (&sp)[14], float (&sg)[14], const int i,
+                         const float *__restrict__ rest_in, float *__restrict__ rest_out, int M, float scale_modifier,
+                         const float *__restrict__ shs, const float *__restrict__ view, const float *__restrict__ proj,
+                         const float *__restrict__ campos, int W, int H, float tanfovx, float tanfovy,
+                         float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dscales,
+                         float4 *__restrict__ dL_drotations, float *__restrict__ dL_dshs,
+                         float *__restrict__ dL_dopacities) {
     constexpr int NC = (DEG + 1) * (DEG + 1);
     float *dsh_out = dL_dshs + (size_t)i * M * 3;
 
@@ -628,86 +882,30 @@ preprocess_backward_body(const K11In &in, float (&sp)[14], float (&sg)[14], cons
     const float4 gco = in.gco;
     const float gA = gco.x, gB = gco.y, gC = gco.z;
     if (ADAM) {
-        const float oraw = in.op;
-        const float so = 1.0f / (1.0f + expf(-oraw));
-        sp[13] = oraw;
+        const float so = sigmoidf(in.op);
+        sp[13] = in.op;
         sg[13] = gco.w * so * (1.0f - so);
     } else if (RAW) {
-        const float so = 1.0f / (1.0f + expf(-in.op));
+        const float so = sigmoidf(in.op);
         dL_dopacities[i] = gco.w * so * (1.0f - so);
     } else {
         dL_dopacities[i] = gco.w;
     }
 
     // ---- conic -> cov2D -> (cov3D, t)
-    float t[3];
-    t[0] = cam.v[0] * p[0] + cam.v[4] * p[1] + cam.v[8] * p[2] + cam.v[12];
-    t[1] = cam.v[1] * p[0] + cam.v[5] * p[1] + cam.v[9] * p[2] + cam.v[13];
-    t[2] = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
-    float T[2][3], tc[3];
-    bool xin, yin;
-    compute_T(t, cam.v, fx, fy, tanfovx, tanfovy, T, tc, xin, yin);
-    const float *cv = in.cv;
-    const float S[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
-    float ST0[3], ST1[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        ST0[r] = S[r][0] * T[0][0] + S[r][1] * T[0][1] + S[r][2] * T[0][2];
-        ST1[r] = S[r][0] * T[1][0] + S[r][1] * T[1][1] + S[r][2] * T[1][2];
-    }
-    const float a = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2] + 0.3f;
-    const float b = T[0][0] * ST1[0] + T[0][1] * ST1[1] + T[0][2] * ST1[2];
-    const float c = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2] + 0.3f;
-    const float denom = a * c - b * b;
-    const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-    float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
-    float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (denom2inv != 0.f) {
-        dL_da = denom2inv * (-c * c * gA + b * c * gB + (denom - a * c) * gC);
-        dL_dc = denom2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
-        dL_db = denom2inv * (2.f * b * c * gA - (denom + 2.f * b * b) * gB + 2.f * a * b * gC);
-        dcov[0] = T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc;
-        dcov[3] = T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc;
-        dcov[5] = T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc;
-        dcov[1] = 2.f * T[0][0] * T[0][1] * dL_da + (T[0][0] * T[1][1] + T[0][1] * T[1][0]) * dL_db +
-                  2.f * T[1][0] * T[1][1] * dL_dc;
-        dcov[2] = 2.f * T[0][0] * T[0][2] * dL_da + (T[0][0] * T[1][2] + T[0][2] * T[1][0]) * dL_db +
-                  2.f * T[1][0] * T[1][2] * dL_dc;
-        dcov[4] = 2.f * T[0][2] * T[0][1] * dL_da + (T[0][1] * T[1][2] + T[0][2] * T[1][1]) * dL_db +
-                  2.f * T[1][1] * T[1][2] * dL_dc;
-    }
-    float dT0[3], dT1[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        dT0[k] = 2.f * ST0[k] * dL_da + ST1[k] * dL_db;
-        dT1[k] = 2.f * ST1[k] * dL_dc + ST0[k] * dL_db;
-    }
-    const float dJ00 = dT0[0] * cam.v[0] + dT0[1] * cam.v[4] + dT0[2] * cam.v[8];
-    const float dJ02 = dT0[0] * cam.v[2] + dT0[1] * cam.v[6] + dT0[2] * cam.v[10];
-    const float dJ11 = dT1[0] * cam.v[1] + dT1[1] * cam.v[5] + dT1[2] * cam.v[9];
-    const float dJ12 = dT1[0] * cam.v[2] + dT1[1] * cam.v[6] + dT1[2] * cam.v[10];
-    const float tz = 1.f / tc[2], tz2 = tz * tz, tz3 = tz2 * tz;
-    float dt[3];
-    dt[0] = (xin ? 1.f : 0.f) * (-fx * tz2 * dJ02);
-    dt[1] = (yin ? 1.f : 0.f) * (-fy * tz2 * dJ12);
-    dt[2] = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.f * fx * tc[0]) * tz3 * dJ02 + (2.f * fy * tc[1]) * tz3 * dJ12;
+    float S[3][3];
+    cov3d_unpack(in.cv, S);
+    const Cov2DGrad cg = cov2d_backward(cam.v, fx, fy, tanfovx, tanfovy, p, S, gA, gB, gC);
     float dmean[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++)
-        dmean[k] = cam.v[k * 4 + 0] * dt[0] + cam.v[k * 4 + 1] * dt[1] + cam.v[k * 4 + 2] * dt[2];
+    for (int k = 0; k < 3; k++) dmean[k] = cg.dmean[k];
 
     // ---- means2D (NDC-scaled) -> mean through the perspective divide
     {
-        const float phx = cam.p[0] * p[0] + cam.p[4] * p[1] + cam.p[8] * p[2] + cam.p[12];
-        const float phy = cam.p[1] * p[0] + cam.p[5] * p[1] + cam.p[9] * p[2] + cam.p[13];
-        const float phw = cam.p[3] * p[0] + cam.p[7] * p[1] + cam.p[11] * p[2] + cam.p[15];
-        const float mw = 1.0f / (phw + 0.0000001f);
-        const float mul1 = phx * mw * mw, mul2 = phy * mw * mw;
-        const float2 g2 = in.g2;
+        float dm[3];
+        means2d_to_mean(cam.p, p, in.g2, dm);
 #pragma unroll
-        for (int k = 0; k < 3; k++)
-            dmean[k] += (cam.p[k * 4 + 0] * mw - cam.p[k * 4 + 3] * mul1) * g2.x +
-                        (cam.p[k * 4 + 1] * mw - cam.p[k * 4 + 3] * mul2) * g2.y;
+        for (int k = 0; k < 3; k++) dmean[k] += dm[k];
     }
 
     // ---- colour -> SH coefficients and view direction
@@ -725,66 +923,12 @@ preprocess_backward_body(const K11In &in, float (&sp)[14], float (&sg)[14], cons
 #pragma unroll
             for (int k = 0; k < NC * 3; k++) sh[k] = sp[k];
         }
-        const float dox = p[0] - cam.c[0], doy = p[1] - cam.c[1], doz = p[2] - cam.c[2];
-        const float len = sqrtf(dox * dox + doy * doy + doz * doz);
-        const float x = dox / len, y = doy / len, z = doz / len;
-        float ddir[3] = {0.f, 0.f, 0.f};
-        float dsh[NC * 3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            const float g = in.cl[ch] ? 0.f : in.grgb[ch];
-            float dx = 0.f, dy = 0.f, dz = 0.f;
-            dsh[0 * 3 + ch] = SH_C0 * g;
-            if (DEG > 0) {
-                dsh[1 * 3 + ch] = -SH_C1 * y * g;
-                dsh[2 * 3 + ch] = SH_C1 * z * g;
-                dsh[3 * 3 + ch] = -SH_C1 * x * g;
-                dx = -SH_C1 * sh[3 * 3 + ch];
-                dy = -SH_C1 * sh[1 * 3 + ch];
-                dz = SH_C1 * sh[2 * 3 + ch];
-                if (DEG > 1) {
-                    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                    dsh[4 * 3 + ch] = SH_C2[0] * xy * g;
-                    dsh[5 * 3 + ch] = SH_C2[1] * yz * g;
-                    dsh[6 * 3 + ch] = SH_C2[2] * (2.f * zz - xx - yy) * g;
-                    dsh[7 * 3 + ch] = SH_C2[3] * xz * g;
-                    dsh[8 * 3 + ch] = SH_C2[4] * (xx - yy) * g;
-                    dx += SH_C2[0] * y * sh[4 * 3 + ch] + SH_C2[2] * 2.f * -x * sh[6 * 3 + ch] +
-                          SH_C2[3] * z * sh[7 * 3 + ch] + SH_C2[4] * 2.f * x * sh[8 * 3 + ch];
-                    dy += SH_C2[0] * x * sh[4 * 3 + ch] + SH_C2[1] * z * sh[5 * 3 + ch] +
-                          SH_C2[2] * 2.f * -y * sh[6 * 3 + ch] + SH_C2[4] * 2.f * -y * sh[8 * 3 + ch];
-                    dz += SH_C2[1] * y * sh[5 * 3 + ch] + SH_C2[2] * 2.f * 2.f * z * sh[6 * 3 + ch] +
-                          SH_C2[3] * x * sh[7 * 3 + ch];
-                    if (DEG > 2) {
-                        dsh[9 * 3 + ch] = SH_C3[0] * y * (3.f * xx - yy) * g;
-                        dsh[10 * 3 + ch] = SH_C3[1] * xy * z * g;
-                        dsh[11 * 3 + ch] = SH_C3[2] * y * (4.f * zz - xx - yy) * g;
-                        dsh[12 * 3 + ch] = SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * g;
-                        dsh[13 * 3 + ch] = SH_C3[4] * x * (4.f * zz - xx - yy) * g;
-                        dsh[14 * 3 + ch] = SH_C3[5] * z * (xx - yy) * g;
-                        dsh[15 * 3 + ch] = SH_C3[6] * x * (xx - 3.f * yy) * g;
-                        dx += SH_C3[0] * sh[9 * 3 + ch] * 3.f * 2.f * xy + SH_C3[1] * sh[10 * 3 + ch] * yz +
-                              SH_C3[2] * sh[11 * 3 + ch] * -2.f * xy + SH_C3[3] * sh[12 * 3 + ch] * -3.f * 2.f * xz +
-                              SH_C3[4] * sh[13 * 3 + ch] * (-3.f * xx + 4.f * zz - yy) +
-                              SH_C3[5] * sh[14 * 3 + ch] * 2.f * xz + SH_C3[6] * sh[15 * 3 + ch] * 3.f * (xx - yy);
-                        dy += SH_C3[0] * sh[9 * 3 + ch] * 3.f * (xx - yy) + SH_C3[1] * sh[10 * 3 + ch] * xz +
-                              SH_C3[2] * sh[11 * 3 + ch] * (-3.f * yy + 4.f * zz - xx) +
-                              SH_C3[3] * sh[12 * 3 + ch] * -3.f * 2.f * yz + SH_C3[4] * sh[13 * 3 + ch] * -2.f * xy +
-                              SH_C3[5] * sh[14 * 3 + ch] * -2.f * yz + SH_C3[6] * sh[15 * 3 + ch] * -3.f * 2.f * xy;
-                        dz += SH_C3[1] * sh[10 * 3 + ch] * xy + SH_C3[2] * sh[11 * 3 + ch] * 4.f * 2.f * yz +
-                              SH_C3[3] * sh[12 * 3 + ch] * 3.f * (2.f * zz - xx - yy) +
-                              SH_C3[4] * sh[13 * 3 + ch] * 4.f * 2.f * xz + SH_C3[5] * sh[14 * 3 + ch] * (xx - yy);
-                    }
-                }
-            }
-            ddir[0] += dx * g;
-            ddir[1] += dy * g;
-            ddir[2] += dz * g;
-        }
-        const float dot = x * ddir[0] + y * ddir[1] + z * ddir[2];
-        dmean[0] += (ddir[0] - x * dot) / len;
-        dmean[1] += (ddir[1] - y * dot) / len;
-        dmean[2] += (ddir[2] - z * dot) / len;
+        const float g3[3] = {in.cl[0] ? 0.f : in.grgb[0], in.cl[1] ? 0.f : in.grgb[1], in.cl[2] ? 0.f : in.grgb[2]};
+        float dsh[NC * 3], dm[3];
+        viewdir_backward<DEG>(cam.c, p, ShRegs{sh}, g3, DshAssign{dsh}, dm);
+        dmean[0] += dm[0];
+        dmean[1] += dm[1];
+        dmean[2] += dm[2];
         if (RAW) {
             if (ADAM) {
 #pragma unroll
@@ -823,73 +967,22 @@ preprocess_backward_body(const K11In &in, float (&sp)[14], float (&sg)[14], cons
         dL_dmeans3D[3 * (size_t)i + 2] = dmean[2];
     }
 
-    // ---- cov3D -> scales, rotations.  Sigma = M^T M, M = S R^T
+    // ---- cov3D -> scales, rotations
     {
-        const float4 qraw = in.q;
-        float4 q = qraw;
-        float sc[3] = {in.sc[0], in.sc[1], in.sc[2]};
-        const float scraw[3] = {sc[0], sc[1], sc[2]};
         float gsc[3];
-        float qn = 1.f, qnr = 1.f;
-        if (RAW) {
-            qnr = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-            qn = fmaxf(qnr, 1e-12f);
-            q = make_float4(q.x / qn, q.y / qn, q.z / qn, q.w / qn);
-            sc[0] = expf(sc[0]);
-            sc[1] = expf(sc[1]);
-            sc[2] = expf(sc[2]);
-        }
-        float R[3][3];
-        quat_to_R(q, R);
-        const float s[3] = {scale_modifier * sc[0], scale_modifier * sc[1], scale_modifier * sc[2]};
-        float Mm[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int cc = 0; cc < 3; cc++) Mm[r][cc] = s[r] * R[cc][r];
-        const float dS[3][3] = {{dcov[0], 0.5f * dcov[1], 0.5f * dcov[2]},
-                                {0.5f * dcov[1], dcov[3], 0.5f * dcov[4]},
-                                {0.5f * dcov[2], 0.5f * dcov[4], dcov[5]}};
-        float dM[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int cc = 0; cc < 3; cc++)
-                dM[r][cc] = 2.f * (Mm[r][0] * dS[0][cc] + Mm[r][1] * dS[1][cc] + Mm[r][2] * dS[2][cc]);
-        float dR[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            gsc[r] = (RAW ? sc[r] : 1.f) *  // d exp(x) = exp(x) dx
-                scale_modifier * (R[0][r] * dM[r][0] + R[1][r] * dM[r][1] + R[2][r] * dM[r][2]);
-            if (!ADAM) dL_dscales[3 * (size_t)i + r] = gsc[r];
-#pragma unroll
-            for (int j = 0; j < 3; j++) dR[j][r] = s[r] * dM[r][j];
-        }
+        float4 dq;
+        cov3d_backward<RAW>(in.q, in.sc, scale_modifier, cg.dcov, gsc, dq);
         if (ADAM) {
 #pragma unroll
             for (int e = 0; e < 3; e++) {
-                sp[3 + e] = scraw[e];
+                sp[3 + e] = in.sc[e];
                 sg[3 + e] = gsc[e];
             }
-        }
-        const float r_ = q.x, x = q.y, y = q.z, z = q.w;
-        float4 dq;
-        dq.x = 2.f * (-z * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
-        dq.y = 2.f * (y * dR[0][1] + z * dR[0][2] + y * dR[1][0] - 2.f * x * dR[1][1] - r_ * dR[1][2] + z * dR[2][0] +
-                      r_ * dR[2][1] - 2.f * x * dR[2][2]);
-        dq.z = 2.f * (-2.f * y * dR[0][0] + x * dR[0][1] + r_ * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r_ * dR[2][0] +
-                      z * dR[2][1] - 2.f * y * dR[2][2]);
-        dq.w = 2.f * (-2.f * z * dR[0][0] - r_ * dR[0][1] + x * dR[0][2] + r_ * dR[1][0] - 2.f * z * dR[1][1] +
-                      y * dR[1][2] + x * dR[2][0] + y * dR[2][1]);
-        if (RAW) {  // through q = x / max(|x|, 1e-12)
-            const float dot = qnr > 1e-12f ? (q.x * dq.x + q.y * dq.y + q.z * dq.z + q.w * dq.w) : 0.f;
-            dq = make_float4((dq.x - q.x * dot) / qn, (dq.y - q.y * dot) / qn, (dq.z - q.z * dot) / qn,
-                             (dq.w - q.w * dot) / qn);
-        }
-        if (ADAM) {
-            sp[6] = qraw.x; sp[7] = qraw.y; sp[8] = qraw.z; sp[9] = qraw.w;
+            sp[6] = in.q.x; sp[7] = in.q.y; sp[8] = in.q.z; sp[9] = in.q.w;
             sg[6] = dq.x; sg[7] = dq.y; sg[8] = dq.z; sg[9] = dq.w;
         } else {
+#pragma unroll
+            for (int r = 0; r < 3; r++) dL_dscales[3 * (size_t)i + r] = gsc[r];
             dL_drotations[i] = dq;
         }
     }
@@ -925,12 +1018,10 @@ preprocess_backward_kernel(int P, int M, const float *__restrict__ means3D, cons
             rest_stage_commit(s_rest, st, shs_rest, P);
             __syncthreads();
             if (i < P)
-                preprocess_backward_body<DEG, RAW>(in, ad, ad2, i, s_rest + threadIdx.x * REST_W, s_rest + threadIdx.x * REST_W, P, M,
-                                                   means3D, scales, scale_modifier, rotations, shs, shs_rest,
-                                                   opacities_raw, view, proj, campos, W, H, tanfovx, tanfovy, radii,
-                                                   cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb, gstride,
-                                                   dL_dmeans3D, dL_dscales, dL_drotations, dL_dshs, dL_dshs_rest,
-                                                   dL_dopacities);
+                preprocess_backward_body<DEG, RAW>(in, ad, ad2, i, s_rest + threadIdx.x * REST_W,
+                                                   s_rest + threadIdx.x * REST_W, M, scale_modifier, shs, view, proj,
+                                                   campos, W, H, tanfovx, tanfovy, dL_dmeans3D, dL_dscales,
+                                                   dL_drotations, dL_dshs, dL_dopacities);
             __syncthreads();
             rest_stage_out(s_rest, dL_dshs_rest, P);
             return;
@@ -940,11 +1031,9 @@ preprocess_backward_kernel(int P, int M, const float *__restrict__ means3D, cons
     const K11In in = k11_load<RAW>(ic, means3D, scales, rotations, shs, opacities_raw, radii, cov3D, clamped, dL_dmeans2D,
                                    dL_dconic_opacity, dL_drgb, gstride);
     preprocess_backward_body<DEG, RAW>(in, ad, ad2, i, RAW ? shs_rest + (size_t)i * (M - 1) * 3 : nullptr,
-                                       RAW ? dL_dshs_rest + (size_t)i * (M - 1) * 3 : nullptr, P, M, means3D, scales,
-                                       scale_modifier, rotations, shs, shs_rest, opacities_raw, view, proj, campos, W, H,
-                                       tanfovx, tanfovy, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb,
-                                       gstride, dL_dmeans3D, dL_dscales, dL_drotations, dL_dshs, dL_dshs_rest,
-                                       dL_dopacities);
+                                       RAW ? dL_dshs_rest + (size_t)i * (M - 1) * 3 : nullptr, M, scale_modifier, shs,
+                                       view, proj, campos, W, H, tanfovx, tanfovy, dL_dmeans3D, dL_dscales,
+                                       dL_drotations, dL_dshs, dL_dopacities);
 }
 
 // K11 + Adam, one camera, 16-coefficient model (the launcher checks): the same body with the stores replaced by the
@@ -973,21 +1062,13 @@ preprocess_backward_adam_kernel(int P, float *__restrict__ xyz, float *__restric
     float sp[14], sg[14];
     if (i < P)
         preprocess_backward_body<DEG, true, true>(in, sp, sg, i, s_rest + threadIdx.x * REST_W,
-                                                  s_rest + threadIdx.x * REST_W, P, 16, xyz, scaling, scale_modifier,
-                                                  rotation, f_dc, f_rest, opacity, view, proj, campos, W, H, tanfovx,
-                                                  tanfovy, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity,
-                                                  dL_drgb, gstride, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                  s_rest + threadIdx.x * REST_W, 16, scale_modifier, f_dc, view, proj,
+                                                  campos, W, H, tanfovx, tanfovy, nullptr, nullptr, nullptr, nullptr,
                                                   nullptr);
-#ifdef GSR_K11_SMALL_DIRECT
-    if (i < P) k11_adam_small(ad, i, xyz, scaling, rotation, f_dc, opacity, sp, sg);
-    __syncthreads();
-    rest_adam_out(s_rest, f_rest, ad, P);
-#else
     __syncthreads();
     rest_adam_out(s_rest, f_rest, ad, P);
     __syncthreads();  // the stage is free: the moments of the small tensors go through it
     k11_adam_small_lds(s_rest, ad, P, i, xyz, scaling, rotation, f_dc, opacity, sp, sg);
-#endif
 }
 
 // ------------------------------------------------------------------------- K1 / K11, batched over cameras
@@ -1028,23 +1109,13 @@ preprocess_forward_batched_kernel(int P, int B, int M, const float *__restrict__
     const int gx = (W + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (H + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
     // ---- camera-independent part, once
     const float p[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
-    float4 q = *reinterpret_cast<const float4 *>(rotation + 4 * (size_t)i);
-    const float qn = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f);
-    q = make_float4(q.x / qn, q.y / qn, q.z / qn, q.w / qn);
+    float qnr, qn;
+    const float4 q = quat_normalize(*reinterpret_cast<const float4 *>(rotation + 4 * (size_t)i), qnr, qn);
     const float s[3] = {scale_modifier * expf(scaling[3 * (size_t)i]), scale_modifier * expf(scaling[3 * (size_t)i + 1]),
                         scale_modifier * expf(scaling[3 * (size_t)i + 2])};
-    const float op = 1.0f / (1.0f + expf(-opacity[i]));
-    float R[3][3];
-    quat_to_R(q, R);
-    float L[3][3], S[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) L[a][b] = R[a][b] * s[b];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) S[a][b] = L[a][0] * L[b][0] + L[a][1] * L[b][1] + L[a][2] * L[b][2];
+    const float op = sigmoidf(opacity[i]);
+    float S[3][3];
+    cov3d_from_scale_rot(q, s, S);
     cov3D[6 * (size_t)i + 0] = S[0][0]; cov3D[6 * (size_t)i + 1] = S[0][1]; cov3D[6 * (size_t)i + 2] = S[0][2];
     cov3D[6 * (size_t)i + 3] = S[1][1]; cov3D[6 * (size_t)i + 4] = S[1][2]; cov3D[6 * (size_t)i + 5] = S[2][2];
     float shl[NC * 3];
@@ -1072,53 +1143,16 @@ preprocess_forward_batched_kernel(int P, int B, int M, const float *__restrict__
         float col[3] = {0.f, 0.f, 0.f};
         bool cl[3] = {false, false, false};
         float t[3];
-        t[0] = cam.v[0] * p[0] + cam.v[4] * p[1] + cam.v[8] * p[2] + cam.v[12];
-        t[1] = cam.v[1] * p[0] + cam.v[5] * p[1] + cam.v[9] * p[2] + cam.v[13];
-        t[2] = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
+        view_transform(cam.v, p, t);
         do {
-            if (t[2] <= 0.2f) break;
-            const float phx = cam.p[0] * p[0] + cam.p[4] * p[1] + cam.p[8] * p[2] + cam.p[12];
-            const float phy = cam.p[1] * p[0] + cam.p[5] * p[1] + cam.p[9] * p[2] + cam.p[13];
-            const float phw = cam.p[3] * p[0] + cam.p[7] * p[1] + cam.p[11] * p[2] + cam.p[15];
-            const float pw = 1.0f / (phw + 0.0000001f);
-            const float pprojx = phx * pw, pprojy = phy * pw;
-            float T[2][3], tc[3];
-            bool xin, yin;
-            compute_T(t, cam.v, fx, fy, tanfovx, tanfovy, T, tc, xin, yin);
-            float ST0[3], ST1[3];
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-                ST0[r] = S[r][0] * T[0][0] + S[r][1] * T[0][1] + S[r][2] * T[0][2];
-                ST1[r] = S[r][0] * T[1][0] + S[r][1] * T[1][1] + S[r][2] * T[1][2];
-            }
-            const float a = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2] + 0.3f;
-            const float b = T[0][0] * ST1[0] + T[0][1] * ST1[1] + T[0][2] * ST1[2];
-            const float c = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2] + 0.3f;
-            const float det = a * c - b * b;
-            if (det == 0.0f) break;
-            const float det_inv = 1.f / det;
-            const float mid = 0.5f * (a + c);
-            const float lam = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
-            const int rad = (int)ceilf(3.f * sqrtf(lam));
-            const float px = ((pprojx + 1.0f) * W - 1.0f) * 0.5f;
-            const float py = ((pprojy + 1.0f) * H - 1.0f) * 0.5f;
-            int minx, miny, maxx, maxy;
-            gsr_get_rect(px, py, rad, gx, gy, minx, miny, maxx, maxy);
-            if ((maxx - minx) * (maxy - miny) == 0) break;
-            float d[3] = {p[0] - cam.c[0], p[1] - cam.c[1], p[2] - cam.c[2]};
-            const float inv = 1.0f / sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            d[0] *= inv; d[1] *= inv; d[2] *= inv;
-            eval_sh<DEG>(shl, d[0], d[1], d[2], col);
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                col[k] += 0.5f;
-                cl[k] = col[k] < 0.f;
-                col[k] = fmaxf(col[k], 0.f);
-            }
-            radius = rad;
-            xy = make_float2(px, py);
+            if (t[2] <= 0.2f) break;  // near-plane cull
+            Geom2D g;
+            if (!project_geometry(cam, tanfovx, tanfovy, fx, fy, W, H, gx, gy, p, t, S, g)) break;
+            shade<DEG>(cam.c, p, shl, col, cl);
+            radius = g.rad;
+            xy = g.xy;
             depth = t[2];
-            co = make_float4(c * det_inv, -b * det_inv, a * det_inv, op);
+            co = make_float4(g.conic[0], g.conic[1], g.conic[2], op);
         } while (false);
         const size_t o = (size_t)bc * P + i;
         radii[o] = radius;
@@ -1225,7 +1259,8 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
     }
     float sp[14], sg[14];  // ADAM: the per-lane parameters / gradients, updated after the stage-out (below)
     if (i < P) {
-    const float S[3][3] = {{cvr[0], cvr[1], cvr[2]}, {cvr[1], cvr[3], cvr[4]}, {cvr[2], cvr[4], cvr[5]}};
+    float S[3][3];
+    cov3d_unpack(cvr, S);
     // the SH coefficients above the DC term: read from the LDS stage where they are needed (staged), not held in 45
     // registers across the camera loop next to the 48 accumulators (the kernel needed 270 registers and spilled)
     const float *const shl = s_rest + threadIdx.x * REST_W;  // (an LDS address: ds_read, not a flat load)
@@ -1245,7 +1280,6 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
     for (int k = 0; k < NC * 3; k++) dsh[k] = 0.f;
     float dop = 0.f;
 
-#define SHV(k) (staged ? shl[(k) * 3 + ch - 3] : sh[(k) * 3 + ch])
     // Two loops over the cameras (round 6): the colour part first -- its 48 accumulators and the coefficients it reads
     // from the LDS stage are dead before the geometry part starts, whose covariance chain then has the registers to
     // itself (one loop needed 270 registers and spilled; the sums per camera are unchanged, dmean's order of summation
@@ -1260,69 +1294,14 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
         if (staged) asm volatile("" ::: "memory");  // (keeps the LDS reads of the coefficients inside the loop)
         const float *cp = cams + (size_t)bc * CAM_STRIDE;
         const float camc[3] = {cp[32], cp[33], cp[34]};
-        {
-            const float dox = p[0] - camc[0], doy = p[1] - camc[1], doz = p[2] - camc[2];
-            const float len = sqrtf(dox * dox + doy * doy + doz * doz);
-            const float x = dox / len, y = doy / len, z = doz / len;
-            float ddir[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                const float g = cin.cl[ch] ? 0.f : cin.grgb[ch];
-                float dx = 0.f, dy = 0.f, dz = 0.f;
-                dsh[0 * 3 + ch] += SH_C0 * g;
-                if (DEG > 0) {
-                    dsh[1 * 3 + ch] += -SH_C1 * y * g;
-                    dsh[2 * 3 + ch] += SH_C1 * z * g;
-                    dsh[3 * 3 + ch] += -SH_C1 * x * g;
-                    dx = -SH_C1 * SHV(3);
-                    dy = -SH_C1 * SHV(1);
-                    dz = SH_C1 * SHV(2);
-                    if (DEG > 1) {
-                        const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                        dsh[4 * 3 + ch] += SH_C2[0] * xy * g;
-                        dsh[5 * 3 + ch] += SH_C2[1] * yz * g;
-                        dsh[6 * 3 + ch] += SH_C2[2] * (2.f * zz - xx - yy) * g;
-                        dsh[7 * 3 + ch] += SH_C2[3] * xz * g;
-                        dsh[8 * 3 + ch] += SH_C2[4] * (xx - yy) * g;
-                        dx += SH_C2[0] * y * SHV(4) + SH_C2[2] * 2.f * -x * SHV(6) +
-                              SH_C2[3] * z * SHV(7) + SH_C2[4] * 2.f * x * SHV(8);
-                        dy += SH_C2[0] * x * SHV(4) + SH_C2[1] * z * SHV(5) +
-                              SH_C2[2] * 2.f * -y * SHV(6) + SH_C2[4] * 2.f * -y * SHV(8);
-                        dz += SH_C2[1] * y * SHV(5) + SH_C2[2] * 2.f * 2.f * z * SHV(6) +
-                              SH_C2[3] * x * SHV(7);
-                        if (DEG > 2) {
-                            dsh[9 * 3 + ch] += SH_C3[0] * y * (3.f * xx - yy) * g;
-                            dsh[10 * 3 + ch] += SH_C3[1] * xy * z * g;
-                            dsh[11 * 3 + ch] += SH_C3[2] * y * (4.f * zz - xx - yy) * g;
-                            dsh[12 * 3 + ch] += SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * g;
-                            dsh[13 * 3 + ch] += SH_C3[4] * x * (4.f * zz - xx - yy) * g;
-                            dsh[14 * 3 + ch] += SH_C3[5] * z * (xx - yy) * g;
-                            dsh[15 * 3 + ch] += SH_C3[6] * x * (xx - 3.f * yy) * g;
-                            dx += SH_C3[0] * SHV(9) * 3.f * 2.f * xy + SH_C3[1] * SHV(10) * yz +
-                                  SH_C3[2] * SHV(11) * -2.f * xy + SH_C3[3] * SHV(12) * -3.f * 2.f * xz +
-                                  SH_C3[4] * SHV(13) * (-3.f * xx + 4.f * zz - yy) +
-                                  SH_C3[5] * SHV(14) * 2.f * xz + SH_C3[6] * SHV(15) * 3.f * (xx - yy);
-                            dy += SH_C3[0] * SHV(9) * 3.f * (xx - yy) + SH_C3[1] * SHV(10) * xz +
-                                  SH_C3[2] * SHV(11) * (-3.f * yy + 4.f * zz - xx) +
-                                  SH_C3[3] * SHV(12) * -3.f * 2.f * yz + SH_C3[4] * SHV(13) * -2.f * xy +
-                                  SH_C3[5] * SHV(14) * -2.f * yz + SH_C3[6] * SHV(15) * -3.f * 2.f * xy;
-                            dz += SH_C3[1] * SHV(10) * xy + SH_C3[2] * SHV(11) * 4.f * 2.f * yz +
-                                  SH_C3[3] * SHV(12) * 3.f * (2.f * zz - xx - yy) +
-                                  SH_C3[4] * SHV(13) * 4.f * 2.f * xz + SH_C3[5] * SHV(14) * (xx - yy);
-                        }
-                    }
-                }
-                ddir[0] += dx * g;
-                ddir[1] += dy * g;
-                ddir[2] += dz * g;
-            }
-            const float dot = x * ddir[0] + y * ddir[1] + z * ddir[2];
-            dmean[0] += (ddir[0] - x * dot) / len;
-            dmean[1] += (ddir[1] - y * dot) / len;
-            dmean[2] += (ddir[2] - z * dot) / len;
-        }
+        const float g3[3] = {cin.cl[0] ? 0.f : cin.grgb[0], cin.cl[1] ? 0.f : cin.grgb[1],
+                             cin.cl[2] ? 0.f : cin.grgb[2]};
+        float dm[3];
+        viewdir_backward<DEG>(camc, p, ShStagedOrRegs{staged, shl, sh}, g3, DshAdd{dsh}, dm);
+        dmean[0] += dm[0];
+        dmean[1] += dm[1];
+        dmean[2] += dm[2];
     }
-#undef SHV
     // the colour gradient is complete: DC to the per-lane slots / HBM, the rest over the coefficients in the stage
     if constexpr (ADAM) {
 #pragma unroll
@@ -1356,69 +1335,17 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
         const float4 gco = cin.gco;
         const float gA = gco.x, gB = gco.y, gC = gco.z;
         dop += gco.w;
-        float t[3];
-        t[0] = cam.v[0] * p[0] + cam.v[4] * p[1] + cam.v[8] * p[2] + cam.v[12];
-        t[1] = cam.v[1] * p[0] + cam.v[5] * p[1] + cam.v[9] * p[2] + cam.v[13];
-        t[2] = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
-        float T[2][3], tc[3];
-        bool xin, yin;
-        compute_T(t, cam.v, fx, fy, tanfovx, tanfovy, T, tc, xin, yin);
-        float ST0[3], ST1[3];
+        const Cov2DGrad cg = cov2d_backward(cam.v, fx, fy, tanfovx, tanfovy, p, S, gA, gB, gC);
+        if (cg.live) {
 #pragma unroll
-        for (int r = 0; r < 3; r++) {
-            ST0[r] = S[r][0] * T[0][0] + S[r][1] * T[0][1] + S[r][2] * T[0][2];
-            ST1[r] = S[r][0] * T[1][0] + S[r][1] * T[1][1] + S[r][2] * T[1][2];
+            for (int e = 0; e < 6; e++) dcov[e] += cg.dcov[e];
         }
-        const float a = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2] + 0.3f;
-        const float b = T[0][0] * ST1[0] + T[0][1] * ST1[1] + T[0][2] * ST1[2];
-        const float c = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2] + 0.3f;
-        const float denom = a * c - b * b;
-        const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-        float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
-        if (denom2inv != 0.f) {
-            dL_da = denom2inv * (-c * c * gA + b * c * gB + (denom - a * c) * gC);
-            dL_dc = denom2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
-            dL_db = denom2inv * (2.f * b * c * gA - (denom + 2.f * b * b) * gB + 2.f * a * b * gC);
-            dcov[0] += T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc;
-            dcov[3] += T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc;
-            dcov[5] += T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc;
-            dcov[1] += 2.f * T[0][0] * T[0][1] * dL_da + (T[0][0] * T[1][1] + T[0][1] * T[1][0]) * dL_db +
-                       2.f * T[1][0] * T[1][1] * dL_dc;
-            dcov[2] += 2.f * T[0][0] * T[0][2] * dL_da + (T[0][0] * T[1][2] + T[0][2] * T[1][0]) * dL_db +
-                       2.f * T[1][0] * T[1][2] * dL_dc;
-            dcov[4] += 2.f * T[0][2] * T[0][1] * dL_da + (T[0][1] * T[1][2] + T[0][2] * T[1][1]) * dL_db +
-                       2.f * T[1][1] * T[1][2] * dL_dc;
-        }
-        float dT0[3], dT1[3];
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            dT0[k] = 2.f * ST0[k] * dL_da + ST1[k] * dL_db;
-            dT1[k] = 2.f * ST1[k] * dL_dc + ST0[k] * dL_db;
-        }
-        const float dJ00 = dT0[0] * cam.v[0] + dT0[1] * cam.v[4] + dT0[2] * cam.v[8];
-        const float dJ02 = dT0[0] * cam.v[2] + dT0[1] * cam.v[6] + dT0[2] * cam.v[10];
-        const float dJ11 = dT1[0] * cam.v[1] + dT1[1] * cam.v[5] + dT1[2] * cam.v[9];
-        const float dJ12 = dT1[0] * cam.v[2] + dT1[1] * cam.v[6] + dT1[2] * cam.v[10];
-        const float tz = 1.f / tc[2], tz2 = tz * tz, tz3 = tz2 * tz;
-        float dt[3];
-        dt[0] = (xin ? 1.f : 0.f) * (-fx * tz2 * dJ02);
-        dt[1] = (yin ? 1.f : 0.f) * (-fy * tz2 * dJ12);
-        dt[2] = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.f * fx * tc[0]) * tz3 * dJ02 + (2.f * fy * tc[1]) * tz3 * dJ12;
+        for (int k = 0; k < 3; k++) dmean[k] += cg.dmean[k];
+        float dm[3];
+        means2d_to_mean(cam.p, p, cin.g2, dm);
 #pragma unroll
-        for (int k = 0; k < 3; k++)
-            dmean[k] += cam.v[k * 4 + 0] * dt[0] + cam.v[k * 4 + 1] * dt[1] + cam.v[k * 4 + 2] * dt[2];
-        {
-            const float phx = cam.p[0] * p[0] + cam.p[4] * p[1] + cam.p[8] * p[2] + cam.p[12];
-            const float phy = cam.p[1] * p[0] + cam.p[5] * p[1] + cam.p[9] * p[2] + cam.p[13];
-            const float phw = cam.p[3] * p[0] + cam.p[7] * p[1] + cam.p[11] * p[2] + cam.p[15];
-            const float mw = 1.0f / (phw + 0.0000001f);
-            const float mul1 = phx * mw * mw, mul2 = phy * mw * mw;
-            const float2 g2 = cin.g2;
-#pragma unroll
-            for (int k = 0; k < 3; k++)
-                dmean[k] += (cam.p[k * 4 + 0] * mw - cam.p[k * 4 + 3] * mul1) * g2.x +
-                            (cam.p[k * 4 + 1] * mw - cam.p[k * 4 + 3] * mul2) * g2.y;
-        }
+        for (int k = 0; k < 3; k++) dmean[k] += dm[k];
     }
     // ---- stores + the camera-independent tail (cov3D -> scale / quaternion, activations), once
     if constexpr (ADAM) {
@@ -1433,7 +1360,7 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
         dL_dxyz[3 * (size_t)i + 2] = dmean[2];
     }
     {
-        const float so = 1.0f / (1.0f + expf(-oraw));
+        const float so = sigmoidf(oraw);
         if constexpr (ADAM) {
             sp[13] = oraw;
             sg[13] = dop * so * (1.0f - so);
@@ -1442,59 +1369,20 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
         }
     }
     {
-        const float qnr = sqrtf(qraw.x * qraw.x + qraw.y * qraw.y + qraw.z * qraw.z + qraw.w * qraw.w);
-        const float qn = fmaxf(qnr, 1e-12f);
-        const float4 q = make_float4(qraw.x / qn, qraw.y / qn, qraw.z / qn, qraw.w / qn);
-        const float sc[3] = {expf(scraw[0]), expf(scraw[1]), expf(scraw[2])};
         float gsc[3];
-        float R[3][3];
-        quat_to_R(q, R);
-        const float s[3] = {scale_modifier * sc[0], scale_modifier * sc[1], scale_modifier * sc[2]};
-        float Mm[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int cc = 0; cc < 3; cc++) Mm[r][cc] = s[r] * R[cc][r];
-        const float dS[3][3] = {{dcov[0], 0.5f * dcov[1], 0.5f * dcov[2]},
-                                {0.5f * dcov[1], dcov[3], 0.5f * dcov[4]},
-                                {0.5f * dcov[2], 0.5f * dcov[4], dcov[5]}};
-        float dM[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int cc = 0; cc < 3; cc++)
-                dM[r][cc] = 2.f * (Mm[r][0] * dS[0][cc] + Mm[r][1] * dS[1][cc] + Mm[r][2] * dS[2][cc]);
-        float dR[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            gsc[r] = sc[r] * scale_modifier * (R[0][r] * dM[r][0] + R[1][r] * dM[r][1] + R[2][r] * dM[r][2]);
-            if constexpr (!ADAM) dL_dscaling[3 * (size_t)i + r] = gsc[r];
-#pragma unroll
-            for (int j = 0; j < 3; j++) dR[j][r] = s[r] * dM[r][j];
-        }
+        float4 gq;
+        cov3d_backward<true>(qraw, scraw, scale_modifier, dcov, gsc, gq);
         if constexpr (ADAM) {
 #pragma unroll
             for (int e = 0; e < 3; e++) {
                 sp[3 + e] = scraw[e];
                 sg[3 + e] = gsc[e];
             }
-        }
-        const float r_ = q.x, x = q.y, y = q.z, z = q.w;
-        float4 dq;
-        dq.x = 2.f * (-z * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
-        dq.y = 2.f * (y * dR[0][1] + z * dR[0][2] + y * dR[1][0] - 2.f * x * dR[1][1] - r_ * dR[1][2] + z * dR[2][0] +
-                      r_ * dR[2][1] - 2.f * x * dR[2][2]);
-        dq.z = 2.f * (-2.f * y * dR[0][0] + x * dR[0][1] + r_ * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r_ * dR[2][0] +
-                      z * dR[2][1] - 2.f * y * dR[2][2]);
-        dq.w = 2.f * (-2.f * z * dR[0][0] - r_ * dR[0][1] + x * dR[0][2] + r_ * dR[1][0] - 2.f * z * dR[1][1] +
-                      y * dR[1][2] + x * dR[2][0] + y * dR[2][1]);
-        const float dot = qnr > 1e-12f ? (q.x * dq.x + q.y * dq.y + q.z * dq.z + q.w * dq.w) : 0.f;
-        const float4 gq = make_float4((dq.x - q.x * dot) / qn, (dq.y - q.y * dot) / qn, (dq.z - q.z * dot) / qn,
-                                      (dq.w - q.w * dot) / qn);
-        if constexpr (ADAM) {
             sp[6] = qraw.x; sp[7] = qraw.y; sp[8] = qraw.z; sp[9] = qraw.w;
             sg[6] = gq.x; sg[7] = gq.y; sg[8] = gq.z; sg[9] = gq.w;
         } else {
+#pragma unroll
+            for (int r = 0; r < 3; r++) dL_dscaling[3 * (size_t)i + r] = gsc[r];
             dL_drotation[i] = gq;
         }
     }
@@ -1576,45 +1464,6 @@ constexpr int KC_NS = 27;            // non-trivial sums per camera
 constexpr int KC_RESIDENT = 512;
 constexpr int KC_FIN_SLICES = 32;                 // the finalize adds the partial rows in this many contiguous slices
 
-// d colour / d (unit view direction), contracted with the colour gradient g3: the `ddir` of K11 without its dsh half
-template <int DEG>
-__device__ __forceinline__ void sh_ddir(const float *__restrict__ sh, float x, float y, float z, const float (&g3)[3],
-                                        float (&ddir)[3]) {
-    ddir[0] = ddir[1] = ddir[2] = 0.f;
-    if (DEG == 0) return;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        float dx = -SH_C1 * sh[3 * 3 + ch];
-        float dy = -SH_C1 * sh[1 * 3 + ch];
-        float dz = SH_C1 * sh[2 * 3 + ch];
-        if (DEG > 1) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            dx += SH_C2[0] * y * sh[4 * 3 + ch] + SH_C2[2] * 2.f * -x * sh[6 * 3 + ch] + SH_C2[3] * z * sh[7 * 3 + ch] +
-                  SH_C2[4] * 2.f * x * sh[8 * 3 + ch];
-            dy += SH_C2[0] * x * sh[4 * 3 + ch] + SH_C2[1] * z * sh[5 * 3 + ch] + SH_C2[2] * 2.f * -y * sh[6 * 3 + ch] +
-                  SH_C2[4] * 2.f * -y * sh[8 * 3 + ch];
-            dz += SH_C2[1] * y * sh[5 * 3 + ch] + SH_C2[2] * 2.f * 2.f * z * sh[6 * 3 + ch] +
-                  SH_C2[3] * x * sh[7 * 3 + ch];
-            if (DEG > 2) {
-                dx += SH_C3[0] * sh[9 * 3 + ch] * 3.f * 2.f * xy + SH_C3[1] * sh[10 * 3 + ch] * yz +
-                      SH_C3[2] * sh[11 * 3 + ch] * -2.f * xy + SH_C3[3] * sh[12 * 3 + ch] * -3.f * 2.f * xz +
-                      SH_C3[4] * sh[13 * 3 + ch] * (-3.f * xx + 4.f * zz - yy) + SH_C3[5] * sh[14 * 3 + ch] * 2.f * xz +
-                      SH_C3[6] * sh[15 * 3 + ch] * 3.f * (xx - yy);
-                dy += SH_C3[0] * sh[9 * 3 + ch] * 3.f * (xx - yy) + SH_C3[1] * sh[10 * 3 + ch] * xz +
-                      SH_C3[2] * sh[11 * 3 + ch] * (-3.f * yy + 4.f * zz - xx) +
-                      SH_C3[3] * sh[12 * 3 + ch] * -3.f * 2.f * yz + SH_C3[4] * sh[13 * 3 + ch] * -2.f * xy +
-                      SH_C3[5] * sh[14 * 3 + ch] * -2.f * yz + SH_C3[6] * sh[15 * 3 + ch] * -3.f * 2.f * xy;
-                dz += SH_C3[1] * sh[10 * 3 + ch] * xy + SH_C3[2] * sh[11 * 3 + ch] * 4.f * 2.f * yz +
-                      SH_C3[3] * sh[12 * 3 + ch] * 3.f * (2.f * zz - xx - yy) +
-                      SH_C3[4] * sh[13 * 3 + ch] * 4.f * 2.f * xz + SH_C3[5] * sh[14 * 3 + ch] * (xx - yy);
-            }
-        }
-        ddir[0] += dx * g3[ch];
-        ddir[1] += dy * g3[ch];
-        ddir[2] += dz * g3[ch];
-    }
-}
-
 // one (Gaussian, camera) pair: adds its 27 contributions to acc
 template <int DEG>
 __device__ __forceinline__ void cams_accumulate(float (&acc)[KC_NS], const float *__restrict__ cp, int W, int H,
@@ -1626,83 +1475,39 @@ __device__ __forceinline__ void cams_accumulate(float (&acc)[KC_NS], const float
     const float fx = W / (2.0f * tanfovx), fy = H / (2.0f * tanfovy);
     const float ph[4] = {p[0], p[1], p[2], 1.f};
     // ---- conic -> cov2D -> T = J Wc -> (t, Wc): K11's chain
-    float t[3];
-    t[0] = cam.v[0] * p[0] + cam.v[4] * p[1] + cam.v[8] * p[2] + cam.v[12];
-    t[1] = cam.v[1] * p[0] + cam.v[5] * p[1] + cam.v[9] * p[2] + cam.v[13];
-    t[2] = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
-    float T[2][3], tc[3];
-    bool xin, yin;
-    compute_T(t, cam.v, fx, fy, tanfovx, tanfovy, T, tc, xin, yin);
-    const float S[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
-    float ST0[3], ST1[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        ST0[r] = S[r][0] * T[0][0] + S[r][1] * T[0][1] + S[r][2] * T[0][2];
-        ST1[r] = S[r][0] * T[1][0] + S[r][1] * T[1][1] + S[r][2] * T[1][2];
-    }
-    const float a = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2] + 0.3f;
-    const float b = T[0][0] * ST1[0] + T[0][1] * ST1[1] + T[0][2] * ST1[2];
-    const float c = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2] + 0.3f;
-    const float denom = a * c - b * b;
-    const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-    const float gA = gco.x, gB = gco.y, gC = gco.z;
-    float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
-    if (denom2inv != 0.f) {
-        dL_da = denom2inv * (-c * c * gA + b * c * gB + (denom - a * c) * gC);
-        dL_dc = denom2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
-        dL_db = denom2inv * (2.f * b * c * gA - (denom + 2.f * b * b) * gB + 2.f * a * b * gC);
-    }
-    float dT0[3], dT1[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        dT0[k] = 2.f * ST0[k] * dL_da + ST1[k] * dL_db;
-        dT1[k] = 2.f * ST1[k] * dL_dc + ST0[k] * dL_db;
-    }
-    const float dJ00 = dT0[0] * cam.v[0] + dT0[1] * cam.v[4] + dT0[2] * cam.v[8];
-    const float dJ02 = dT0[0] * cam.v[2] + dT0[1] * cam.v[6] + dT0[2] * cam.v[10];
-    const float dJ11 = dT1[0] * cam.v[1] + dT1[1] * cam.v[5] + dT1[2] * cam.v[9];
-    const float dJ12 = dT1[0] * cam.v[2] + dT1[1] * cam.v[6] + dT1[2] * cam.v[10];
-    const float tz = 1.f / tc[2], tz2 = tz * tz, tz3 = tz2 * tz;
-    float dt[3];
-    dt[0] = (xin ? 1.f : 0.f) * (-fx * tz2 * dJ02);
-    dt[1] = (yin ? 1.f : 0.f) * (-fy * tz2 * dJ12);
-    dt[2] = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.f * fx * tc[0]) * tz3 * dJ02 + (2.f * fy * tc[1]) * tz3 * dJ12;
+    float S[3][3];
+    cov3d_unpack(cv, S);
+    const Cov2DGrad cg = cov2d_backward(cam.v, fx, fy, tanfovx, tanfovy, p, S, gco.x, gco.y, gco.z);
+    const float(&tc)[3] = cg.tc;
 #pragma unroll
     for (int r = 0; r < 4; r++)
 #pragma unroll
-        for (int k = 0; k < 3; k++) acc[r * 3 + k] += ph[r] * dt[k];
+        for (int k = 0; k < 3; k++) acc[r * 3 + k] += ph[r] * cg.dt[k];
     const float J00 = fx / tc[2], J02 = -(fx * tc[0]) / (tc[2] * tc[2]);
     const float J11 = fy / tc[2], J12 = -(fy * tc[1]) / (tc[2] * tc[2]);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        acc[k * 3 + 0] += J00 * dT0[k];
-        acc[k * 3 + 1] += J11 * dT1[k];
-        acc[k * 3 + 2] += J02 * dT0[k] + J12 * dT1[k];
+        acc[k * 3 + 0] += J00 * cg.dT0[k];
+        acc[k * 3 + 1] += J11 * cg.dT1[k];
+        acc[k * 3 + 2] += J02 * cg.dT0[k] + J12 * cg.dT1[k];
     }
     // ---- means2D (NDC-scaled) -> p_hom through the perspective divide
     {
-        const float phx = cam.p[0] * p[0] + cam.p[4] * p[1] + cam.p[8] * p[2] + cam.p[12];
-        const float phy = cam.p[1] * p[0] + cam.p[5] * p[1] + cam.p[9] * p[2] + cam.p[13];
-        const float phw = cam.p[3] * p[0] + cam.p[7] * p[1] + cam.p[11] * p[2] + cam.p[15];
-        const float mw = 1.0f / (phw + 0.0000001f);
-        const float mul1 = phx * mw * mw, mul2 = phy * mw * mw;
+        float mw, mul1, mul2;
+        perspective_backward(cam.p, p, mw, mul1, mul2);
         const float dh[3] = {mw * g2.x, mw * g2.y, -(mul1 * g2.x + mul2 * g2.y)};
 #pragma unroll
         for (int r = 0; r < 4; r++)
 #pragma unroll
             for (int k = 0; k < 3; k++) acc[12 + r * 3 + k] += ph[r] * dh[k];
     }
-    // ---- colour -> view direction -> campos
+    // ---- colour -> view direction -> campos (the coefficient gradients are not wanted here)
     if constexpr (DEG > 0) {
-        const float dox = p[0] - cam.c[0], doy = p[1] - cam.c[1], doz = p[2] - cam.c[2];
-        const float len = sqrtf(dox * dox + doy * doy + doz * doz);
-        const float x = dox / len, y = doy / len, z = doz / len;
-        float ddir[3];
-        sh_ddir<DEG>(sh, x, y, z, g3, ddir);
-        const float dot = x * ddir[0] + y * ddir[1] + z * ddir[2];
-        acc[24] -= (ddir[0] - x * dot) / len;
-        acc[25] -= (ddir[1] - y * dot) / len;
-        acc[26] -= (ddir[2] - z * dot) / len;
+        float dm[3];
+        viewdir_backward<DEG>(cam.c, p, ShRegs{sh}, g3, DshDrop{}, dm);
+        acc[24] -= dm[0];
+        acc[25] -= dm[1];
+        acc[26] -= dm[2];
     }
 }
 
@@ -2022,8 +1827,7 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_dyn(
     if (al & 15) return GSR_EINVAL;  // 16-byte accesses on the moments and the _features_rest block
     ad.grad_scale = grad_scale;
     const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
-    static const bool one_cam_batched = [] { const char *e = getenv("GSR_K11_ONE_BATCHED"); return e && *e == '1'; }();
-    if (B == 1 && tanfov0 && !one_cam_batched) {  // one camera: the leaner kernel without accumulators
+    if (B == 1 && tanfov0) {  // one camera: the leaner kernel without accumulators
         GSR_DISPATCH_DEG(sh_degree,
                          hipLaunchKernelGGL(preprocess_backward_adam_kernel<DEG>, grid, block, 0,
                                             reinterpret_cast<hipStream_t>(stream), P, xyz, scaling, scale_modifier,

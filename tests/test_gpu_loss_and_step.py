@@ -445,7 +445,7 @@ def test_batched_camera_preprocess_equals_per_camera(device, deg):
     for k in range(B):
         assert torch.equal(radii[k], outs_a[k][3])
         assert torch.equal(m2[k], outs_a[k][0]) and torch.equal(depths[k], outs_a[k][4])
-        assert rel_err(rgb[k], outs_a[k][1]) < 1e-6 and rel_err(co[k], outs_a[k][2]) < 1e-6
+        assert torch.equal(rgb[k], outs_a[k][1]) and torch.equal(co[k], outs_a[k][2])  # one copy of the K1 math
     for pa, pb in zip(ra, rb):
         assert rel_err(pb.grad, pa.grad) < 1e-5
 
