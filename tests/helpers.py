@@ -122,3 +122,36 @@ def c_chain_kw(g, kw, bg, mask, wgt):
 
 
 GOLDEN_GRADS = ["d_means2D", "d_means3D", "d_scales", "d_rotations", "d_shs", "d_opacities"]
+
+
+# ---------------------------------------------------------------------------- element-wise check against fp64
+def elem_tolerance(ref64, ref32, K=8):
+    """K * max(max|ref32 - ref64|, 4 * 2^-24 * max|ref64|): the reference's own fp32 error (the same reference code run
+    in float32 on the CPU), never the kernel's, with a floor of four half-ulps of the largest value"""
+    r64, r32 = ref64.detach().double().cpu(), ref32.detach().double().cpu()
+    if r64.numel() == 0:
+        return 0.0
+    e32 = float((r32 - r64).abs().max())
+    floor = 4.0 * 2.0 ** -24 * float(r64.abs().max())
+    return K * max(e32, floor)
+
+
+def assert_elem_close(got, ref64, ref32, K=8, what=""):
+    """every element: |got - ref64| <= K * max(max|ref32 - ref64|, floor) (elem_tolerance); no element is excluded, a
+    NaN fails.  -> the observed ratio max|got - ref64| / max(max|ref32 - ref64|, floor), for the caller's log"""
+    g, r64 = got.detach().double().cpu(), ref64.detach().double().cpu()
+    assert g.shape == r64.shape, f"{what}: shape {tuple(g.shape)} != {tuple(r64.shape)}"
+    if r64.numel() == 0:
+        return 0.0
+    tol = elem_tolerance(ref64, ref32, K)
+    unit = tol / K
+    err = (g - r64).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)
+    worst = int(err.reshape(-1).argmax())
+    ratio = float(err.reshape(-1)[worst]) / unit if unit > 0 else (0.0 if float(err.max()) == 0 else float("inf"))
+    if not ratio <= K:
+        idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), err.shape)) if err.dim() else ()
+        raise AssertionError(f"{what}: element {idx}: got {g.reshape(-1)[worst].item():.9g}, fp64 reference "
+                             f"{r64.reshape(-1)[worst].item():.9g}, error / unit = {ratio:.3g} > K = {K} "
+                             f"(unit = {unit:.3g})")
+    return ratio
