@@ -30,7 +30,7 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "_C", "load_im
            "merge_image_tiles_by_pos", "set_timing_mode", "fused_l1_ssim_band", "fused_band_loss", "fused_activations", "pack_camera",
            "preprocess_gaussians_raw_batched", "knn_mean_dist2", "group_rows", "gather_rows", "densify_plan", "densify_move", "exchange_need",
            "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "densify_stats",
-           "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing"]
+           "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing", "image_metrics", "metrics_from_sums"]
 
 BLOCK_X, BLOCK_Y, ONE_DIM_BLOCK_SIZE = 16, 16, 256
 
@@ -1489,6 +1489,61 @@ def fused_band_loss(image, gt_u8, y0, y1, lambda_dssim, n, band_rows=None):
 
 
 # ------------------------------------------------------------------------- a19: fused activations
+# ------------------------------------------------------------------------------- N1e: evaluation metrics
+METRICS_QUANTIZE, METRICS_NO_SSIM = 1, 2  # include/gsraster.h: GSR_METRICS_*
+
+
+def image_metrics(image, gt_u8, y0=0, y1=None, *, ssim=True, quantize=False, out_u8=None):
+    """-> float64 [C,3] on the device: per channel (sum |x - y|, sum (x - y)^2, sum ssim_map(x, y)) over rows [y0, y1) of
+    the full image [C,H,W] against the full uint8 ground truth [C,H,W]; x = clamp(image, 0, 1) (quantize: the byte a saved
+    PNG holds, / 255), y = gt / 255 (train_internal.py:471-478, utils/image_utils.py:19-21, metrics.py:78-79).  The SSIM
+    window reads up to five rows above and below the band from the same two buffers, so the sums of the bands of a
+    partition add up to the full image's.  ssim=False: the third column is 0 and nothing outside the band is read.
+    out_u8 (uint8 [C, y1-y0, W], optional) receives the quantised band.  Forward only; no host sync."""
+    if not (image.is_cuda and gt_u8.is_cuda and (out_u8 is None or out_u8.is_cuda)):
+        raise RuntimeError("image_metrics: device tensors required (no CPU fallback)")
+    if image.dim() != 3:
+        raise ValueError(f"image must be [C,H,W], got {tuple(image.shape)}")
+    image = image.detach()
+    if image.dtype != torch.float32 or not image.is_contiguous():
+        image = image.float().contiguous()
+    C, H, W = image.shape
+    y1 = H if y1 is None else int(y1)
+    y0 = int(y0)
+    if not 0 <= y0 < y1 <= H:
+        raise ValueError(f"band [{y0}, {y1}) is not inside the {H} rows of the image")
+    if gt_u8.dtype != torch.uint8 or tuple(gt_u8.shape) != (C, H, W):
+        raise ValueError(f"ground truth must be uint8 [{C},{H},{W}], got {gt_u8.dtype} {tuple(gt_u8.shape)}")
+    gt_u8 = gt_u8.contiguous()
+    if out_u8 is not None and (out_u8.dtype != torch.uint8 or tuple(out_u8.shape) != (C, y1 - y0, W)
+                               or not out_u8.is_contiguous()):
+        raise ValueError(f"out_u8 must be a dense uint8 [{C},{y1 - y0},{W}]")
+    dev = image.device
+    flags = (METRICS_QUANTIZE if quantize else 0) | (0 if ssim else METRICS_NO_SSIM)
+    nb = lib.gsr_image_metrics_num_partials(C, y1 - y0, W)
+    partials = torch.empty((nb, 3), dtype=torch.float32, device=dev)
+    sums = torch.empty((C, 3), dtype=torch.float64, device=dev)
+    with _on(dev), kernel_timer.range("image_metrics", Px=(y1 - y0) * W, C=C, ssim=bool(ssim)):
+        s = _stream()
+        check(lib.gsr_image_metrics(C, H, W, _ptr(image), H * W, _ptr(gt_u8), H * W, y0, y1, flags, _ptr(partials),
+                                    _ptr(out_u8), s), "gsr_image_metrics")
+        check(lib.gsr_image_metrics_finalize(C, nb, _ptr(partials), _ptr(sums), s), "gsr_image_metrics_finalize")
+    return sums
+
+
+def metrics_from_sums(sums, H, W):
+    """image_metrics' sums of a WHOLE image (all bands added) [..., C, 3] -> fp64 device scalars (l1, psnr, ssim) [...]:
+    l1 = mean |x - y|, psnr = the mean of the per-channel 20 log10(1 / sqrt(mse_c)) exactly as psnr(image, gt).mean() forms
+    it (utils/image_utils.py:19-21; an exact match gives inf there and here), ssim = the mean of the SSIM map."""
+    sums = sums.double()
+    C = sums.shape[-2]
+    n = float(H) * float(W)
+    l1 = sums[..., 0].sum(-1) / (C * n)
+    psnr = (20.0 * torch.log10(1.0 / torch.sqrt(sums[..., 1] / n))).mean(-1)
+    ssim = sums[..., 2].sum(-1) / (C * n)
+    return l1, psnr, ssim
+
+
 class _FusedActivations(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scaling, rotation, opacity, features_dc, features_rest):

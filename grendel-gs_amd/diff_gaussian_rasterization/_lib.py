@@ -52,6 +52,10 @@ SIGNATURES = {
     "gsr_stamp": (c_int, [c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
     "gsr_band_mask": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gsr_l1_ssim_finalize": (c_int, [c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "gsr_image_metrics_num_partials": (c_int, [c_int, c_int, c_int]),
+    "gsr_image_metrics": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p]),
+    "gsr_image_metrics_finalize": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gsr_exchange_need": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
     "gsr_exchange_chunks": (c_size_t, [c_int]),

@@ -2,7 +2,7 @@
 
 Stand-alone stand-in for the slice of the reference's utils/general_utils.py that the
 `gaussian_renderer` mirror touches (names and meaning identical to utils/general_utils.py:24-113,
-161-169,194-269 there), so that bench.py / tests / smoke run on a box without the reference tree.
+146-158,161-169,194-269 there), so that bench.py / tests / smoke run on a box without the reference tree.
 When the mirror is dropped into the reference tree, `import utils.general_utils` resolves to the
 reference's own module instead and nothing here is used.
 """
@@ -118,6 +118,14 @@ def get_denfify_iter():  # (sic) utils/general_utils.py:116
 def inc_densify_iter():
     global DENSIFY_ITER
     DENSIFY_ITER += 1
+
+
+def check_update_at_this_iter(iteration, bsz, update_interval, update_residual):
+    """does the batch that covers iterations [iteration, iteration + bsz) hold one with
+    it % update_interval == update_residual?  (utils/general_utils.py:146-158: the trigger of everything periodic)"""
+    lo = iteration % update_interval
+    hi = lo + bsz
+    return lo <= update_residual < hi or lo <= update_residual + update_interval < hi
 
 
 def check_initial_gpu_memory_usage(prefix):

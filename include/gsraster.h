@@ -401,6 +401,30 @@ int gsr_l1_ssim_finalize(int num_partials, const float *partials, float c_l1, fl
                          float *out3, gsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N1e  fused evaluation metrics of one row band, forward only -- what training_report prints
+ * (train_internal.py:471-478: clamp both, l1_loss(...).mean(), psnr(...).mean()), the per-channel PSNR of
+ * utils/image_utils.py:19-21, and the SSIM / PSNR metrics.py:78-79 takes of the saved PNGs -- as SUMS over the rows
+ * [y0, y1) of a full [C, height, width] fp32 image against the full uint8 ground truth (row stride = width, channel
+ * strides in elements, >= height * width).  Per element x = clamp(image, 0, 1) -- with GSR_METRICS_QUANTIZE
+ * x = q / 255, q = floor(clamp(x * 255 + 0.5, 0, 255)) formed exactly like mul(255).add_(0.5).clamp_(0, 255).to(uint8) --
+ * and y = gt * (1/255f).  partials [gsr_image_metrics_num_partials(C, y1 - y0, width)][3] = per 32x32 tile
+ * (sum |x-y|, sum (x-y)^2, sum ssim_map); the tiles of a channel are contiguous.  The SSIM window (N1's: 11x11,
+ * sigma 1.5, C1 = 0.01^2, C2 = 0.03^2) reads rows [max(0, y0 - 5), min(height, y1 + 5)) of both buffers: zero padding at
+ * the IMAGE's edges only, so the band sums of a partition add up to the full image's.  GSR_METRICS_NO_SSIM: no window,
+ * no halo rows are read, the third sum is 0.  out_u8 (optional) [C, y1 - y0, width] receives the quantised band q
+ * whether or not the sums use it.  GSR_EINVAL: a null image / gt / partials, y0 < 0, y0 >= y1, y1 > height, an
+ * unknown flag bit, a channel stride below height * width.
+ * finalize: sums [C][3] (double) = each channel's partials added in a fixed order in fp64 (bit-reproducible);
+ * num_partials = the count of the launch that wrote them (a multiple of channels). */
+#define GSR_METRICS_QUANTIZE 1
+#define GSR_METRICS_NO_SSIM 2
+int gsr_image_metrics_num_partials(int channels, int rows, int width);
+int gsr_image_metrics(int channels, int height, int width, const float *image, int64_t image_channel_stride,
+                      const uint8_t *gt, int64_t gt_channel_stride, int y0, int y1, int flags,
+                      float *partials, uint8_t *out_u8, gsr_stream_t stream);
+int gsr_image_metrics_finalize(int channels, int num_partials, const float *partials, double *sums, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N3  fused Adam step for one parameter tensor of n fp32 elements (16-byte aligned, dense):
  * the update stock torch.optim.Adam performs as configured at scene/gaussian_model.py:292
  * (no weight decay, no amsgrad), with the reference's `grad /= bsz` (train_internal.py:319-324)
