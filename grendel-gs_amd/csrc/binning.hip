@@ -1226,30 +1226,6 @@ extern "C" int gsr_bin_speculative_async(int P, int width, int height, const flo
     return 0;
 }
 
-// The same followed by gsr_bin_count_wait.
-// *status = 0: the lists are complete (the count fitted the capacity); 1: the caller must run gsr_bin_sort with buffers for
-// *num_rendered_host pairs (no capacity yet, the count outgrew it, or the persistent prepare kernel repeated itself).
-extern "C" int gsr_bin_speculative(int P, int width, int height, const float *means2D, const float *depths,
-                                   const int32_t *radii, const float *conic_opacity, const uint8_t *compute_locally,
-                                   void *prep, size_t prep_bytes, int64_t capacity, void *scratch, size_t scratch_bytes,
-                                   uint32_t *point_list, int32_t *ranges, int64_t *num_rendered_host, int *status,
-                                   gsr_stream_t stream_) {
-    if (!num_rendered_host || !status) return GSR_EINVAL;
-    *num_rendered_host = 0;
-    *status = 1;
-    uint32_t ticket = 0;
-    int sorted = 0;
-    int rc = gsr_bin_speculative_async(P, width, height, means2D, depths, radii, conic_opacity, compute_locally, prep,
-                                       prep_bytes, capacity, scratch, scratch_bytes, point_list, ranges, &ticket, &sorted,
-                                       stream_);
-    if (rc) return rc;
-    rc = gsr_bin_count_wait(ticket, num_rendered_host, stream_);
-    if (rc == GSR_ERETRY) return 0;  // (count valid, the bounded sort wrote nothing: status 1)
-    if (rc) return rc;
-    if (sorted && *num_rendered_host <= capacity) *status = 0;
-    return 0;
-}
-
 extern "C" size_t gsr_bin_total_offset(int P, int width, int height) {
     if (P < 0 || width <= 0 || height <= 0) return 0;
     return prep_layout(P, width, height).offsets + sizeof(uint32_t) * (size_t)P;  // offsets[P]: K4's total

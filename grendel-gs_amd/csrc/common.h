@@ -155,5 +155,4 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
                                   const uint8_t *compute_locally, const float *bg, const float *final_T,
                                   const int32_t *n_contrib, const float *dL_dpixels, float *dL_record,
                                   const float *out_color, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
-                                  int record_is_zero, hipStream_t stream, double *acc64 = nullptr,
-                                  uint8_t *touched = nullptr);
+                                  int record_is_zero, double *acc64, uint8_t *touched, hipStream_t stream);

@@ -476,14 +476,13 @@ constexpr int MB = 8;      // entries per MFMA batch: rows 0-7 of the 16 x 16 re
 constexpr int MSTR = 66;   // row stride of the (q, w) matrix in 8-byte elements: phase A writes and phase B reads conflict-free
 
 // segment `sidx` of tile `tile`: the list entries [sidx * SEG_LEN, next boundary with a checkpoint or the end)
-template <typename Acc>
 __device__ __forceinline__ void
 composite_backward_segment(const int tile, const int sidx, int W, int H, int gx, const int2 *__restrict__ ranges,
                            const uint32_t *__restrict__ point_list, const float2 *__restrict__ means2D,
                            const float4 *__restrict__ conic_opacity, const float *__restrict__ rgb,
                            const uint8_t *__restrict__ compute_locally, const float *__restrict__ bg,
                            const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
-                           const float *__restrict__ dL_dpixels, Acc *__restrict__ dL_record,
+                           const float *__restrict__ dL_dpixels, double *__restrict__ dL_record,
                            const float *__restrict__ out_color, const SegWs &seg, uint8_t *__restrict__ touched) {
     if (!compute_locally[tile]) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -767,8 +766,8 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
 #ifndef GSR_ABL_NOATOMIC
                 if (val != 0.f) {
                     const uint32_t id = __float_as_uint(sout[10 * e + 9]);
-                    atomicAdd(dL_record + 9 * (size_t)id + col, (Acc)val);
-                    // the rows that received anything (gsr_render_backward_seg_t): every writer stores the same byte
+                    atomicAdd(dL_record + 9 * (size_t)id + col, (double)val);
+                    // the rows that received anything (gsr_render_backward's `touched`): every writer stores the same byte
                     if (touched) touched[id] = 1;
                 }
 #else
@@ -786,14 +785,13 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
     }
 }
 
-template <typename Acc>
 __global__ void __launch_bounds__(256, 4)  // 4 waves per SIMD: <= 128 VGPRs (LDS admits 4 workgroups per CU)
 composite_backward_kernel(int W, int H, int gx, int tiles, const int2 *__restrict__ ranges,
                           const uint32_t *__restrict__ point_list, const float2 *__restrict__ means2D,
                           const float4 *__restrict__ conic_opacity, const float *__restrict__ rgb,
                           const uint8_t *__restrict__ compute_locally, const float *__restrict__ bg,
                           const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
-                          const float *__restrict__ dL_dpixels, Acc *__restrict__ dL_record,
+                          const float *__restrict__ dL_dpixels, double *__restrict__ dL_record,
                           const float *__restrict__ out_color, const SegWs seg, int band_first, int band_tiles,
                           uint8_t *__restrict__ touched) {
     // workgroups [0, nstatic): segment 0 of every tile (of the band, when the caller named it: see K8), XCD-contiguous
@@ -860,6 +858,19 @@ size_t gsr_composite_seg_bytes(int W, int H) {
     return seg_ws_bytes(gx * gy, SEG_CAP);
 }
 
+// The launch geometry of a row band [row_lo, row_hi) of tile rows (include/gsraster.h: 0, 0 = the whole grid; row_lo == -1:
+// `row_hi` tile rows are a CAPACITY, the band is read from the device, see composite_forward_kernel).
+struct BandGrid {
+    bool band;       // the grid covers band_tiles tiles instead of all of them
+    int band_first;  // first tile of the band, -1: device band
+    int band_tiles;
+};
+static BandGrid band_grid_of(int row_lo, int row_hi, int gx, int gy) {
+    const bool dyn = row_lo == -1 && row_hi > 0 && row_hi <= gy;
+    const bool band = dyn || (row_lo >= 0 && row_lo < row_hi && row_hi <= gy && !(row_lo == 0 && row_hi == gy));
+    return {band, dyn ? -1 : band ? row_lo * gx : 0, dyn ? row_hi * gx : band ? (row_hi - row_lo) * gx : 0};
+}
+
 int gsr_launch_composite_forward(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
                                  const float *means2D, const float *conic_opacity, const float *rgb,
                                  const uint8_t *compute_locally, const float *bg, float *out_color, float *final_T,
@@ -872,38 +883,33 @@ int gsr_launch_composite_forward(int P, int W, int H, const int32_t *ranges, con
     if (zero_bytes & 15)
         GSR_HIP(hipMemsetAsync(reinterpret_cast<char *>(zero_ptr) + zero16_n * 16, 0, zero_bytes & 15, stream));
     const int gx = (W + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (H + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    // row_lo == -1: `row_hi` tile rows are a CAPACITY, the band is read from the device (see composite_forward_kernel)
-    const bool dyn = row_lo == -1 && row_hi > 0 && row_hi <= gy;
-    const bool band = dyn || (row_lo >= 0 && row_lo < row_hi && row_hi <= gy && !(row_lo == 0 && row_hi == gy));
-    const int band_first = dyn ? -1 : band ? row_lo * gx : 0;
-    const int band_tiles = dyn ? row_hi * gx : band ? (row_hi - row_lo) * gx : 0;
+    const BandGrid b = band_grid_of(row_lo, row_hi, gx, gy);
     if (seg_ws && seg_bytes < seg_ws_bytes(gx * gy, SEG_CAP)) return GSR_ENOSPACE;
     const SegWs seg = seg_ws_of(seg_ws, gx * gy, SEG_CAP);
     if (seg_ws) GSR_HIP(hipMemsetAsync(seg_ws, 0, 64, stream));  // { segments queued, the backward's ticket }
     auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(band ? band_tiles : gx * gy), dim3(256), 0, stream, W, H, gx,
+        hipLaunchKernelGGL(kern, dim3(b.band ? b.band_tiles : gx * gy), dim3(256), 0, stream, W, H, gx,
                            reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
                            reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, out_color, final_T,
-                           n_contrib, seg, band_first, band_tiles, reinterpret_cast<uint4 *>(zero_ptr), zero16_n);
+                           n_contrib, seg, b.band_first, b.band_tiles, reinterpret_cast<uint4 *>(zero_ptr), zero16_n);
     };
-    if (seg_ws && band) launch(composite_forward_kernel<true, true>);
+    if (seg_ws && b.band) launch(composite_forward_kernel<true, true>);
     else if (seg_ws) launch(composite_forward_kernel<true, false>);
-    else if (band) launch(composite_forward_kernel<false, true>);
+    else if (b.band) launch(composite_forward_kernel<false, true>);
     else launch(composite_forward_kernel<false, false>);
     GSR_LAUNCH_CHECK();
     return 0;
 }
 
-// the fp64 sums of K10 rounded once to the fp32 record (gsr_render_backward_seg_d)
+// the fp64 sums of K10 rounded once to the fp32 record, which is written whole
 __global__ void record_from_f64_kernel(const double *__restrict__ acc, float *__restrict__ rec, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) rec[i] = (float)acc[i];
 }
 
-// the same for the rows K10 touched only (gsr_render_backward_seg_t): lane = row.  K10 set touched[row] wherever it added
-// into the row; the forward's composite kernel left every other row of the record at 0.0f and of the sums at 0.0, which
-// is what the full pass would round them to, so those rows are neither read nor written: P bytes of flags plus 108
-// bytes per touched row.
+// the same for the rows K10 touched only: lane = row.  K10 set touched[row] wherever it added into the row; the
+// forward's composite kernel left every other row of the record at 0.0f and of the sums at 0.0, which is what the full
+// pass would round them to, so those rows are neither read nor written: P bytes of flags plus 108 bytes per touched row.
 __global__ void record_from_f64_touched_kernel(const double *__restrict__ acc, float *__restrict__ rec,
                                                const uint8_t *__restrict__ touched, int P) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -922,49 +928,35 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
                                   const uint8_t *compute_locally, const float *bg, const float *final_T,
                                   const int32_t *n_contrib, const float *dL_dpixels, float *dL_record,
                                   const float *out_color, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
-                                  int record_is_zero, hipStream_t stream, double *acc64, uint8_t *touched) {
-    // (record_is_zero: the forward launch cleared the buffer K10 adds into -- the record, or acc64 when given --
-    // gsr_render_forward_seg_z; acc64: [P,9] fp64 sums, rounded once to the record afterwards, which is written whole;
-    // touched: [P] row flags -- the forward cleared sums, record AND flags, only the rows K10 flags are rounded)
-    if (!record_is_zero || !acc64) touched = nullptr;
+                                  int record_is_zero, double *acc64, uint8_t *touched, hipStream_t stream) {
+    // (acc64: [P,9] fp64 sums K10 adds into, rounded once to the record afterwards; record_is_zero: the forward launch
+    // cleared them; touched: [P] row flags -- the forward cleared sums, record AND flags, only the rows K10 flags are
+    // rounded)
     if (!record_is_zero) {
-        if (acc64) GSR_HIP(hipMemsetAsync(acc64, 0, sizeof(double) * 9 * (size_t)P, stream));
-        else GSR_HIP(hipMemsetAsync(dL_record, 0, sizeof(float) * 9 * (size_t)P, stream));
+        touched = nullptr;
+        GSR_HIP(hipMemsetAsync(acc64, 0, sizeof(double) * 9 * (size_t)P, stream));
     }
     if (P == 0) return 0;
     const int gx = (W + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (H + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    // row_lo == -1: `row_hi` tile rows are a CAPACITY, the band is read from the device (see composite_forward_kernel)
-    const bool dyn = row_lo == -1 && row_hi > 0 && row_hi <= gy;
-    const bool band = dyn || (row_lo >= 0 && row_lo < row_hi && row_hi <= gy && !(row_lo == 0 && row_hi == gy));
-    const int band_first = dyn ? -1 : band ? row_lo * gx : 0;
-    const int band_tiles = dyn ? row_hi * gx : band ? (row_hi - row_lo) * gx : 0;
+    const BandGrid b = band_grid_of(row_lo, row_hi, gx, gy);
     if (seg_ws && (seg_bytes < seg_ws_bytes(gx * gy, SEG_CAP) || !out_color)) return GSR_EINVAL;
     const SegWs seg = seg_ws_of(seg_ws, gx * gy, SEG_CAP);
     // the workers' ticket is reset per launch, so that a second backward over the same forward (retain_graph, gradcheck)
     // walks the queued segments again (rearming it inside the kernel cost K10 its 128-register budget: 196 B of spills,
     // +20 % on every launch; this is a 4-byte fill on the thin-band path only)
     if (seg_ws) GSR_HIP(hipMemsetAsync(reinterpret_cast<char *>(seg_ws) + sizeof(uint32_t), 0, sizeof(uint32_t), stream));
-    const dim3 grid((band ? band_tiles : gx * gy) + (seg_ws ? SEG_WORKERS : 0));
-    if (acc64) {
-        hipLaunchKernelGGL(composite_backward_kernel<double>, grid, dim3(256), 0, stream, W, H, gx, gx * gy,
-                           reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
-                           reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
-                           dL_dpixels, acc64, out_color, seg, band_first, band_tiles, touched);
-        GSR_LAUNCH_CHECK();
-        const size_t n = 9 * (size_t)P;
-        if (touched)
-            hipLaunchKernelGGL(record_from_f64_touched_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream,
-                               acc64, dL_record, touched, P);
-        else
-            hipLaunchKernelGGL(record_from_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, acc64,
-                               dL_record, n);
-    } else {
-        hipLaunchKernelGGL(composite_backward_kernel<float>, grid, dim3(256), 0, stream, W, H, gx, gx * gy,
-                           reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
-                           reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
-                           dL_dpixels, dL_record, out_color, seg, band_first, band_tiles,
-                           static_cast<uint8_t *>(nullptr));
-    }
+    const dim3 grid((b.band ? b.band_tiles : gx * gy) + (seg_ws ? SEG_WORKERS : 0));
+    hipLaunchKernelGGL(composite_backward_kernel, grid, dim3(256), 0, stream, W, H, gx, gx * gy,
+                       reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
+                       reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
+                       dL_dpixels, acc64, out_color, seg, b.band_first, b.band_tiles, touched);
+    GSR_LAUNCH_CHECK();
+    if (touched)
+        hipLaunchKernelGGL(record_from_f64_touched_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream,
+                           acc64, dL_record, touched, P);
+    else
+        hipLaunchKernelGGL(record_from_f64_kernel, dim3((unsigned)((9 * (size_t)P + 255) / 256)), dim3(256), 0, stream,
+                           acc64, dL_record, 9 * (size_t)P);
     GSR_LAUNCH_CHECK();
     return 0;
 }

@@ -802,7 +802,8 @@ _TOUCHED_ROWS = [os.environ.get("GSR_TOUCHED_ROWS", "1") != "0"]  # env: A/B mea
 def set_list_segments(on):
     """True (default): on THIN bands (<= 2048 tiles, named by the caller through cuda_args["_gsr_band"]) the composite
     forward leaves checkpoints every 256 walked list entries and the backward runs the segments in parallel workgroups
-    (gsr_render_*_seg); "always": on every launch; False: one workgroup walks a tile's whole list"""
+    (seg_ws of gsr_render_forward / gsr_render_backward); "always": on every launch; False: one workgroup walks a tile's
+    whole list"""
     _SEGMENTS[0] = "always" if on == "always" else bool(on)
 
 
@@ -1142,7 +1143,8 @@ class _RenderGaussians(torch.autograd.Function):
             # sort -- and the launches are sized for `capacity` tile rows (include/gsraster.h; graphed_step.py)
             band_rows = row_hi if row_lo == -1 else row_hi - row_lo
             thin = 0 < band_rows * gx <= 2048  # at most two rounds of resident workgroups
-            # list segments for the backward (include/gsraster.h: gsr_render_forward_seg) when a backward can follow and
+            # list segments for the backward (include/gsraster.h: seg_ws of gsr_render_forward) when a backward can follow
+            # and
             # the band is THIN: measured (profiles/r04_ab_segments.txt) -9 us net on a 1/8 band, nothing on a whole image
             # (its lists finish in staggered rounds anyway) where the checkpoints only cost the forward 4-9 us
             seg_ws, seg_bytes = None, 0
@@ -1152,9 +1154,10 @@ class _RenderGaussians(torch.autograd.Function):
             lists = [point_list]  # (a list: a late pair count may replace the point_list, see settle below)
             # K10's [P,9] gradient record (means2D 0:2, rgb 2:5, conic_opacity 5:9) and the [P,9] fp64 sums it is rounded
             # from are allocated HERE when a backward can follow; the sums are cleared by K8's own workgroups
-            # (include/gsraster.h: gsr_render_forward_seg_z) instead of by a 72 MB fill launch at the head of the
+            # (include/gsraster.h: zero_ptr of gsr_render_forward) instead of by a 72 MB fill launch at the head of the
             # backward.  With them, in the same buffer, go the record's own rows and one byte per row that K10 sets
-            # where it adds into the row (gsr_render_backward_seg_t): [72 P | 36 P | P, padded to 16] bytes, all cleared
+            # where it adds into the row (gsr_render_backward's `touched`): [72 P | 36 P | P, padded to 16] bytes, all
+            # cleared
             # here, so that the backward rounds only the rows K10 touched and every other row of the record is the 0.0f
             # the forward left
             record = acc64 = touched = None
@@ -1175,11 +1178,10 @@ class _RenderGaussians(torch.autograd.Function):
             def launch_k8(meta_D):
                 with kernel_timer.range("composite_forward", P=P, D=meta_D, **ctx.px_meta) as k8t, \
                         zhx_range(cuda_args, "70 render time"):
-                    check(lib.gsr_render_forward_seg_z(P, W, H, _ptr(ranges), _ptr(lists[0]), _ptr(means2D),
-                                                       _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(out),
-                                                       _ptr(final_T), _ptr(n_contrib), _ptr(seg_ws), seg_bytes, row_lo,
-                                                       row_hi, _ptr(zero_buf), zero_bytes,
-                                                       _stream()), "gsr_render_forward_seg_z")
+                    check(lib.gsr_render_forward(P, W, H, _ptr(ranges), _ptr(lists[0]), _ptr(means2D),
+                                                 _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(out),
+                                                 _ptr(final_T), _ptr(n_contrib), _ptr(seg_ws), seg_bytes, row_lo,
+                                                 row_hi, _ptr(zero_buf), zero_bytes, _stream()), "gsr_render_forward")
                 return k8t
 
             k8t = launch_k8(D)
@@ -1264,11 +1266,11 @@ class _RenderGaussians(torch.autograd.Function):
             with kernel_timer.range("composite_backward", P=P, D=ctx.num_rendered, **ctx.px_meta), \
                     zhx_range(ctx.cuda_args, "b10 render time"):
                 seg_ws, seg_bytes, row_lo, row_hi = ctx.seg
-                check(lib.gsr_render_backward_seg_t(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
-                                                    _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(final_T),
-                                                    _ptr(n_contrib), _ptr(g_out), _ptr(record), _ptr(out_img),
-                                                    _ptr(seg_ws), seg_bytes, row_lo, row_hi, 1 if record_is_zero else 0,
-                                                    _ptr(acc64), _ptr(touched), _stream()), "gsr_render_backward_seg_t")
+                check(lib.gsr_render_backward(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                                              _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(final_T),
+                                              _ptr(n_contrib), _ptr(g_out), _ptr(record), _ptr(out_img),
+                                              _ptr(seg_ws), seg_bytes, row_lo, row_hi, 1 if record_is_zero else 0,
+                                              _ptr(acc64), _ptr(touched), _stream()), "gsr_render_backward")
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("bwd1", id(cap_stats))
             if timing != "off":

@@ -38,8 +38,6 @@ SIGNATURES = {
     "gsr_bin_sort_capacity": (c_int64, [c_int, c_size_t, c_int, c_int]),
     "gsr_bin_sort_bounded": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
                                      c_void_p, c_void_p]),
-    "gsr_render_forward": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_l1_ssim_num_partials": (c_int, [c_int, c_int, c_int]),
     "gsr_l1_ssim_forward": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
@@ -102,9 +100,6 @@ SIGNATURES = {
                                                                                          c_void_p, c_void_p]),
     "gsr_bin_total_offset": (c_size_t, [c_int, c_int, c_int]),
     "gsr_bin_segments_offset": (c_size_t, [c_int, c_int, c_int]),
-    "gsr_bin_speculative": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_size_t, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, ctypes.POINTER(c_int64),
-                                    ctypes.POINTER(c_int), c_void_p]),
     "gsr_bin_speculative_async": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_size_t, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(c_int), c_void_p]),
@@ -115,29 +110,19 @@ SIGNATURES = {
     "gsr_bin_timeline": (c_int, [c_int, c_void_p, c_int, ctypes.POINTER(c_int)]),
     "gsr_flag_if_greater": (c_int, [c_void_p, ctypes.c_uint32, c_void_p, ctypes.c_uint32, c_void_p, c_void_p]),
     "gsr_render_seg_bytes": (c_size_t, [c_int, c_int]),
-    "gsr_render_forward_seg": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
-                                       c_void_p]),
-    "gsr_render_backward_seg": (c_int, [c_int, c_int, c_int] + [c_void_p] * 13 + [c_size_t, c_int, c_int, c_void_p]),
-    "gsr_render_forward_seg_z": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
-                                         c_int, c_void_p, c_size_t, c_void_p]),
-    "gsr_render_backward_seg_z": (c_int, [c_int, c_int, c_int] + [c_void_p] * 13 + [c_size_t, c_int, c_int, c_int,
-                                                                                   c_void_p]),
-    "gsr_render_backward_seg_d": (c_int, [c_int, c_int, c_int] + [c_void_p] * 13 + [c_size_t, c_int, c_int, c_int,
-                                                                                   c_void_p, c_void_p]),
-    "gsr_render_backward_seg_t": (c_int, [c_int, c_int, c_int] + [c_void_p] * 13 + [c_size_t, c_int, c_int, c_int,
-                                                                                   c_void_p, c_void_p, c_void_p]),
+    "gsr_render_forward": (c_int, [c_int, c_int, c_int] + [c_void_p] * 11 + [c_size_t, c_int, c_int, c_void_p, c_size_t,
+                                                                           c_void_p]),
+    "gsr_render_backward": (c_int, [c_int, c_int, c_int] + [c_void_p] * 13 + [c_size_t, c_int, c_int, c_int, c_void_p,
+                                                                            c_void_p, c_void_p]),
     "gsr_composite_walked": (c_int, [ctypes.POINTER(ctypes.c_ulonglong), c_int]),
     "gsr_publish_flag": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p]),
     "gsr_exchange_check": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_uint64, c_int, c_void_p,
                                    ctypes.c_uint32, ctypes.c_uint32, c_void_p, c_void_p]),
     "gsr_activate_forward": (c_int, [c_int, c_int] + [c_void_p] * 10),
     "gsr_activate_backward": (c_int, [c_int, c_int] + [c_void_p] * 13),
-    "gsr_render_backward": (c_int, [c_int, c_int, c_int] + [c_void_p] * 12),
 }
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def _load():

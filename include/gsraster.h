@@ -44,7 +44,7 @@ typedef void *gsr_stream_t;
 
 const char *gsr_error_string(int code);
 
-/* ABI version of this library (bumped on any signature change). */
+/* ABI version of this library (bumped when a signature changes or a symbol is removed; new symbols alone do not). */
 int gsr_abi_version(void);
 
 /* `_C.get_block_XY()` -- arguments/__init__.py:254-257.  Always (16, 16, 256). */
@@ -141,19 +141,15 @@ int gsr_bin_prepare_async(int P, int width, int height, const float *means2D, co
                           uint32_t *ticket, gsr_stream_t stream);
 int gsr_bin_count_wait(uint32_t ticket, int64_t *num_rendered_host, gsr_stream_t stream);
 int64_t gsr_bin_sort_capacity(int P, size_t scratch_bytes, int width, int height);
-/* The three calls above as ONE (ABI 11; one host-side call per view instead of three): prepare, then -- `capacity` > 0 --
- * the bounded sort into (scratch, point_list [capacity]), then the count.  *status = 0: lists and ranges are complete;
- * 1: run gsr_bin_sort with buffers for *num_rendered_host pairs (no capacity given, the count outgrew it, or the
- * persistent prepare kernel had to repeat itself: see gsr_set_bin_persistent). */
-int gsr_bin_speculative(int P, int width, int height, const float *means2D, const float *depths, const int32_t *radii,
-                        const float *conic_opacity, const uint8_t *compute_locally, void *prep, size_t prep_bytes,
-                        int64_t capacity, void *scratch, size_t scratch_bytes, uint32_t *point_list, int32_t *ranges,
-                        int64_t *num_rendered_host, int *status, gsr_stream_t stream);
-/* gsr_bin_speculative without its wait (ABI 12): prepare, then -- `capacity` > 0 -- the bounded sort; *ticket names the pair
- * count for gsr_bin_count_wait, *sorted = 1 when the bounded sort was launched.  The kernels that consume the lists (K8,
- * K10) read the range table, never the count, so the caller launches them FIRST and looks at the count afterwards: had it
- * outgrown the capacity (or gsr_bin_count_wait returned GSR_ERETRY) the bounded sort wrote nothing and left every range
- * empty -- the consumer drew the background -- and the caller repeats gsr_bin_sort + the consumer with exact sizes.
+/* The first two calls above as ONE host-side call per view: prepare, then -- `capacity` > 0 -- the bounded sort into
+ * (scratch, point_list [capacity]); *ticket names the pair count for gsr_bin_count_wait, *sorted = 1 when the bounded
+ * sort was launched.  Lists and ranges are complete when *sorted = 1, gsr_bin_count_wait returns 0 and the count is
+ * <= capacity; otherwise (no capacity given, the count outgrew it, or the persistent prepare kernel had to repeat itself
+ * -- gsr_bin_count_wait returns GSR_ERETRY, see gsr_set_bin_persistent) the caller runs gsr_bin_sort with buffers for the
+ * counted pairs.  The kernels that consume the lists (K8, K10) read the range table, never the count, so the caller
+ * launches them FIRST and looks at the count afterwards: in the incomplete case the bounded sort wrote nothing and left
+ * every range empty -- the consumer drew the background -- and the caller repeats gsr_bin_sort + the consumer with exact
+ * sizes.
  * Stands where the reference's rasterizer reads `num_rendered` back between its sort-key emission and its sort
  * (analyze_statistic.py:1972-1991 stage list: "24 updateDistributedStatLocally.updateTileTouched" -> "50 SortPairs"). */
 int gsr_bin_speculative_async(int P, int width, int height, const float *means2D, const float *depths,
@@ -253,103 +249,77 @@ int gsr_bin_sort_bounded(int P, int width, int height, const uint8_t *compute_lo
  * K8  composite forward -- the rest of render_gaussians (gaussian_renderer/__init__.py:1271-1282).
  * out_color [3,H,W]: sum c*alpha*T + T_final*bg on locally computed tiles, exactly 0 elsewhere
  * (images are assembled by SUM all-reduce, train_internal.py:466-469); final_T [H,W];
- * n_contrib int32 [H,W] (1-based position of the last blended entry of the tile's list). */
-int gsr_render_forward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
-                       const float *means2D, const float *conic_opacity, const float *rgb,
-                       const uint8_t *compute_locally, const float *bg, float *out_color, float *final_T,
-                       int32_t *n_contrib, gsr_stream_t stream);
-
-/* K10 composite backward -- autograd backward of render_gaussians.
+ * n_contrib int32 [H,W] (1-based position of the last blended entry of the tile's list).
+ *
+ * K10 composite backward -- autograd backward of render_gaussians.
  * out (fully overwritten): dL_record [P,9], one row per Gaussian =
  *   [0:2] dL_dmeans2D (pixel gradient x (W/2, H/2)), [2:5] dL_drgb, [5:9] dL_dconic_opacity
  * -- the column order of the exchange's differentiable record (means2D, rgb, conic_opacity:
  * gaussian_renderer/__init__.py:647-650), so that at world size > 1 the record IS the message of the mirror
  * all-to-all.  One record instead of three arrays lets the kernel flush the 9 sums of a (tile, Gaussian) pair
- * from 9 adjacent lanes into one 36-byte row: ~8x fewer memory-side atomic requests. */
+ * from 9 adjacent lanes into one row: ~8x fewer memory-side atomic requests.
+ * acc64 (required): [P,9] doubles, device scratch of the caller.  K10 adds its per-tile contributions into it in fp64
+ * and each sum is rounded once into the record.  fp64 adds still depend on their order, but the fp32 result of a sum of
+ * fp32 terms then differs only in the rare case that the fp64 sum lies within fp64 rounding of an fp32 rounding boundary:
+ * on one GPU the record is reproducible from run to run in practice, where fp32 adds would make it depend on the order the
+ * tiles finish.  (At N > 1 the exchange's gradient scatter still adds in fp32.)
+ *
+ * Optional arguments; each feature is off when its argument is absent.
+ *
+ * seg_ws, seg_bytes -- list SEGMENTS.  One workgroup per tile walks the tile's list serially, so a launch lasts at least
+ *   as long as its longest list takes one wave -- which is the whole kernel on a thin row band (one round of resident
+ *   workgroups at world size 8).  The backward can be cut exactly: per pixel it needs the transmittance and the colour
+ *   accumulated IN FRONT of a list position, which the forward knows when it passes that position.  With a workspace of
+ *   gsr_render_seg_bytes(width, height) bytes (caller-allocated, alive and untouched until the backward has run) the
+ *   forward leaves a checkpoint (T, C.rgb per pixel) every 256 list entries it really walks and queues the segment that
+ *   starts there; the backward, given the same workspace, runs segment 0 of every tile in its usual workgroups and hands
+ *   the queued segments to persistent worker workgroups.  It then needs out_color = the forward's image (the colour
+ *   BEHIND a boundary is the final colour minus the checkpointed one).  Early termination is untouched (segments exist
+ *   only for entries the forward walked); gradients equal the one-segment kernel's up to fp32 rounding (the checkpointed
+ *   T replaces a chain of divisions).  A second backward over one forward walks the same segments again.
+ *   seg_ws == NULL: no segments; seg_bytes is ignored and out_color may be NULL in the backward.
+ *   A workspace that is too small: GSR_ENOSPACE (forward), GSR_EINVAL (backward; also for out_color == NULL).
+ *
+ * row_lo, row_hi -- the TILE ROWS [row_lo, row_hi) of the caller's band when it knows them on the host (Grendel's
+ *   strategies do: compute_locally must then be false outside these rows).  The launches then cover the band's tiles
+ *   only; a grid over all tiles costs a constant ~30 us (forward) / ~60 us (backward) of workgroup dispatch for tiles
+ *   that are not ours, whatever the band.  The forward still leaves every pixel outside the band exactly 0.
+ *   row_lo = row_hi = 0 (or any pair that is not a proper sub-range of the grid's rows): the whole grid.
+ *   row_lo == -1: the band is DEVICE data -- row_hi (1 .. grid rows) is only the CAPACITY of the launch in tile rows,
+ *   the band itself is the row hull of compute_locally that the tile sort left behind the range table (row `tiles` of
+ *   `ranges`, written by gsr_bin_sort / _bounded / gsr_bin_speculative_async on the device).  A band of more rows than
+ *   row_hi is the caller's error: its last rows are not drawn.  One launch captured in a hipGraph then serves every band
+ *   of at most row_hi rows (graphed_step.py: one graph for all cameras of a live partition, workload_division.py:806-849
+ *   of the reference moves the cut points per camera); workgroups above the band's tile count only help clearing the
+ *   pixels outside.
+ *
+ * zero_ptr, zero_bytes (forward) / record_is_zero, touched (backward) -- the backward's clears moved into the forward.
+ *   K10 adds into acc64 with atomics, so the sums start at zero.  record_is_zero == 0: the backward clears acc64 itself
+ *   with a fill at its head (72 MB per 10^6 Gaussians) and rounds every row into the record.  Instead the forward can
+ *   clear [zero_ptr, zero_ptr + zero_bytes) -- 16-byte aligned, a multiple of 4 bytes, else GSR_EINVAL -- from the
+ *   composite kernel's own workgroups (the kernel is bound by VALU issue, its memory pipes are idle); zero_bytes == 0:
+ *   nothing is cleared.  The caller passes acc64 there (72 P bytes) and record_is_zero = 1 to the backward, which then
+ *   skips its fill.  Nothing else may write the cleared buffers in between.
+ *   touched: [P] bytes.  K10 sets touched[row] = 1 wherever it adds into a row of acc64, and only those rows are rounded
+ *   into the record (K10 reaches about a tenth of the rows of a 10^6-Gaussian scene; the full pass reads 72 and writes
+ *   36 bytes for every row).  For that the FORWARD must have cleared the sums, the record and the flags: the caller lays
+ *   them out as one buffer, [72 P | 36 P | P, padded to 16] bytes = acc64, record, touched, and passes all of it as
+ *   (zero_ptr, zero_bytes); record_is_zero = 1 says so.  The record is then complete when the call returns, bit for bit
+ *   what the full pass writes.  touched == NULL or record_is_zero == 0: the full rounding pass.
+ *
+ * gsr_render_backward with P == 0 returns 0 and touches nothing. */
+size_t gsr_render_seg_bytes(int width, int height);
+int gsr_render_forward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                       const float *means2D, const float *conic_opacity, const float *rgb,
+                       const uint8_t *compute_locally, const float *bg, float *out_color, float *final_T,
+                       int32_t *n_contrib, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, void *zero_ptr,
+                       size_t zero_bytes, gsr_stream_t stream);
 int gsr_render_backward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
                         const float *means2D, const float *conic_opacity, const float *rgb,
                         const uint8_t *compute_locally, const float *bg, const float *final_T,
-                        const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, gsr_stream_t stream);
-/* K8 / K10 with list SEGMENTS (round 4).  One workgroup per tile walks the tile's list serially, so a launch lasts at
- * least as long as its longest list takes one wave -- which is the whole kernel on a thin row band (one round of
- * resident workgroups at world size 8).  The backward can be cut exactly: per pixel it needs the transmittance and the
- * colour accumulated IN FRONT of a list position, which the forward knows when it passes that position.  With a
- * workspace (gsr_render_seg_bytes(width, height) bytes, caller-allocated, alive until the backward has run)
- *   gsr_render_forward_seg  leaves a checkpoint (T, C.rgb per pixel) every 256 list entries it really walks and queues
- *                           the segment that starts there;
- *   gsr_render_backward_seg runs segment 0 of every tile in its usual workgroups and hands the queued segments to
- *                           persistent worker workgroups.  out_color = the forward's image (the colour BEHIND a
- *                           boundary is the final colour minus the checkpointed one).
- * Early termination is untouched (segments exist only for entries the forward walked); gradients equal the one-segment
- * kernel's up to fp32 rounding (the checkpointed T replaces a chain of divisions).  seg_ws == NULL: exactly
- * gsr_render_forward / gsr_render_backward.  Same call sites as those (gaussian_renderer/__init__.py:1271-1282).
- * [row_lo, row_hi): the TILE ROWS of the caller's band when it knows them on the host (Grendel's strategies do:
- * compute_locally must then be false outside these rows), else 0, 0.  The launches then cover the band's tiles only; a
- * grid over all tiles costs a constant ~30 us (forward) / ~60 us (backward) of workgroup dispatch for tiles that are not
- * ours, whatever the band.  The forward still leaves every pixel outside the band exactly 0.
- * row_lo == -1 (ABI 13): the band is DEVICE data -- row_hi (1 .. grid rows) is only the CAPACITY of the launch in tile
- * rows, the band itself is the row hull of compute_locally that the tile sort left behind the range table (row `tiles`
- * of `ranges`, written by gsr_bin_sort / _bounded / _speculative* on the device; a band of more rows than row_hi is the
- * caller's error: its last rows are not drawn).  One launch captured in a hipGraph then serves every band of at most
- * row_hi rows (graphed_step.py: one graph for all cameras of a live partition, workload_division.py:806-849 of the
- * reference moves the cut points per camera); workgroups above the band's tile count only help clearing the pixels
- * outside. */
-size_t gsr_render_seg_bytes(int width, int height);
-int gsr_render_forward_seg(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
-                           const float *means2D, const float *conic_opacity, const float *rgb,
-                           const uint8_t *compute_locally, const float *bg, float *out_color, float *final_T,
-                           int32_t *n_contrib, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
-                           gsr_stream_t stream);
-int gsr_render_backward_seg(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
-                            const float *means2D, const float *conic_opacity, const float *rgb,
-                            const uint8_t *compute_locally, const float *bg, const float *final_T,
-                            const int32_t *n_contrib, const float *dL_dpixels, float *dL_record,
-                            const float *out_color, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
-                            gsr_stream_t stream);
-/* The same pair with the backward's fill moved into the forward (ABI 12).  K10 adds into the [P,9] record with atomics,
- * so the record starts at zero: gsr_render_backward[_seg] clears it with a fill launch at the head of every backward
- * (36 MB per 10^6 Gaussians).  gsr_render_forward_seg_z additionally clears [zero_ptr, zero_ptr + zero_bytes) -- 16-byte
- * aligned, a multiple of 4 bytes; the caller passes the record it will hand to the backward -- from the composite
- * kernel's own workgroups (the kernel is bound by VALU issue, its memory pipes are idle), and
- * gsr_render_backward_seg_z(record_is_zero = 1) skips the fill.  Nothing else may write the record in between. */
-int gsr_render_forward_seg_z(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
-                             const float *means2D, const float *conic_opacity, const float *rgb,
-                             const uint8_t *compute_locally, const float *bg, float *out_color, float *final_T,
-                             int32_t *n_contrib, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, void *zero_ptr,
-                             size_t zero_bytes, gsr_stream_t stream);
-int gsr_render_backward_seg_z(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
-                              const float *means2D, const float *conic_opacity, const float *rgb,
-                              const uint8_t *compute_locally, const float *bg, const float *final_T,
-                              const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
-                              void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero,
-                              gsr_stream_t stream);
-/* gsr_render_backward_seg_d (ABI 14; the training backward): the same, with K10's per-tile contributions added in fp64
- * into `acc64` ([P,9] doubles, device scratch of the caller) and each sum rounded once into the record, which is
- * written whole.  record_is_zero = 1: the forward cleared acc64 (pass it as zero_ptr, 72 * P bytes), else it is cleared
- * here.  fp64 adds still depend on their order, but the fp32 result of a sum of fp32 terms then differs only in the
- * rare case that the fp64 sum lies within fp64 rounding of an fp32 rounding boundary: on one GPU the record is
- * reproducible from run to run in practice, where fp32 adds made it depend on the order the tiles finished.  (At N > 1
- * the exchange's gradient scatter still adds in fp32.) */
-int gsr_render_backward_seg_d(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
-                              const float *means2D, const float *conic_opacity, const float *rgb,
-                              const uint8_t *compute_locally, const float *bg, const float *final_T,
-                              const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
-                              void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero,
-                              double *acc64, gsr_stream_t stream);
-/* gsr_render_backward_seg_t (the training backward; a new symbol, the ABI version stays): gsr_render_backward_seg_d plus
- * `touched`, [P] bytes.  K10 sets touched[row] = 1 wherever it adds into a row of acc64, and only those rows are rounded
- * into the record (K10 reaches about a tenth of the rows of a 10^6-Gaussian scene; the full pass reads 72 and writes
- * 36 bytes for every row).  For that the FORWARD must have cleared the sums, the record and the flags: the caller lays
- * them out as one buffer, [72 P | 36 P | P, padded to 16] bytes = acc64, record, touched, and passes all of it as
- * (zero_ptr, zero_bytes) of gsr_render_forward_seg_z; record_is_zero = 1 says so.  The record is then complete when the
- * call returns, exactly as after gsr_render_backward_seg_d, bit for bit.  touched == NULL or record_is_zero == 0:
- * gsr_render_backward_seg_d itself (the full pass). */
-int gsr_render_backward_seg_t(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
-                              const float *means2D, const float *conic_opacity, const float *rgb,
-                              const uint8_t *compute_locally, const float *bg, const float *final_T,
-                              const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
-                              void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero,
-                              double *acc64, uint8_t *touched, gsr_stream_t stream);
+                        const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
+                        void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero, double *acc64,
+                        uint8_t *touched, gsr_stream_t stream);
 /* Measurement aid (bench.py's roofline leg; the reference has nothing to bind here): list entries the composite kernels
  * WALKED since the last reset, summed over launches -- out2[0] K8, out2[1] K10; per tile the entries its longest-walking
  * quadrant goes through (K8: up to the chunk in which the last pixel saturates; K10: the largest n_contrib of the

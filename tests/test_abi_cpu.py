@@ -25,6 +25,11 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(raw, n), f"{n} declared in include/gsraster.h but not exported"
     assert sorted(_lib.SIGNATURES) == names, "ctypes table and header disagree"
+    # ABI 15 folded the composite variants into gsr_render_forward / gsr_render_backward and retired the synchronous
+    # gsr_bin_speculative: no wrapper of theirs may survive in the library
+    for n in ("gsr_render_forward_seg", "gsr_render_forward_seg_z", "gsr_render_backward_seg", "gsr_render_backward_seg_z",
+              "gsr_render_backward_seg_d", "gsr_render_backward_seg_t", "gsr_bin_speculative"):
+        assert not hasattr(raw, n), f"{n} was retired but is still exported"
 
 
 def test_pure_host_entry_points():
@@ -62,12 +67,24 @@ def test_pure_host_entry_points():
     assert lib.gsr_densify_stats(10, None, None, 1, None, None, None, None) == -1  # a row holds at least (x, y)
     assert lib.gsr_densify_stats(0, None, None, 9, None, None, None, None) == 0
     # ABI 13 (row bands as device data): a launch without its band words, or without a capacity, is refused
-    assert lib.gsr_abi_version() == 14
+    assert lib.gsr_abi_version() == 15
     assert lib.gsr_l1_ssim_forward_band(3, 64, 64, None, 0, None, None, None, None, None, None, None) == -1
     assert lib.gsr_l1_ssim_backward_band(3, 0, 64, None, 0, None, None, None, None, None, None, 1.0, 1.0, None, 0, None,
                                          None) == -1
     assert lib.gsr_band_mask(40, 23, 1, None, 4, None, None) == -1
     assert lib.gsr_band_mask(40, 23, 0, None, 4, None, None) == -1
+    # K8 / K10 (ABI 15: one entry point each).  Dummy non-zero integers stand for device pointers: every call below is
+    # refused, or returns, before anything is dereferenced or launched
+    d = 0x1000  # 16-byte aligned
+    assert lib.gsr_render_forward(1, 0, 16, *([d] * 10), None, 0, 0, 0, None, 0, None) == -1  # width 0
+    assert lib.gsr_render_forward(1, 16, 16, None, *([d] * 9), None, 0, 0, 0, None, 0, None) == -1  # no ranges
+    assert lib.gsr_render_backward(0, 16, 16, *([None] * 13), 0, 0, 0, 0, None, None, None) == 0  # nothing to do
+    # the fp64 sums are required: every pointer but acc64
+    assert lib.gsr_render_backward(1, 16, 16, *([d] * 13), 0, 0, 0, 0, None, d, None) == -1
+    # the range the forward clears is 16-byte aligned and a multiple of 4 bytes
+    assert lib.gsr_render_forward(1, 16, 16, *([d] * 11), 1 << 30, 0, 0, d + 4, 20, None) == -1
+    assert lib.gsr_render_forward(1, 16, 16, *([d] * 10), None, 0, 0, 0, d, 18, None) == -1
+    assert lib.gsr_render_forward(1, 16, 16, *([d] * 10), None, 0, 0, 0, None, 16, None) == -1
     rc = dgr._lib.lib.gsr_preprocess_forward(-1, 3, 16, *([None] * 2), 1.0, *([None] * 6), 10, 10, 1.0, 1.0,
                                              *([None] * 8))
     assert rc == -1

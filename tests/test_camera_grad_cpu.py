@@ -25,7 +25,7 @@ def test_symbols_are_declared_exported_and_bound():
         assert hasattr(raw, n), f"{n} is not exported"
         assert n in _l.SIGNATURES
     assert len(_l.SIGNATURES["gsr_preprocess_backward_cams"][1]) == 23
-    assert _l.lib.gsr_abi_version() == 14 == _l.ABI_VERSION  # two new symbols, no version bump (gsr_densify_* precedent)
+    assert _l.lib.gsr_abi_version() == 15 == _l.ABI_VERSION  # two new symbols, no version bump (gsr_densify_* precedent)
 
 
 def test_workspace_size_is_positive_and_monotone():

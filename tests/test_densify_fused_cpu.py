@@ -61,7 +61,7 @@ def test_entry_points_validate_before_any_device_work():
     assert move(roles=(2, 1), samples=None) == -1
     assert move(roles=(3, 1), alts=VP(None, 64)) == -1
     assert move(roles=(3, 1), alts=None) == -1
-    assert lib.gsr_abi_version() == 14          # new symbols only
+    assert lib.gsr_abi_version() == 15          # new symbols only
 
 
 def _cpu_model(n, seed, world):

@@ -1,8 +1,8 @@
-"""-m gpu: the composite backward rounds only the rows K10 touched (include/gsraster.h: gsr_render_backward_seg_t).
+"""-m gpu: the composite backward rounds only the rows K10 touched (include/gsraster.h: `touched` of gsr_render_backward).
 
 K10 adds into [P,9] fp64 sums and flags the rows it adds into; the rounding pass then visits the flagged rows only and
 every other row of the fp32 record keeps the 0.0f the forward's composite kernel left there.  The full pass
-(gsr_render_backward_seg_d: every row read and rounded) is the reference: the fp64 sums make both deterministic, so the
+(touched = NULL or record_is_zero = 0: every row read and rounded) is the reference: the fp64 sums make both deterministic, so the
 two records are compared BIT FOR BIT, through the operator, on shapes that reach the edge paths of both kernels --
 images that are no multiple of the 16-pixel tile or the 8-pixel quadrant (clamped loads of the MFMA operand at the right
 and bottom edges), a single tile, P = 1 / 7 / 1000 (odd P: the forward's clear ends in a tail of < 16 bytes), nothing

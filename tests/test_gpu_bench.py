@@ -1,5 +1,5 @@
 """bench.py end to end on a small scene: a plain run times exactly --steps steps and nothing else, and two runs with the
-same arguments write the same outputs (the training backward rounds fp64 sums, gsr_render_backward_seg_d)."""
+same arguments write the same outputs (the training backward rounds fp64 sums, gsr_render_backward's acc64)."""
 import json
 import os
 import subprocess

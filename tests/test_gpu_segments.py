@@ -1,5 +1,5 @@
-"""List segments in the composite backward (include/gsraster.h: gsr_render_forward_seg / gsr_render_backward_seg): K8 leaves
-a checkpoint every 256 list entries it really walks, K10 runs the segments of a tile in parallel workgroups starting
+"""List segments in the composite backward (include/gsraster.h: seg_ws of gsr_render_forward / gsr_render_backward): K8
+leaves a checkpoint every 256 list entries it really walks, K10 runs the segments of a tile in parallel workgroups starting
 from the checkpointed transmittance / colour.  The forward's arithmetic is untouched (image bitwise equal with and
 without the workspace); the gradients equal the one-segment kernel's up to fp32 rounding and the C oracle's within the
 usual 1e-4; a queue that overflows (more boundaries than checkpoint slots) only leaves long tails unsplit."""

@@ -75,7 +75,7 @@ def run(W):
     utils.DEFAULT_GROUP = utils.IN_NODE_GROUP = F.FakeGroup(W, rank) if W > 1 else utils.SingleGPUGroup()
 
     # run the workload for a few steps, then look at the LAST K10 launch: reset the buffer before every backward
-    orig = lib.gsr_render_backward_seg
+    orig = lib.gsr_render_backward
     n = ctypes.c_uint(0)
 
     def spy(*args):
@@ -83,7 +83,7 @@ def run(W):
         fn(None, ctypes.byref(n), 1)
         return orig(*args)
 
-    lib.gsr_render_backward_seg = spy
+    lib.gsr_render_backward = spy
     bench.run_workload(a, "c2", W, rank if W > 1 else 0, dev, 4, 2, 1, 0, single_view=(W == 1), collect_kernels=False)
     torch.cuda.synchronize()
     buf = (ctypes.c_ulonglong * (4 * (1 << 16)))()
