@@ -1438,6 +1438,287 @@ preprocess_backward_adam_batched_kernel(int P, int B, float *__restrict__ xyz, f
                                                 ad);
 }
 
+// ------------------------------------------------------------------- sparse (lazy) K11 + Adam
+// gsr_preprocess_backward_adam_raw_batched_sparse: the fused update for the rows that received a gradient, nothing for
+// the others (include/gsraster.h has the definition of "active").  Three launches on one stream, no host read-back:
+//   reset     one lane: the workspace's counter = 0
+//   classify  one pass over radii [B,P] and the gradient rows of the visible (camera, row) pairs -> active_out, and the
+//             compacted list of active rows: ballots per wave, ONE atomic per workgroup of SA_CROWS rows to claim slots
+//             (the list is ascending inside a workgroup's slots; the workgroups' order is the atomics')
+//   update    a grid of fixed size, ceil(P / K11_BLOCK) workgroups; workgroup c takes list[c * K11_BLOCK ...] and leaves
+//             at once when that is past the count it reads from the workspace.  One lane per active row: the row's
+//             arithmetic is preprocess_backward_batched_body's (the same device functions in the same order, so the
+//             same bits), its _features_rest row and the three arrays' 180 bytes per row move through the LDS stage --
+//             lane e of the workgroup's 45 x K11_BLOCK words reads word e % 45 of row list[e / 45]: consecutive lanes
+//             read consecutive words of a 180-byte row.
+// Bytes: 4 B (+ 36 B where visible) per row and camera for the classification, + 4 B per row for active_out; per ACTIVE row
+// 4 (list) + 56 + 24 (parameters, cov3D) + B * 43 (radius, record row, clamp flags) + 180 (SH) read, 236 parameters
+// written, 2 * 236 moments read and written: 236 * 6 + 84 + 43 B.
+constexpr int SA_CBLOCK = 256;          // lanes of a classify workgroup ...
+constexpr int SA_CPER = 4;              // ... and rows per lane: one slot-claiming atomic per 1024 rows
+constexpr int SA_CROWS = SA_CBLOCK * SA_CPER;
+struct SparseWs {  // head of the caller's workspace; the list of active rows follows
+    uint32_t count, pad[3];
+};
+
+__device__ __forceinline__ bool sa_nonzero(float x) {  // != 0.0f on the bits: -0.0 is zero, a denormal and a NaN are not
+    return (__float_as_uint(x) & 0x7fffffffu) != 0u;
+}
+
+__global__ void sparse_adam_reset_kernel(const uint32_t *__restrict__ skip, SparseWs *__restrict__ ws) {
+    if (skip && *skip) return;
+    ws->count = 0u;
+}
+
+__global__ void __launch_bounds__(SA_CBLOCK)
+sparse_adam_classify_kernel(int P, int B, const int32_t *__restrict__ radii, const float *__restrict__ dL_dmeans2D,
+                            const float *__restrict__ dL_dconic_opacity, const float *__restrict__ dL_drgb, int gstride,
+                            const uint32_t *__restrict__ skip, SparseWs *__restrict__ ws, uint32_t *__restrict__ list,
+                            uint8_t *__restrict__ active_out) {
+    if (skip && *skip) return;
+    constexpr int NW = SA_CBLOCK / GSR_WAVE;
+    __shared__ uint32_t s_cnt[SA_CPER * NW];
+    __shared__ uint32_t s_base;
+    const size_t row0 = (size_t)blockIdx.x * SA_CROWS;
+    const int wave = threadIdx.x / GSR_WAVE;
+    bool act[SA_CPER];
+    uint32_t rank[SA_CPER];
+#pragma unroll
+    for (int j = 0; j < SA_CPER; j++) {
+        const size_t i = row0 + (size_t)j * SA_CBLOCK + threadIdx.x;
+        bool a = false;
+        if (i < (size_t)P) {
+            for (int bc = 0; bc < B; bc++) {
+                const size_t o = (size_t)bc * P + i;
+                if (radii[o] <= 0) continue;  // the gradient words of a culled pair are not even read
+                const float2 g2 = grad_ld2(dL_dmeans2D, o, gstride);
+                const float4 gco = grad_ld4(dL_dconic_opacity, o, gstride);
+                const float *gr = dL_drgb + (size_t)(gstride ? gstride : 3) * o;
+                a = a || sa_nonzero(g2.x) || sa_nonzero(g2.y) || sa_nonzero(gr[0]) || sa_nonzero(gr[1]) ||
+                    sa_nonzero(gr[2]) || sa_nonzero(gco.x) || sa_nonzero(gco.y) || sa_nonzero(gco.z) ||
+                    sa_nonzero(gco.w);
+            }
+            if (active_out) active_out[i] = a ? 1 : 0;
+        }
+        const unsigned long long bal = __ballot(a);
+        act[j] = a;
+        rank[j] = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if ((threadIdx.x & (GSR_WAVE - 1)) == 0) s_cnt[j * NW + wave] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {  // exclusive scan of the 16 counts, in the order of the rows; one atomic for the workgroup
+        uint32_t run = 0;
+        for (int k = 0; k < SA_CPER * NW; k++) {
+            const uint32_t c = s_cnt[k];
+            s_cnt[k] = run;
+            run += c;
+        }
+        s_base = run ? atomicAdd(&ws->count, run) : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < SA_CPER; j++)
+        if (act[j])  // (slot < P: every row is counted at most once)
+            list[s_base + s_cnt[j * NW + wave] + rank[j]] = (uint32_t)(row0 + (size_t)j * SA_CBLOCK + threadIdx.x);
+}
+
+// word e of the workgroup's K11_BLOCK x 45 stage -> its offset in a [P, 45] array, through the row list in LDS
+__device__ __forceinline__ size_t sa_rest_offset(const uint32_t *__restrict__ s_rows, int e) {
+    const int r = e / REST_W;
+    return (size_t)s_rows[r] * REST_W + (size_t)(e - r * REST_W);
+}
+
+template <int DEG>
+__global__ void __launch_bounds__(K11_BLOCK, K11B_WAVES_PER_EU)
+sparse_adam_update_kernel(int P, int B, float *__restrict__ xyz, float *__restrict__ scaling, float scale_modifier,
+                          float *__restrict__ rotation, float *__restrict__ f_dc, float *__restrict__ f_rest,
+                          float *__restrict__ opacity, const float *__restrict__ cams, int W, int H,
+                          const int32_t *__restrict__ radii, const float *__restrict__ cov3D,
+                          const uint8_t *__restrict__ clamped, const float *__restrict__ dL_dmeans2D,
+                          const float *__restrict__ dL_dconic_opacity, const float *__restrict__ dL_drgb, int gstride,
+                          const K11Adam ad_in, const SparseWs *__restrict__ ws, const uint32_t *__restrict__ list,
+                          uint32_t *__restrict__ num_active) {
+    if (ad_in.skip && *ad_in.skip) return;
+    const uint32_t count = min(ws->count, (uint32_t)P);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && num_active) *num_active = count;
+    const size_t first = (size_t)blockIdx.x * K11_BLOCK;
+    if (first >= count) return;  // (uniform) past the list: at a tenth of the rows active, nine workgroups of ten
+    const K11Adam ad = k11_adam_resolve(ad_in);
+    constexpr int NC = (DEG + 1) * (DEG + 1);
+    constexpr int UN = 5;  // words per lane in flight in the stage's copies: 45 = 9 x 5
+    __shared__ float s_rest[K11_BLOCK * REST_W];
+    __shared__ uint32_t s_rows[K11_BLOCK];
+    const int rows = (int)min((size_t)K11_BLOCK, (size_t)count - first);
+    const int nw = rows * REST_W;
+    const bool live = (int)threadIdx.x < rows;
+    // (clamped slot: lanes past the end of the list load the last row's inputs and compute nothing)
+    const uint32_t irow = list[first + min((int)threadIdx.x, rows - 1)];
+    s_rows[threadIdx.x] = irow;
+    const size_t ic = irow;
+    const float p[3] = {xyz[3 * ic], xyz[3 * ic + 1], xyz[3 * ic + 2]};
+    float cvr[6];
+#pragma unroll
+    for (int e = 0; e < 6; e++) cvr[e] = cov3D[6 * ic + e];
+    const float dc[3] = {f_dc[3 * ic], f_dc[3 * ic + 1], f_dc[3 * ic + 2]};
+    const float oraw = opacity[ic];
+    const float4 qraw = *reinterpret_cast<const float4 *>(rotation + 4 * ic);
+    const float scraw[3] = {scaling[3 * ic], scaling[3 * ic + 1], scaling[3 * ic + 2]};
+    __syncthreads();
+    // ---- the rows' SH coefficients above DC into the stage
+    for (int k0 = 0; k0 < REST_W; k0 += UN) {
+        float v[UN];
+#pragma unroll
+        for (int u = 0; u < UN; u++)
+            v[u] = f_rest[sa_rest_offset(s_rows, min((k0 + u) * K11_BLOCK + (int)threadIdx.x, nw - 1))];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < UN; u++) {
+            const int e = (k0 + u) * K11_BLOCK + (int)threadIdx.x;
+            if (e < nw) s_rest[e] = v[u];
+        }
+    }
+    __syncthreads();
+    if (live) {
+        float sp[14], sg[14];
+        float S[3][3];
+        cov3d_unpack(cvr, S);
+        const float *const shl = s_rest + threadIdx.x * REST_W;
+        float sh[NC * 3];
+        sh[0] = dc[0];
+        sh[1] = dc[1];
+        sh[2] = dc[2];
+        float dmean[3] = {0.f, 0.f, 0.f};
+        float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float dsh[NC * 3];
+#pragma unroll
+        for (int k = 0; k < NC * 3; k++) dsh[k] = 0.f;
+        float dop = 0.f;
+        // colour part of all cameras, then geometry part of all cameras: the batched body's order of summation
+        for (int bc = 0; bc < B; bc++) {
+            const size_t o = (size_t)bc * P + ic;
+            const K11CamSH cin = k11_cam_load_sh(o, radii, clamped, dL_drgb, gstride);
+            if (cin.rad <= 0) continue;
+            asm volatile("" ::: "memory");  // (keeps the LDS reads of the coefficients inside the loop)
+            const float *cp = cams + (size_t)bc * CAM_STRIDE;
+            const float camc[3] = {cp[32], cp[33], cp[34]};
+            const float g3[3] = {cin.cl[0] ? 0.f : cin.grgb[0], cin.cl[1] ? 0.f : cin.grgb[1],
+                                 cin.cl[2] ? 0.f : cin.grgb[2]};
+            float dm[3];
+            viewdir_backward<DEG>(camc, p, ShStagedOrRegs{true, shl, sh}, g3, DshAdd{dsh}, dm);
+            dmean[0] += dm[0];
+            dmean[1] += dm[1];
+            dmean[2] += dm[2];
+        }
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+            sp[10 + e] = sh[e];
+            sg[10 + e] = dsh[e];
+        }
+        {
+            float *rp = s_rest + threadIdx.x * REST_W;  // the row's own words: its gradient replaces its coefficients
+#pragma unroll
+            for (int k = 3; k < NC * 3; k++) rp[k - 3] = dsh[k];
+            for (int k = NC * 3; k < 16 * 3; k++) rp[k - 3] = 0.f;
+        }
+        for (int bc = 0; bc < B; bc++) {
+            const size_t o = (size_t)bc * P + ic;
+            const K11CamGeo cin = k11_cam_load_geo(o, radii, dL_dmeans2D, dL_dconic_opacity, gstride);
+            if (cin.rad <= 0) continue;
+            const float *cp = cams + (size_t)bc * CAM_STRIDE;
+            const Cam cam = load_cam_packed(cp);
+            const float tanfovx = cp[35], tanfovy = cp[36];
+            const float fx = W / (2.0f * tanfovx), fy = H / (2.0f * tanfovy);
+            const float4 gco = cin.gco;
+            const float gA = gco.x, gB = gco.y, gC = gco.z;
+            dop += gco.w;
+            const Cov2DGrad cg = cov2d_backward(cam.v, fx, fy, tanfovx, tanfovy, p, S, gA, gB, gC);
+            if (cg.live) {
+#pragma unroll
+                for (int e = 0; e < 6; e++) dcov[e] += cg.dcov[e];
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) dmean[k] += cg.dmean[k];
+            float dm[3];
+            means2d_to_mean(cam.p, p, cin.g2, dm);
+#pragma unroll
+            for (int k = 0; k < 3; k++) dmean[k] += dm[k];
+        }
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+            sp[e] = p[e];
+            sg[e] = dmean[e];
+        }
+        {
+            const float so = sigmoidf(oraw);
+            sp[13] = oraw;
+            sg[13] = dop * so * (1.0f - so);
+        }
+        {
+            float gsc[3];
+            float4 gq;
+            cov3d_backward<true>(qraw, scraw, scale_modifier, dcov, gsc, gq);
+#pragma unroll
+            for (int e = 0; e < 3; e++) {
+                sp[3 + e] = scraw[e];
+                sg[3 + e] = gsc[e];
+            }
+            sp[6] = qraw.x; sp[7] = qraw.y; sp[8] = qraw.z; sp[9] = qraw.w;
+            sg[6] = gq.x; sg[7] = gq.y; sg[8] = gq.z; sg[9] = gq.w;
+        }
+        // ---- the 14 per-lane values: a gathered row's moments are 12 / 16 / 4 bytes here and there, read by the lane
+        constexpr int T[14] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 5};
+        constexpr int KK[14] = {3, 3, 3, 3, 3, 3, 4, 4, 4, 4, 3, 3, 3, 1};
+        constexpr int C[14] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 0};
+        float *const base[6] = {xyz, scaling, rotation, f_dc, nullptr, opacity};
+        float m[14], v[14];
+#pragma unroll
+        for (int e = 0; e < 14; e++) {
+            m[e] = ad.m[T[e]][ic * KK[e] + C[e]];
+            v[e] = ad.v[T[e]][ic * KK[e] + C[e]];
+        }
+#pragma unroll
+        for (int e = 0; e < 14; e++) {
+            const int t = T[e];
+            float pe = sp[e];
+            gsr_adam1(pe, __fmul_rn(sg[e], ad.grad_scale), m[e], v[e], ad.lr_c[t], ad.b1[t], ad.b2[t], ad.omb1[t],
+                      ad.omb2[t], ad.inv_sqrt_bc2[t], ad.eps[t]);
+            base[t][ic * KK[e] + C[e]] = pe;
+            ad.m[t][ic * KK[e] + C[e]] = m[e];
+            ad.v[t][ic * KK[e] + C[e]] = v[e];
+        }
+    }
+    __syncthreads();
+    // ---- _features_rest: gradient from the stage, parameter and moments gathered in the stage's order
+    {
+        constexpr int t = 4;
+        float *const mr = ad.m[t], *const vr = ad.v[t];
+        const float gs = ad.grad_scale, lr_c = ad.lr_c[t], b1 = ad.b1[t], b2 = ad.b2[t], omb1 = ad.omb1[t],
+                    omb2 = ad.omb2[t], isb = ad.inv_sqrt_bc2[t], eps = ad.eps[t];
+        for (int k0 = 0; k0 < REST_W; k0 += UN) {
+            size_t off[UN];
+            float pn[UN], mn[UN], vn[UN];
+#pragma unroll
+            for (int u = 0; u < UN; u++) {
+                off[u] = sa_rest_offset(s_rows, min((k0 + u) * K11_BLOCK + (int)threadIdx.x, nw - 1));
+                pn[u] = f_rest[off[u]];
+                mn[u] = mr[off[u]];
+                vn[u] = vr[off[u]];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < UN; u++) {
+                const int e = (k0 + u) * K11_BLOCK + (int)threadIdx.x;
+                if (e < nw) {
+                    gsr_adam1(pn[u], __fmul_rn(s_rest[e], gs), mn[u], vn[u], lr_c, b1, b2, omb1, omb2, isb, eps);
+                    f_rest[off[u]] = pn[u];
+                    mr[off[u]] = mn[u];
+                    vr[off[u]] = vn[u];
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------- K11c: camera (pose) gradients
 // dL/d(viewmatrix, projmatrix, campos) of a batch of cameras: per visible Gaussian and camera the 27 sums below,
 // reduced over the whole shard.  The per-Gaussian quantities are K11's own (the same dL_da/db/dc with its
@@ -1842,6 +2123,67 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_dyn(
                                         reinterpret_cast<hipStream_t>(stream), P, B, xyz, scaling, scale_modifier,
                                         rotation, features_dc, features_rest, opacity, cams, width, height, radii,
                                         cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride, ad));
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
+// The sparse (lazy) form of the fused launch: see the kernels above and include/gsraster.h.
+extern "C" size_t gsr_sparse_step_workspace_bytes(int P) {
+    return sizeof(SparseWs) + sizeof(uint32_t) * 2 * (((size_t)(P > 0 ? P : 1) + 1) / 2);  // a multiple of 8 bytes
+}
+
+extern "C" int gsr_preprocess_backward_adam_raw_batched_sparse(
+    int P, int B, int sh_degree, int sh_coeffs, float *xyz, float *scaling, float scale_modifier, float *rotation,
+    float *features_dc, float *features_rest, float *opacity, const float *cams, int width, int height,
+    const int32_t *radii, const float *cov3D, const uint8_t *clamped, const float *dL_dmeans2D,
+    const float *dL_dconic_opacity, const float *dL_drgb, int grad_row_stride, float *const *exp_avgs,
+    float *const *exp_avg_sqs, const double *lrs, const double *beta1s, const double *beta2s, const double *epss,
+    const int64_t *steps, float grad_scale, const float *dyn_dev, const uint32_t *skip_flag_dev, void *workspace,
+    size_t workspace_bytes, uint8_t *active_out, uint32_t *num_active_dev, gsr_stream_t stream) {
+    if (P < 0 || B < 1 || sh_degree < 0 || sh_degree > 3 || sh_coeffs != 16 || width <= 0 || height <= 0 ||
+        grad_row_stride < 0 || (grad_row_stride != 0 && grad_row_stride < 9))
+        return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!xyz || !scaling || !rotation || !features_dc || !features_rest || !opacity || !cams || !radii || !cov3D ||
+        !clamped || !dL_dmeans2D || !dL_dconic_opacity || !dL_drgb || !exp_avgs || !exp_avg_sqs || !beta1s ||
+        !beta2s || !epss || (!dyn_dev && (!lrs || !steps)) || !workspace)
+        return GSR_EINVAL;
+    K11Adam ad{};
+    ad.dyn = dyn_dev;
+    ad.skip = skip_flag_dev;
+    for (int t = 0; t < 6; t++) {
+        if (!exp_avgs[t] || !exp_avg_sqs[t] || (!dyn_dev && steps[t] < 1)) return GSR_EINVAL;
+        const double bc1 = dyn_dev ? 1.0 : 1.0 - pow(beta1s[t], (double)steps[t]);
+        const double bc2 = dyn_dev ? 1.0 : 1.0 - pow(beta2s[t], (double)steps[t]);
+        ad.m[t] = exp_avgs[t];
+        ad.v[t] = exp_avg_sqs[t];
+        ad.lr_c[t] = dyn_dev ? 0.f : (float)(lrs[t] / bc1);
+        ad.b1[t] = (float)beta1s[t];
+        ad.b2[t] = (float)beta2s[t];
+        ad.omb1[t] = (float)(1.0 - beta1s[t]);
+        ad.omb2[t] = (float)(1.0 - beta2s[t]);
+        ad.inv_sqrt_bc2[t] = (float)(1.0 / sqrt(bc2));
+        ad.eps[t] = (float)epss[t];
+    }
+    ad.grad_scale = grad_scale;
+    if ((uintptr_t)rotation & 15) return GSR_EINVAL;  // the quaternion is one 16-byte load
+    if (grad_row_stride == 0 && (((uintptr_t)dL_dmeans2D & 7) || ((uintptr_t)dL_dconic_opacity & 15)))
+        return GSR_EINVAL;  // dense gradients are read with 8- / 16-byte loads
+    if (((uintptr_t)workspace & 7) || workspace_bytes < gsr_sparse_step_workspace_bytes(P)) return GSR_ENOSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    SparseWs *ws = static_cast<SparseWs *>(workspace);
+    uint32_t *list = reinterpret_cast<uint32_t *>(ws + 1);
+    hipLaunchKernelGGL(sparse_adam_reset_kernel, dim3(1), dim3(1), 0, st, skip_flag_dev, ws);
+    GSR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sparse_adam_classify_kernel, dim3(gsr_div_up(P, SA_CROWS)), dim3(SA_CBLOCK), 0, st, P, B, radii,
+                       dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride, skip_flag_dev, ws, list, active_out);
+    GSR_LAUNCH_CHECK();
+    const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
+    GSR_DISPATCH_DEG(sh_degree,
+                     hipLaunchKernelGGL(sparse_adam_update_kernel<DEG>, grid, block, 0, st, P, B, xyz, scaling,
+                                        scale_modifier, rotation, features_dc, features_rest, opacity, cams, width,
+                                        height, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb,
+                                        grad_row_stride, ad, ws, list, num_active_dev));
     GSR_LAUNCH_CHECK();
     return 0;
 }

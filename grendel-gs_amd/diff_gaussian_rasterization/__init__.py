@@ -585,10 +585,15 @@ class PendingProjectionBackward:
         return _launch_k11(self.params, self.cams, self.radii, self.cov3D, self.clamped, self.g_means2D,
                            self.g_conic_opacity, self.g_rgb, self.gstride, self.meta, self.tanfov0, None)
 
-    def fused_step(self, exp_avgs, exp_avg_sqs, lrs, beta1s, beta2s, epss, steps, grad_scale, cache=None):
+    def fused_step(self, exp_avgs, exp_avg_sqs, lrs, beta1s, beta2s, epss, steps, grad_scale, cache=None,
+                   sparse=False):
         """K11 + Adam of the six tensors in one launch; arguments in the order of self.params.  `cache`: a dict the
         caller keeps between steps -- the ctypes tables of the moments' addresses and of the betas / eps only change
-        when the model is rebuilt, and this call sits on the host's critical path in front of the launch."""
+        when the model is rebuilt, and this call sits on the host's critical path in front of the launch.
+        `sparse`: the lazy update over the rows that received a gradient (include/gsraster.h:
+        gsr_preprocess_backward_adam_raw_batched_sparse) instead of the dense one; its workspace and the device word
+        that receives the number of active rows live in `cache` ("sparse_ws", "num_active"), grow-only and re-made when
+        P changes, so a captured iteration allocates nothing new on replay."""
         self.join_stream()
         xyz, scaling, rotation, f_dc, f_rest, opacity = self.params
         deg, smod, W, H, M = self.meta
@@ -604,6 +609,28 @@ class PendingProjectionBackward:
         tf = (ctypes.c_float * 2)(float(self.tanfov0[0]), float(self.tanfov0[1])) \
             if (B == 1 and self.tanfov0 is not None) else None
         cap_ctx = _CAPTURE[0]
+        if sparse:
+            if cache is None:
+                cache = {}
+            need = int(lib.gsr_sparse_step_workspace_bytes(P))
+            ws = cache.get("sparse_ws")
+            if ws is None or ws[0] != P or ws[1].device != xyz.device or ws[1].numel() * 8 < need:
+                ws = (P, torch.empty((need + 7) // 8, dtype=torch.int64, device=xyz.device),
+                      torch.zeros(1, dtype=torch.int32, device=xyz.device))
+                cache["sparse_ws"] = ws
+                cache["num_active"] = ws[2]
+            dyn, flag = (_ptr(cap_ctx.dyn), _ptr(cap_ctx.flag)) if cap_ctx is not None else (None, None)
+            with _on(xyz.device), (kernel_timer.range("preprocess_backward_adam_sparse", N=P, B=B, M=M)
+                                   if cap_ctx is None else _NULL_RANGE):
+                check(lib.gsr_preprocess_backward_adam_raw_batched_sparse(
+                    P, B, deg, M, _ptr(xyz), _ptr(scaling), smod, _ptr(rotation), _ptr(f_dc), _ptr(f_rest),
+                    _ptr(opacity), _ptr(self.cams), W, H, _ptr(self.radii), _ptr(self.cov3D), _ptr(self.clamped),
+                    _ptr(self.g_means2D), _ptr(self.g_conic_opacity), _ptr(self.g_rgb), self.gstride, tabs[1], tabs[2],
+                    None if cap_ctx is not None else D(*lrs), tabs[3], tabs[4], tabs[5],
+                    None if cap_ctx is not None else I64(*steps), float(grad_scale), dyn, flag, _ptr(ws[1]),
+                    ws[1].numel() * 8, None, _ptr(ws[2]), _stream()),
+                    "gsr_preprocess_backward_adam_raw_batched_sparse")
+            return
         if cap_ctx is not None:
             # captured launch: lr / bias corrections come from the capture's device block at execution time, and the
             # launch is a no-op when a capacity check of the same replay has raised the flag word

@@ -94,6 +94,12 @@ SIGNATURES = {
     "gsr_preprocess_backward_adam_raw_batched_dyn": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float] +
                                                      [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 6 + [c_int] +
                                                      [c_void_p] * 7 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_sparse_step_workspace_bytes": (c_size_t, [c_int]),
+    "gsr_preprocess_backward_adam_raw_batched_sparse": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                                c_float] + [c_void_p] * 5 + [c_int, c_int] +
+                                                        [c_void_p] * 6 + [c_int] + [c_void_p] * 7 +
+                                                        [c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                                         c_void_p, c_void_p]),
     "gsr_preprocess_backward_cams_bytes": (c_size_t, [c_int, c_int]),
     "gsr_preprocess_backward_cams": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                              c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_size_t,

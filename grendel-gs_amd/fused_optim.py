@@ -17,8 +17,21 @@ as reset_opacity -- materialized for the tensors that are still current), `zero_
 backward before the step materializes both.  What changes: code that READS `.grad` of the raw parameters between
 backward and step sees None -- the reference's own `param.grad /= bsz` loop (train_internal.py:319-324) would be such a
 reader and silently do nothing, so the scale has to be passed as `grad_scale` (constructor or step()), as bench.py
-does.  `means2D.grad` (densification statistics) is unaffected: it comes from K10, not K11."""
+does.  `means2D.grad` (densification statistics) is unaffected: it comes from K10, not K11.
+
+`sparse=True` (opt-in, needs fuse_backward; default from the environment variable GSR_SPARSE_ADAM, read at construction:
+"" and "0" mean off) makes the fused launch a SPARSE one (include/gsraster.h:
+gsr_preprocess_backward_adam_raw_batched_sparse): only the rows that received a gradient in this step -- visible in
+some camera of the batch with a non-zero incoming gradient word -- are updated, with exactly the dense arithmetic; all
+other rows are not touched and none of their 1.4 KB of parameters and moments moves through HBM.  This is LAZY Adam and
+NOT what the reference's dense optimizer does: for a row without a gradient the moments do not decay and the parameter
+does not coast on its momentum; the bias corrections still come from the group's global step count, which advances
+every step for all six groups.  A step that cannot be fused (a materialized pending gradient, sh_coeffs != 16,
+parameters outside the projection backward) takes the plain dense Adam for the tensors concerned and is counted in
+`dense_fallback_steps`; sparse launches are counted in `sparse_steps`, and `last_num_active` is the device word with
+the number of rows the last sparse launch updated (reading it is the caller's sync)."""
 import ctypes
+import os
 
 import torch
 
@@ -27,7 +40,13 @@ from diff_gaussian_rasterization import _lib, _on, _stream, kernel_timer
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, fuse_backward=False, grad_scale=1.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, fuse_backward=False, grad_scale=1.0,
+                 sparse=None):
+        if sparse is None:  # the environment's default only applies where the mode can run
+            sparse = bool(fuse_backward) and os.environ.get("GSR_SPARSE_ADAM", "0") not in ("", "0")
+        if sparse and not fuse_backward:
+            raise ValueError("FusedAdam(sparse=True) needs fuse_backward=True: the sparse update is a form of the fused "
+                             "K11 + Adam launch")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self.grad_scale = float(grad_scale)
         self._pending = None
@@ -36,6 +55,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._warned_replicated = False
         self.fused_steps = 0         # steps in which K11 ran inside the optimizer kernel
         self.materialized_steps = 0  # deferred backwards that had to fall back to the plain K11
+        self.sparse = bool(sparse)
+        self.sparse_steps = 0          # fused steps that ran as the sparse launch
+        self.dense_fallback_steps = 0  # steps of the sparse mode in which the plain dense Adam updated something
         self.fuse_backward = False
         if fuse_backward:
             self.set_fuse_backward(True)
@@ -48,6 +70,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._warned_replicated = False
         self.__dict__.setdefault("fused_steps", 0)
         self.__dict__.setdefault("materialized_steps", 0)
+        self.__dict__.setdefault("sparse", False)
+        self.__dict__.setdefault("sparse_steps", 0)
+        self.__dict__.setdefault("dense_fallback_steps", 0)
 
     # ------------------------------------------------------------------ deferred K11 (see the module docstring)
     def set_fuse_backward(self, on):
@@ -59,6 +84,18 @@ class FusedAdam(torch.optim.Optimizer):
         elif _dgr.deferred_backward_sink() is self:
             self._flush_pending()
             _dgr.set_deferred_backward_sink(None)
+
+    def set_sparse(self, on):
+        """switch the sparse (lazy) form of the fused launch on / off; see the module docstring"""
+        if on and not self.fuse_backward:
+            raise ValueError("FusedAdam.set_sparse(True) needs fuse_backward=True")
+        self.sparse = bool(on)
+
+    @property
+    def last_num_active(self):
+        """the device word (int32 tensor of one element) with the number of rows the last sparse launch updated, or
+        None before the first one; reading its value synchronizes with the device"""
+        return self._launch_cache.get("num_active")
 
     def _owner(self, t):
         """(group, parameter) of this optimizer whose storage is tensor t, or None"""
@@ -186,7 +223,8 @@ class FusedAdam(torch.optim.Optimizer):
         pend.fused_step([st["exp_avg"] for st in sts], [st["exp_avg_sq"] for st in sts],
                         [g["lr"] for g, _ in owners], [g["betas"][0] for g, _ in owners],
                         [g["betas"][1] for g, _ in owners], [g["eps"] for g, _ in owners],
-                        [int(st["step"]) + 1 for st in sts], grad_scale, cache=self._launch_cache)
+                        [int(st["step"]) + 1 for st in sts], grad_scale, cache=self._launch_cache,
+                        **({"sparse": True} if self.sparse else {}))
         if _dgr.capturing() is not None:
             # the launch was recorded into a hipGraph, not executed: the step counters move when a replay is launched
             # (graph_advance); the graph's owner finds the six (group, parameter) pairs here
@@ -194,6 +232,8 @@ class FusedAdam(torch.optim.Optimizer):
             return {id(p) for _, p in owners}
         torch._foreach_add_([st["step"] for st in sts], 1)
         self.fused_steps += 1
+        if self.sparse:
+            self.sparse_steps += 1
         return {id(p) for _, p in owners}
 
     # ------------------------------------------------------------------ a captured iteration (graphed_step.py)
@@ -213,13 +253,15 @@ class FusedAdam(torch.optim.Optimizer):
         """a replay of the captured iteration has been launched (n > 0) / n replays turned out to be no-ops (n < 0)"""
         torch._foreach_add_([self.state[p]["step"] for _, p in self._graph_owners], float(n))
         self.fused_steps += n
+        if self.sparse:
+            self.sparse_steps += n
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=None):
         """`grad_scale` multiplies every gradient before the update (1 / bsz in the reference's loop; default: the
         constructor's).  All parameter tensors that have a gradient are updated by ONE kernel launch
         (gsr_adam_step_multi); with fuse_backward the six raw parameters of a pending projection backward are updated
-        by the fused K11 + Adam launch instead."""
+        by the fused K11 + Adam launch instead -- with `sparse`, its lazy form over the rows that received a gradient."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -252,6 +294,8 @@ class FusedAdam(torch.optim.Optimizer):
                                "outside the projection backward carry gradients)")
         if steps:
             torch._foreach_add_(steps, 1)  # host tensors, as in the stock optimizer's state
+            if self.sparse:
+                self.dense_fallback_steps += 1
         for i in range(0, len(batch), 16):
             part = batch[i:i + 16]
             K = len(part)

@@ -677,6 +677,50 @@ int gsr_preprocess_backward_adam_raw_batched_dyn(int P, int B, int sh_degree, in
                                                  float grad_scale, const float *tanfov0, const float *dyn_dev,
                                                  const uint32_t *skip_flag_dev, gsr_stream_t stream);
 
+/* Sparse Adam: the fused K11 + Adam update over the rows that received a gradient (opt-in; LAZY Adam, not what the
+ * reference's dense optimizer does -- so there is no reference call site for this entry point: the dense pair
+ * gsr_preprocess_backward_raw_batched + gsr_adam_step_multi, restricted to the active rows, is the arbiter).
+ * Row i is ACTIVE in a step iff some camera k < B has radii[k,i] > 0 and at least one of that camera's nine incoming
+ * gradient words for the row compares != 0.0f.  The nine words are 2 of dL_dmeans2D, 3 of dL_drgb and 4 of
+ * dL_dconic_opacity.
+ *   - -0.0 counts as zero.
+ *   - A NaN counts as non-zero, so a poisoned gradient is never hidden.
+ *   - The gradient words of a (k,i) with radii[k,i] <= 0 must not influence anything.
+ * K11 is linear in the incoming gradients and yields zeros for culled Gaussians, so the inactive rows are exactly the
+ * rows whose six parameter gradients are zero by construction in the dense path.
+ *   - Active rows get the dense fused update: the same K11 sums in the same order as the camera-batched kernel, then
+ *     gsr_adam_step_multi's arithmetic with grad_scale.  Bias corrections come from the group's global step count
+ *     (steps / dyn_dev), not from a count per row.
+ *   - Inactive rows are not touched: parameters and both moments stay bit for bit what they were (the moments do not
+ *     decay, the parameter does not coast on its momentum), and nothing is read from them beyond radii and, where
+ *     radii > 0, the gradient words.
+ *   - The caller advances the step counters of all six groups by one per step, as in the dense path.
+ * P .. grad_row_stride and exp_avgs .. grad_scale exactly as in gsr_preprocess_backward_adam_raw_batched_dyn (there is
+ * no tanfov0: one kernel serves every B, tanfov comes from the camera record), dyn_dev and skip_flag_dev as there.
+ * Needs sh_coeffs == 16.  Three launches on `stream` and no host read-back (capturable in a hipGraph): the active rows
+ * are compacted into a list in `workspace` (8-byte aligned, >= gsr_sparse_step_workspace_bytes(P), need not be zeroed,
+ * private to the call until it has executed) and the update runs a grid of fixed size that takes the count from there.
+ * The order of the list is not defined; every row is updated by exactly one lane, so the results do not depend on it.
+ * active_out (DEVICE, [P] bytes, may be NULL): 1 for every updated row, 0 for the others.  num_active_dev (DEVICE word,
+ * may be NULL): the number of active rows.  A non-zero skip word makes the call change nothing at all: active_out and
+ * num_active_dev are then left untouched too.  Arguments are validated before any device work -- GSR_EINVAL: a null
+ * pointer, sh_coeffs != 16, a negative size, rotation (or, with grad_row_stride == 0, a gradient) not aligned for its
+ * vector loads; GSR_ENOSPACE: a workspace that is too small or not 8-byte aligned.  P == 0 returns 0. */
+size_t gsr_sparse_step_workspace_bytes(int P);
+int gsr_preprocess_backward_adam_raw_batched_sparse(int P, int B, int sh_degree, int sh_coeffs, float *xyz,
+                                                    float *scaling, float scale_modifier, float *rotation,
+                                                    float *features_dc, float *features_rest, float *opacity,
+                                                    const float *cams, int width, int height, const int32_t *radii,
+                                                    const float *cov3D, const uint8_t *clamped,
+                                                    const float *dL_dmeans2D, const float *dL_dconic_opacity,
+                                                    const float *dL_drgb, int grad_row_stride,
+                                                    float *const *exp_avgs, float *const *exp_avg_sqs,
+                                                    const double *lrs, const double *beta1s, const double *beta2s,
+                                                    const double *epss, const int64_t *steps, float grad_scale,
+                                                    const float *dyn_dev, const uint32_t *skip_flag_dev,
+                                                    void *workspace, size_t workspace_bytes, uint8_t *active_out,
+                                                    uint32_t *num_active_dev, gsr_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * a19  fused parameter activations -- GaussianModel.get_scaling / get_rotation / get_opacity /
  * get_features (scene/gaussian_model.py:109-129): scales = exp(_scaling) [N,3], rotations =
