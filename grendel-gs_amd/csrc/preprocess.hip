@@ -10,6 +10,9 @@
 // off so that integer outputs (radii, tile rects) are reproducible against a plain C evaluation.
 #include "common.h"
 
+#include <initializer_list>
+#include <type_traits>
+
 // no FMA contraction in this file: see the header comment (memory-bound kernels, no cost)
 #pragma clang fp contract(off)
 
@@ -1213,7 +1216,98 @@ __device__ __forceinline__ K11CamGeo k11_cam_load_geo(size_t o, const int32_t *_
     return c;
 }
 
-template <int DEG, bool ADAM>
+// Where the lanes of the camera-batched body find their rows.  DenseRows: lane i of the grid owns row i, a workgroup's
+// rows are contiguous (the LDS stage moves them in 16-byte pieces).  ListRows (the sparse update, ADAM and 16
+// coefficients only): lane e of workgroup c owns row list[c * K11_BLOCK + e] where that is below count, and the caller
+// has sent home the workgroups with c * K11_BLOCK >= count; the rows lie anywhere, so the stage and the moments are
+// gathered word by word through the row table in LDS with the three device functions below.  Everything between
+// stage-in and update -- both camera loops, the SH gradient over the stage, the 14 slots -- is one text for both
+// (DESIGN.md 3.3 on why it is a parameter of the body and not a set of shared helpers).
+struct DenseRows {};
+struct ListRows {
+    const uint32_t *list;
+    uint32_t count;
+};
+constexpr int SA_UN = 5;  // words per lane in flight in the gathered stage's copies: 45 = 9 x 5
+// word e of the workgroup's K11_BLOCK x 45 stage -> its offset in a [P, 45] array, through the row list in LDS
+__device__ __forceinline__ size_t sa_rest_offset(const uint32_t *__restrict__ s_rows, int e) {
+    const int r = e / REST_W;
+    return (size_t)s_rows[r] * REST_W + (size_t)(e - r * REST_W);
+}
+// the listed rows' SH coefficients above DC into the stage (nw: words of the workgroup's rows)
+__device__ __forceinline__ void sa_rest_stage_in(float *__restrict__ s_rest, const uint32_t *__restrict__ s_rows,
+                                                 const float *__restrict__ f_rest, int nw) {
+    for (int k0 = 0; k0 < REST_W; k0 += SA_UN) {
+        float v[SA_UN];
+#pragma unroll
+        for (int u = 0; u < SA_UN; u++)
+            v[u] = f_rest[sa_rest_offset(s_rows, min((k0 + u) * K11_BLOCK + (int)threadIdx.x, nw - 1))];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < SA_UN; u++) {
+            const int e = (k0 + u) * K11_BLOCK + (int)threadIdx.x;
+            if (e < nw) s_rest[e] = v[u];
+        }
+    }
+}
+// the 14 per-lane values of row ic: a gathered row's moments are 12 / 16 / 4 bytes here and there, read by the lane
+__device__ __forceinline__ void sa_adam_small(const K11Adam &ad, size_t ic, float *__restrict__ xyz,
+                                              float *__restrict__ scaling, float *__restrict__ rotation,
+                                              float *__restrict__ f_dc, float *__restrict__ opacity,
+                                              const float (&sp)[14], const float (&sg)[14]) {
+    constexpr int T[14] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 5};
+    constexpr int KK[14] = {3, 3, 3, 3, 3, 3, 4, 4, 4, 4, 3, 3, 3, 1};
+    constexpr int C[14] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 0};
+    float *const base[6] = {xyz, scaling, rotation, f_dc, nullptr, opacity};
+    float m[14], v[14];
+#pragma unroll
+    for (int e = 0; e < 14; e++) {
+        m[e] = ad.m[T[e]][ic * KK[e] + C[e]];
+        v[e] = ad.v[T[e]][ic * KK[e] + C[e]];
+    }
+#pragma unroll
+    for (int e = 0; e < 14; e++) {
+        const int t = T[e];
+        float pe = sp[e];
+        gsr_adam1(pe, __fmul_rn(sg[e], ad.grad_scale), m[e], v[e], ad.lr_c[t], ad.b1[t], ad.b2[t], ad.omb1[t],
+                  ad.omb2[t], ad.inv_sqrt_bc2[t], ad.eps[t]);
+        base[t][ic * KK[e] + C[e]] = pe;
+        ad.m[t][ic * KK[e] + C[e]] = m[e];
+        ad.v[t][ic * KK[e] + C[e]] = v[e];
+    }
+}
+// _features_rest of the listed rows: gradient from the stage, parameter and moments gathered in the stage's order
+__device__ __forceinline__ void sa_rest_adam_out(const float *__restrict__ s_rest, const uint32_t *__restrict__ s_rows,
+                                                 float *__restrict__ f_rest, const K11Adam &ad, int nw) {
+    constexpr int t = 4;
+    float *const mr = ad.m[t], *const vr = ad.v[t];
+    const float gs = ad.grad_scale, lr_c = ad.lr_c[t], b1 = ad.b1[t], b2 = ad.b2[t], omb1 = ad.omb1[t],
+                omb2 = ad.omb2[t], isb = ad.inv_sqrt_bc2[t], eps = ad.eps[t];
+    for (int k0 = 0; k0 < REST_W; k0 += SA_UN) {
+        size_t off[SA_UN];
+        float pn[SA_UN], mn[SA_UN], vn[SA_UN];
+#pragma unroll
+        for (int u = 0; u < SA_UN; u++) {
+            off[u] = sa_rest_offset(s_rows, min((k0 + u) * K11_BLOCK + (int)threadIdx.x, nw - 1));
+            pn[u] = f_rest[off[u]];
+            mn[u] = mr[off[u]];
+            vn[u] = vr[off[u]];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < SA_UN; u++) {
+            const int e = (k0 + u) * K11_BLOCK + (int)threadIdx.x;
+            if (e < nw) {
+                gsr_adam1(pn[u], __fmul_rn(s_rest[e], gs), mn[u], vn[u], lr_c, b1, b2, omb1, omb2, isb, eps);
+                f_rest[off[u]] = pn[u];
+                mr[off[u]] = mn[u];
+                vr[off[u]] = vn[u];
+            }
+        }
+    }
+}
+
+template <int DEG, bool ADAM, typename ROWS = DenseRows>
 __device__ __forceinline__ void
 preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ xyz,
                                    const float *__restrict__ scaling, float scale_modifier,
@@ -1226,16 +1320,31 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
                                    int gstride,
                                    float *__restrict__ dL_dxyz, float *__restrict__ dL_dscaling,
                                    float4 *__restrict__ dL_drotation, float *__restrict__ dL_ddc,
-                                   float *__restrict__ dL_drest, float *__restrict__ dL_dopacity, const K11Adam &ad) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+                                   float *__restrict__ dL_drest, float *__restrict__ dL_dopacity, const K11Adam &ad,
+                                   const ROWS rows = ROWS{}) {
+    constexpr bool LIST = std::is_same<ROWS, ListRows>::value;
+    static_assert(!LIST || ADAM, "ListRows is the sparse K11 + Adam update (and takes M == 16)");
     __shared__ float s_rest[K11_BLOCK * REST_W];
+    __shared__ uint32_t s_rows[LIST ? K11_BLOCK : 1];  // ListRows: the workgroup's rows, for the gathers
     const bool staged = M == 16;  // _features_rest in, its gradient out: coalesced through LDS (ADAM: always)
     constexpr int NC = (DEG + 1) * (DEG + 1);
     // ---- every load of the lane that does not depend on another is issued here, before the first result is used
-    // (clamped index: lanes past the end load the last Gaussian's inputs and compute nothing)
-    const size_t ic = (size_t)min(i, P - 1);
+    // (clamped index: lanes past the end load the last Gaussian's / the list's last row's inputs and compute nothing)
+    int i, nrows = 0;  // the lane's row;  ListRows: the workgroup's share of the list
+    size_t ic;
     RestStage st;
-    if (staged) st = rest_stage_issue(f_rest, P);
+    if constexpr (LIST) {
+        const size_t first = (size_t)blockIdx.x * K11_BLOCK;
+        nrows = (int)min((size_t)K11_BLOCK, (size_t)rows.count - first);
+        const uint32_t irow = rows.list[first + min((int)threadIdx.x, nrows - 1)];
+        s_rows[threadIdx.x] = irow;
+        i = (int)irow;
+        ic = irow;
+    } else {
+        i = blockIdx.x * blockDim.x + threadIdx.x;
+        ic = (size_t)min(i, P - 1);
+        if (staged) st = rest_stage_issue(f_rest, P);
+    }
     const float p[3] = {xyz[3 * ic], xyz[3 * ic + 1], xyz[3 * ic + 2]};
     float cvr[6];
 #pragma unroll
@@ -1244,21 +1353,29 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
     const float oraw = opacity[ic];
     const float4 qraw = *reinterpret_cast<const float4 *>(rotation + 4 * ic);
     const float scraw[3] = {scaling[3 * ic], scaling[3 * ic + 1], scaling[3 * ic + 2]};
+    // (ListRows has no camera queue: its lanes load a camera's words inside the loops.  With the queue the sparse launch
+    // measured 4-6 % slower at one camera, where the queue's slots hold the same camera twice: EXPERIMENTS.md)
     K11CamSH shq[K11_CAMQ];
     K11CamGeo geoq[K11_CAMQ];
+    if constexpr (!LIST) {
 #pragma unroll
-    for (int u = 0; u < K11_CAMQ; u++) {
-        const size_t o = (size_t)min(u, B - 1) * P + ic;
-        shq[u] = k11_cam_load_sh(o, radii, clamped, dL_drgb, gstride);
-        geoq[u] = k11_cam_load_geo(o, radii, dL_dmeans2D, dL_dconic_opacity, gstride);
+        for (int u = 0; u < K11_CAMQ; u++) {
+            const size_t o = (size_t)min(u, B - 1) * P + ic;
+            shq[u] = k11_cam_load_sh(o, radii, clamped, dL_drgb, gstride);
+            geoq[u] = k11_cam_load_geo(o, radii, dL_dmeans2D, dL_dconic_opacity, gstride);
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (staged) {
+    if constexpr (LIST) {
+        __syncthreads();  // the row table is complete
+        sa_rest_stage_in(s_rest, s_rows, f_rest, nrows * REST_W);
+        __syncthreads();
+    } else if (staged) {
         rest_stage_commit(s_rest, st, f_rest, P);
         __syncthreads();
     }
     float sp[14], sg[14];  // ADAM: the per-lane parameters / gradients, updated after the stage-out (below)
-    if (i < P) {
+    if (LIST ? (int)threadIdx.x < nrows : i < P) {
     float S[3][3];
     cov3d_unpack(cvr, S);
     // the SH coefficients above the DC term: read from the LDS stage where they are needed (staged), not held in 45
@@ -1285,11 +1402,13 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
     // itself (one loop needed 270 registers and spilled; the sums per camera are unchanged, dmean's order of summation
     // is colour part of all cameras, then geometry part of all cameras).
     for (int bc = 0; bc < B; bc++) {
-        const K11CamSH cin = shq[0];
+        const K11CamSH cin = LIST ? k11_cam_load_sh((size_t)bc * P + ic, radii, clamped, dL_drgb, gstride) : shq[0];
+        if constexpr (!LIST) {
 #pragma unroll
-        for (int u = 0; u + 1 < K11_CAMQ; u++) shq[u] = shq[u + 1];
-        if (bc + K11_CAMQ < B)  // (uniform) the camera K11_CAMQ ahead: in flight while this one is differentiated
-            shq[K11_CAMQ - 1] = k11_cam_load_sh((size_t)(bc + K11_CAMQ) * P + i, radii, clamped, dL_drgb, gstride);
+            for (int u = 0; u + 1 < K11_CAMQ; u++) shq[u] = shq[u + 1];
+            if (bc + K11_CAMQ < B)  // (uniform) the camera K11_CAMQ ahead: in flight while this one is differentiated
+                shq[K11_CAMQ - 1] = k11_cam_load_sh((size_t)(bc + K11_CAMQ) * P + i, radii, clamped, dL_drgb, gstride);
+        }
         if (cin.rad <= 0) continue;
         if (staged) asm volatile("" ::: "memory");  // (keeps the LDS reads of the coefficients inside the loop)
         const float *cp = cams + (size_t)bc * CAM_STRIDE;
@@ -1321,12 +1440,15 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
         for (int k = NC * 3; k < M * 3; k++) rp[k - 3] = 0.f;
     }
     for (int bc = 0; bc < B; bc++) {
-        const K11CamGeo cin = geoq[0];
+        const K11CamGeo cin =
+            LIST ? k11_cam_load_geo((size_t)bc * P + ic, radii, dL_dmeans2D, dL_dconic_opacity, gstride) : geoq[0];
+        if constexpr (!LIST) {
 #pragma unroll
-        for (int u = 0; u + 1 < K11_CAMQ; u++) geoq[u] = geoq[u + 1];
-        if (bc + K11_CAMQ < B)
-            geoq[K11_CAMQ - 1] = k11_cam_load_geo((size_t)(bc + K11_CAMQ) * P + i, radii, dL_dmeans2D, dL_dconic_opacity,
-                                                  gstride);
+            for (int u = 0; u + 1 < K11_CAMQ; u++) geoq[u] = geoq[u + 1];
+            if (bc + K11_CAMQ < B)
+                geoq[K11_CAMQ - 1] = k11_cam_load_geo((size_t)(bc + K11_CAMQ) * P + i, radii, dL_dmeans2D,
+                                                      dL_dconic_opacity, gstride);
+        }
         if (cin.rad <= 0) continue;
         const float *cp = cams + (size_t)bc * CAM_STRIDE;
         const Cam cam = load_cam_packed(cp);
@@ -1386,8 +1508,14 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
             dL_drotation[i] = gq;
         }
     }
-    }  // i < P
-    if (staged) {
+    if constexpr (LIST)
+        sa_adam_small(ad, ic, const_cast<float *>(xyz), const_cast<float *>(scaling), const_cast<float *>(rotation),
+                      const_cast<float *>(f_dc), const_cast<float *>(opacity), sp, sg);
+    }  // the lane has a row
+    if constexpr (LIST) {
+        __syncthreads();
+        sa_rest_adam_out(s_rest, s_rows, const_cast<float *>(f_rest), ad, nrows * REST_W);
+    } else if (staged) {
         __syncthreads();
         if constexpr (ADAM) {
             rest_adam_out(s_rest, const_cast<float *>(f_rest), ad, P);
@@ -1447,7 +1575,7 @@ preprocess_backward_adam_batched_kernel(int P, int B, float *__restrict__ xyz, f
 //             (the list is ascending inside a workgroup's slots; the workgroups' order is the atomics')
 //   update    a grid of fixed size, ceil(P / K11_BLOCK) workgroups; workgroup c takes list[c * K11_BLOCK ...] and leaves
 //             at once when that is past the count it reads from the workspace.  One lane per active row: the row's
-//             arithmetic is preprocess_backward_batched_body's (the same device functions in the same order, so the
+//             arithmetic is preprocess_backward_batched_body's (the same body, instantiated with ListRows, so the
 //             same bits), its _features_rest row and the three arrays' 180 bytes per row move through the LDS stage --
 //             lane e of the workgroup's 45 x K11_BLOCK words reads word e % 45 of row list[e / 45]: consecutive lanes
 //             read consecutive words of a 180-byte row.
@@ -1522,12 +1650,6 @@ sparse_adam_classify_kernel(int P, int B, const int32_t *__restrict__ radii, con
             list[s_base + s_cnt[j * NW + wave] + rank[j]] = (uint32_t)(row0 + (size_t)j * SA_CBLOCK + threadIdx.x);
 }
 
-// word e of the workgroup's K11_BLOCK x 45 stage -> its offset in a [P, 45] array, through the row list in LDS
-__device__ __forceinline__ size_t sa_rest_offset(const uint32_t *__restrict__ s_rows, int e) {
-    const int r = e / REST_W;
-    return (size_t)s_rows[r] * REST_W + (size_t)(e - r * REST_W);
-}
-
 template <int DEG>
 __global__ void __launch_bounds__(K11_BLOCK, K11B_WAVES_PER_EU)
 sparse_adam_update_kernel(int P, int B, float *__restrict__ xyz, float *__restrict__ scaling, float scale_modifier,
@@ -1541,182 +1663,13 @@ sparse_adam_update_kernel(int P, int B, float *__restrict__ xyz, float *__restri
     if (ad_in.skip && *ad_in.skip) return;
     const uint32_t count = min(ws->count, (uint32_t)P);
     if (blockIdx.x == 0 && threadIdx.x == 0 && num_active) *num_active = count;
-    const size_t first = (size_t)blockIdx.x * K11_BLOCK;
-    if (first >= count) return;  // (uniform) past the list: at a tenth of the rows active, nine workgroups of ten
+    if ((size_t)blockIdx.x * K11_BLOCK >= count) return;  // (uniform) past the list: at a tenth of the rows active, nine
+                                                          // workgroups of ten
     const K11Adam ad = k11_adam_resolve(ad_in);
-    constexpr int NC = (DEG + 1) * (DEG + 1);
-    constexpr int UN = 5;  // words per lane in flight in the stage's copies: 45 = 9 x 5
-    __shared__ float s_rest[K11_BLOCK * REST_W];
-    __shared__ uint32_t s_rows[K11_BLOCK];
-    const int rows = (int)min((size_t)K11_BLOCK, (size_t)count - first);
-    const int nw = rows * REST_W;
-    const bool live = (int)threadIdx.x < rows;
-    // (clamped slot: lanes past the end of the list load the last row's inputs and compute nothing)
-    const uint32_t irow = list[first + min((int)threadIdx.x, rows - 1)];
-    s_rows[threadIdx.x] = irow;
-    const size_t ic = irow;
-    const float p[3] = {xyz[3 * ic], xyz[3 * ic + 1], xyz[3 * ic + 2]};
-    float cvr[6];
-#pragma unroll
-    for (int e = 0; e < 6; e++) cvr[e] = cov3D[6 * ic + e];
-    const float dc[3] = {f_dc[3 * ic], f_dc[3 * ic + 1], f_dc[3 * ic + 2]};
-    const float oraw = opacity[ic];
-    const float4 qraw = *reinterpret_cast<const float4 *>(rotation + 4 * ic);
-    const float scraw[3] = {scaling[3 * ic], scaling[3 * ic + 1], scaling[3 * ic + 2]};
-    __syncthreads();
-    // ---- the rows' SH coefficients above DC into the stage
-    for (int k0 = 0; k0 < REST_W; k0 += UN) {
-        float v[UN];
-#pragma unroll
-        for (int u = 0; u < UN; u++)
-            v[u] = f_rest[sa_rest_offset(s_rows, min((k0 + u) * K11_BLOCK + (int)threadIdx.x, nw - 1))];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < UN; u++) {
-            const int e = (k0 + u) * K11_BLOCK + (int)threadIdx.x;
-            if (e < nw) s_rest[e] = v[u];
-        }
-    }
-    __syncthreads();
-    if (live) {
-        float sp[14], sg[14];
-        float S[3][3];
-        cov3d_unpack(cvr, S);
-        const float *const shl = s_rest + threadIdx.x * REST_W;
-        float sh[NC * 3];
-        sh[0] = dc[0];
-        sh[1] = dc[1];
-        sh[2] = dc[2];
-        float dmean[3] = {0.f, 0.f, 0.f};
-        float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float dsh[NC * 3];
-#pragma unroll
-        for (int k = 0; k < NC * 3; k++) dsh[k] = 0.f;
-        float dop = 0.f;
-        // colour part of all cameras, then geometry part of all cameras: the batched body's order of summation
-        for (int bc = 0; bc < B; bc++) {
-            const size_t o = (size_t)bc * P + ic;
-            const K11CamSH cin = k11_cam_load_sh(o, radii, clamped, dL_drgb, gstride);
-            if (cin.rad <= 0) continue;
-            asm volatile("" ::: "memory");  // (keeps the LDS reads of the coefficients inside the loop)
-            const float *cp = cams + (size_t)bc * CAM_STRIDE;
-            const float camc[3] = {cp[32], cp[33], cp[34]};
-            const float g3[3] = {cin.cl[0] ? 0.f : cin.grgb[0], cin.cl[1] ? 0.f : cin.grgb[1],
-                                 cin.cl[2] ? 0.f : cin.grgb[2]};
-            float dm[3];
-            viewdir_backward<DEG>(camc, p, ShStagedOrRegs{true, shl, sh}, g3, DshAdd{dsh}, dm);
-            dmean[0] += dm[0];
-            dmean[1] += dm[1];
-            dmean[2] += dm[2];
-        }
-#pragma unroll
-        for (int e = 0; e < 3; e++) {
-            sp[10 + e] = sh[e];
-            sg[10 + e] = dsh[e];
-        }
-        {
-            float *rp = s_rest + threadIdx.x * REST_W;  // the row's own words: its gradient replaces its coefficients
-#pragma unroll
-            for (int k = 3; k < NC * 3; k++) rp[k - 3] = dsh[k];
-            for (int k = NC * 3; k < 16 * 3; k++) rp[k - 3] = 0.f;
-        }
-        for (int bc = 0; bc < B; bc++) {
-            const size_t o = (size_t)bc * P + ic;
-            const K11CamGeo cin = k11_cam_load_geo(o, radii, dL_dmeans2D, dL_dconic_opacity, gstride);
-            if (cin.rad <= 0) continue;
-            const float *cp = cams + (size_t)bc * CAM_STRIDE;
-            const Cam cam = load_cam_packed(cp);
-            const float tanfovx = cp[35], tanfovy = cp[36];
-            const float fx = W / (2.0f * tanfovx), fy = H / (2.0f * tanfovy);
-            const float4 gco = cin.gco;
-            const float gA = gco.x, gB = gco.y, gC = gco.z;
-            dop += gco.w;
-            const Cov2DGrad cg = cov2d_backward(cam.v, fx, fy, tanfovx, tanfovy, p, S, gA, gB, gC);
-            if (cg.live) {
-#pragma unroll
-                for (int e = 0; e < 6; e++) dcov[e] += cg.dcov[e];
-            }
-#pragma unroll
-            for (int k = 0; k < 3; k++) dmean[k] += cg.dmean[k];
-            float dm[3];
-            means2d_to_mean(cam.p, p, cin.g2, dm);
-#pragma unroll
-            for (int k = 0; k < 3; k++) dmean[k] += dm[k];
-        }
-#pragma unroll
-        for (int e = 0; e < 3; e++) {
-            sp[e] = p[e];
-            sg[e] = dmean[e];
-        }
-        {
-            const float so = sigmoidf(oraw);
-            sp[13] = oraw;
-            sg[13] = dop * so * (1.0f - so);
-        }
-        {
-            float gsc[3];
-            float4 gq;
-            cov3d_backward<true>(qraw, scraw, scale_modifier, dcov, gsc, gq);
-#pragma unroll
-            for (int e = 0; e < 3; e++) {
-                sp[3 + e] = scraw[e];
-                sg[3 + e] = gsc[e];
-            }
-            sp[6] = qraw.x; sp[7] = qraw.y; sp[8] = qraw.z; sp[9] = qraw.w;
-            sg[6] = gq.x; sg[7] = gq.y; sg[8] = gq.z; sg[9] = gq.w;
-        }
-        // ---- the 14 per-lane values: a gathered row's moments are 12 / 16 / 4 bytes here and there, read by the lane
-        constexpr int T[14] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 5};
-        constexpr int KK[14] = {3, 3, 3, 3, 3, 3, 4, 4, 4, 4, 3, 3, 3, 1};
-        constexpr int C[14] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 0};
-        float *const base[6] = {xyz, scaling, rotation, f_dc, nullptr, opacity};
-        float m[14], v[14];
-#pragma unroll
-        for (int e = 0; e < 14; e++) {
-            m[e] = ad.m[T[e]][ic * KK[e] + C[e]];
-            v[e] = ad.v[T[e]][ic * KK[e] + C[e]];
-        }
-#pragma unroll
-        for (int e = 0; e < 14; e++) {
-            const int t = T[e];
-            float pe = sp[e];
-            gsr_adam1(pe, __fmul_rn(sg[e], ad.grad_scale), m[e], v[e], ad.lr_c[t], ad.b1[t], ad.b2[t], ad.omb1[t],
-                      ad.omb2[t], ad.inv_sqrt_bc2[t], ad.eps[t]);
-            base[t][ic * KK[e] + C[e]] = pe;
-            ad.m[t][ic * KK[e] + C[e]] = m[e];
-            ad.v[t][ic * KK[e] + C[e]] = v[e];
-        }
-    }
-    __syncthreads();
-    // ---- _features_rest: gradient from the stage, parameter and moments gathered in the stage's order
-    {
-        constexpr int t = 4;
-        float *const mr = ad.m[t], *const vr = ad.v[t];
-        const float gs = ad.grad_scale, lr_c = ad.lr_c[t], b1 = ad.b1[t], b2 = ad.b2[t], omb1 = ad.omb1[t],
-                    omb2 = ad.omb2[t], isb = ad.inv_sqrt_bc2[t], eps = ad.eps[t];
-        for (int k0 = 0; k0 < REST_W; k0 += UN) {
-            size_t off[UN];
-            float pn[UN], mn[UN], vn[UN];
-#pragma unroll
-            for (int u = 0; u < UN; u++) {
-                off[u] = sa_rest_offset(s_rows, min((k0 + u) * K11_BLOCK + (int)threadIdx.x, nw - 1));
-                pn[u] = f_rest[off[u]];
-                mn[u] = mr[off[u]];
-                vn[u] = vr[off[u]];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < UN; u++) {
-                const int e = (k0 + u) * K11_BLOCK + (int)threadIdx.x;
-                if (e < nw) {
-                    gsr_adam1(pn[u], __fmul_rn(s_rest[e], gs), mn[u], vn[u], lr_c, b1, b2, omb1, omb2, isb, eps);
-                    f_rest[off[u]] = pn[u];
-                    mr[off[u]] = mn[u];
-                    vr[off[u]] = vn[u];
-                }
-            }
-        }
-    }
+    preprocess_backward_batched_body<DEG, true>(P, B, 16, xyz, scaling, scale_modifier, rotation, f_dc, f_rest, opacity,
+                                                cams, W, H, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity,
+                                                dL_drgb, gstride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                ad, ListRows{list, count});
 }
 
 // ------------------------------------------------------------------- K11c: camera (pose) gradients
@@ -2049,6 +2002,36 @@ extern "C" int gsr_preprocess_backward_raw_batched(int P, int B, int sh_degree, 
     return 0;
 }
 
+// What the fused entry points below share once P > 0: the null checks of the arguments all of them take (the thirteen
+// device arrays of K11, then the tables), and the kernels' K11Adam from the host tables (lrs .. steps as in gsr_adam_step_multi; with dyn_dev the step-dependent factors
+// come from the device block and lrs / steps are not read).  -> true: GSR_EINVAL.
+static bool k11_adam_fill(K11Adam &ad, std::initializer_list<const void *> device_arrays, float *const *exp_avgs,
+                          float *const *exp_avg_sqs, const double *lrs, const double *beta1s, const double *beta2s,
+                          const double *epss, const int64_t *steps, float grad_scale, const float *dyn_dev,
+                          const uint32_t *skip_flag_dev) {
+    for (const void *a : device_arrays)
+        if (!a) return true;
+    if (!exp_avgs || !exp_avg_sqs || !beta1s || !beta2s || !epss || (!dyn_dev && (!lrs || !steps))) return true;
+    ad.dyn = dyn_dev;
+    ad.skip = skip_flag_dev;
+    ad.grad_scale = grad_scale;
+    for (int t = 0; t < 6; t++) {
+        if (!exp_avgs[t] || !exp_avg_sqs[t] || (!dyn_dev && steps[t] < 1)) return true;
+        const double bc1 = dyn_dev ? 1.0 : 1.0 - pow(beta1s[t], (double)steps[t]);
+        const double bc2 = dyn_dev ? 1.0 : 1.0 - pow(beta2s[t], (double)steps[t]);
+        ad.m[t] = exp_avgs[t];
+        ad.v[t] = exp_avg_sqs[t];
+        ad.lr_c[t] = dyn_dev ? 0.f : (float)(lrs[t] / bc1);
+        ad.b1[t] = (float)beta1s[t];
+        ad.b2[t] = (float)beta2s[t];
+        ad.omb1[t] = (float)(1.0 - beta1s[t]);
+        ad.omb2[t] = (float)(1.0 - beta2s[t]);
+        ad.inv_sqrt_bc2[t] = (float)(1.0 / sqrt(bc2));
+        ad.eps[t] = (float)epss[t];
+    }
+    return false;
+}
+
 // K11 for a batch of cameras fused with the optimizer step of the six tensors it differentiates (see K11Adam):
 // xyz .. opacity are read AND updated in place, exp_avgs / exp_avg_sqs are the moments in the tensor order
 // xyz, scaling, rotation, features_dc, features_rest, opacity; lrs .. steps as in gsr_adam_step_multi.  tanfov0: HOST
@@ -2082,31 +2065,14 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_dyn(
     if (P < 0 || B < 1 || sh_degree < 0 || sh_degree > 3 || sh_coeffs != 16 || width <= 0 || height <= 0)
         return GSR_EINVAL;  // the fused step needs the LDS stage of a 16-coefficient model
     if (P == 0) return 0;
-    if (!xyz || !scaling || !rotation || !features_dc || !features_rest || !opacity || !cams || !radii || !cov3D ||
-        !clamped || !dL_dmeans2D || !dL_dconic_opacity || !dL_drgb || !exp_avgs || !exp_avg_sqs || !beta1s ||
-        !beta2s || !epss || (!dyn_dev && (!lrs || !steps)))
-        return GSR_EINVAL;
     K11Adam ad{};
-    ad.dyn = dyn_dev;
-    ad.skip = skip_flag_dev;
-    for (int t = 0; t < 6; t++) {
-        if (!exp_avgs[t] || !exp_avg_sqs[t] || (!dyn_dev && steps[t] < 1)) return GSR_EINVAL;
-        const double bc1 = dyn_dev ? 1.0 : 1.0 - pow(beta1s[t], (double)steps[t]);
-        const double bc2 = dyn_dev ? 1.0 : 1.0 - pow(beta2s[t], (double)steps[t]);
-        ad.m[t] = exp_avgs[t];
-        ad.v[t] = exp_avg_sqs[t];
-        ad.lr_c[t] = dyn_dev ? 0.f : (float)(lrs[t] / bc1);
-        ad.b1[t] = (float)beta1s[t];
-        ad.b2[t] = (float)beta2s[t];
-        ad.omb1[t] = (float)(1.0 - beta1s[t]);
-        ad.omb2[t] = (float)(1.0 - beta2s[t]);
-        ad.inv_sqrt_bc2[t] = (float)(1.0 / sqrt(bc2));
-        ad.eps[t] = (float)epss[t];
-    }
+    if (k11_adam_fill(ad, {xyz, scaling, rotation, features_dc, features_rest, opacity, cams, radii, cov3D, clamped,
+                           dL_dmeans2D, dL_dconic_opacity, dL_drgb},
+                      exp_avgs, exp_avg_sqs, lrs, beta1s, beta2s, epss, steps, grad_scale, dyn_dev, skip_flag_dev))
+        return GSR_EINVAL;
     uintptr_t al = (uintptr_t)features_rest | (uintptr_t)rotation;
     for (int t = 0; t < 6; t++) al |= (uintptr_t)ad.m[t] | (uintptr_t)ad.v[t];
     if (al & 15) return GSR_EINVAL;  // 16-byte accesses on the moments and the _features_rest block
-    ad.grad_scale = grad_scale;
     const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
     if (B == 1 && tanfov0) {  // one camera: the leaner kernel without accumulators
         GSR_DISPATCH_DEG(sh_degree,
@@ -2144,28 +2110,12 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_sparse(
         grad_row_stride < 0 || (grad_row_stride != 0 && grad_row_stride < 9))
         return GSR_EINVAL;
     if (P == 0) return 0;
-    if (!xyz || !scaling || !rotation || !features_dc || !features_rest || !opacity || !cams || !radii || !cov3D ||
-        !clamped || !dL_dmeans2D || !dL_dconic_opacity || !dL_drgb || !exp_avgs || !exp_avg_sqs || !beta1s ||
-        !beta2s || !epss || (!dyn_dev && (!lrs || !steps)) || !workspace)
-        return GSR_EINVAL;
+    if (!workspace) return GSR_EINVAL;
     K11Adam ad{};
-    ad.dyn = dyn_dev;
-    ad.skip = skip_flag_dev;
-    for (int t = 0; t < 6; t++) {
-        if (!exp_avgs[t] || !exp_avg_sqs[t] || (!dyn_dev && steps[t] < 1)) return GSR_EINVAL;
-        const double bc1 = dyn_dev ? 1.0 : 1.0 - pow(beta1s[t], (double)steps[t]);
-        const double bc2 = dyn_dev ? 1.0 : 1.0 - pow(beta2s[t], (double)steps[t]);
-        ad.m[t] = exp_avgs[t];
-        ad.v[t] = exp_avg_sqs[t];
-        ad.lr_c[t] = dyn_dev ? 0.f : (float)(lrs[t] / bc1);
-        ad.b1[t] = (float)beta1s[t];
-        ad.b2[t] = (float)beta2s[t];
-        ad.omb1[t] = (float)(1.0 - beta1s[t]);
-        ad.omb2[t] = (float)(1.0 - beta2s[t]);
-        ad.inv_sqrt_bc2[t] = (float)(1.0 / sqrt(bc2));
-        ad.eps[t] = (float)epss[t];
-    }
-    ad.grad_scale = grad_scale;
+    if (k11_adam_fill(ad, {xyz, scaling, rotation, features_dc, features_rest, opacity, cams, radii, cov3D, clamped,
+                           dL_dmeans2D, dL_dconic_opacity, dL_drgb},
+                      exp_avgs, exp_avg_sqs, lrs, beta1s, beta2s, epss, steps, grad_scale, dyn_dev, skip_flag_dev))
+        return GSR_EINVAL;
     if ((uintptr_t)rotation & 15) return GSR_EINVAL;  // the quaternion is one 16-byte load
     if (grad_row_stride == 0 && (((uintptr_t)dL_dmeans2D & 7) || ((uintptr_t)dL_dconic_opacity & 15)))
         return GSR_EINVAL;  // dense gradients are read with 8- / 16-byte loads

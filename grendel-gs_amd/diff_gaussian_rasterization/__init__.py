@@ -609,6 +609,14 @@ class PendingProjectionBackward:
         tf = (ctypes.c_float * 2)(float(self.tanfov0[0]), float(self.tanfov0[1])) \
             if (B == 1 and self.tanfov0 is not None) else None
         cap_ctx = _CAPTURE[0]
+        # captured launch: lr / bias corrections come from the capture's device block at execution time, and the launch
+        # is a no-op when a capacity check of the same replay has raised the flag word
+        dyn, flag = (_ptr(cap_ctx.dyn), _ptr(cap_ctx.flag)) if cap_ctx is not None else (None, None)
+        args = [P, B, deg, M, _ptr(xyz), _ptr(scaling), smod, _ptr(rotation), _ptr(f_dc), _ptr(f_rest), _ptr(opacity),
+                _ptr(self.cams), W, H, _ptr(self.radii), _ptr(self.cov3D), _ptr(self.clamped), _ptr(self.g_means2D),
+                _ptr(self.g_conic_opacity), _ptr(self.g_rgb), self.gstride, tabs[1], tabs[2],
+                None if cap_ctx is not None else D(*lrs), tabs[3], tabs[4], tabs[5],
+                None if cap_ctx is not None else I64(*steps), float(grad_scale)]
         if sparse:
             if cache is None:
                 cache = {}
@@ -619,35 +627,16 @@ class PendingProjectionBackward:
                       torch.zeros(1, dtype=torch.int32, device=xyz.device))
                 cache["sparse_ws"] = ws
                 cache["num_active"] = ws[2]
-            dyn, flag = (_ptr(cap_ctx.dyn), _ptr(cap_ctx.flag)) if cap_ctx is not None else (None, None)
-            with _on(xyz.device), (kernel_timer.range("preprocess_backward_adam_sparse", N=P, B=B, M=M)
-                                   if cap_ctx is None else _NULL_RANGE):
-                check(lib.gsr_preprocess_backward_adam_raw_batched_sparse(
-                    P, B, deg, M, _ptr(xyz), _ptr(scaling), smod, _ptr(rotation), _ptr(f_dc), _ptr(f_rest),
-                    _ptr(opacity), _ptr(self.cams), W, H, _ptr(self.radii), _ptr(self.cov3D), _ptr(self.clamped),
-                    _ptr(self.g_means2D), _ptr(self.g_conic_opacity), _ptr(self.g_rgb), self.gstride, tabs[1], tabs[2],
-                    None if cap_ctx is not None else D(*lrs), tabs[3], tabs[4], tabs[5],
-                    None if cap_ctx is not None else I64(*steps), float(grad_scale), dyn, flag, _ptr(ws[1]),
-                    ws[1].numel() * 8, None, _ptr(ws[2]), _stream()),
-                    "gsr_preprocess_backward_adam_raw_batched_sparse")
-            return
-        if cap_ctx is not None:
-            # captured launch: lr / bias corrections come from the capture's device block at execution time, and the
-            # launch is a no-op when a capacity check of the same replay has raised the flag word
-            with _on(xyz.device):
-                check(lib.gsr_preprocess_backward_adam_raw_batched_dyn(
-                    P, B, deg, M, _ptr(xyz), _ptr(scaling), smod, _ptr(rotation), _ptr(f_dc), _ptr(f_rest),
-                    _ptr(opacity), _ptr(self.cams), W, H, _ptr(self.radii), _ptr(self.cov3D), _ptr(self.clamped),
-                    _ptr(self.g_means2D), _ptr(self.g_conic_opacity), _ptr(self.g_rgb), self.gstride, tabs[1], tabs[2],
-                    None, tabs[3], tabs[4], tabs[5], None, float(grad_scale), tf, _ptr(cap_ctx.dyn), _ptr(cap_ctx.flag),
-                    _stream()), "gsr_preprocess_backward_adam_raw_batched_dyn")
-            return
-        with _on(xyz.device), kernel_timer.range("preprocess_backward_adam", N=P, B=B, M=M):
-            check(lib.gsr_preprocess_backward_adam_raw_batched(
-                P, B, deg, M, _ptr(xyz), _ptr(scaling), smod, _ptr(rotation), _ptr(f_dc), _ptr(f_rest), _ptr(opacity),
-                _ptr(self.cams), W, H, _ptr(self.radii), _ptr(self.cov3D), _ptr(self.clamped), _ptr(self.g_means2D),
-                _ptr(self.g_conic_opacity), _ptr(self.g_rgb), self.gstride, tabs[1], tabs[2], D(*lrs), tabs[3], tabs[4],
-                tabs[5], I64(*steps), float(grad_scale), tf, _stream()), "gsr_preprocess_backward_adam_raw_batched")
+            name, timed = "gsr_preprocess_backward_adam_raw_batched_sparse", "preprocess_backward_adam_sparse"
+            args += [dyn, flag, _ptr(ws[1]), ws[1].numel() * 8, None, _ptr(ws[2])]
+        elif cap_ctx is not None:
+            name, timed = "gsr_preprocess_backward_adam_raw_batched_dyn", None  # (never timed: captured)
+            args += [tf, dyn, flag]
+        else:
+            name, timed = "gsr_preprocess_backward_adam_raw_batched", "preprocess_backward_adam"
+            args += [tf]
+        with _on(xyz.device), (kernel_timer.range(timed, N=P, B=B, M=M) if cap_ctx is None else _NULL_RANGE):
+            check(getattr(lib, name)(*args, _stream()), name)
 
 
 def _launch_k11(params, cams, radii, cov3D, clamped, g_means2D, g_conic_opacity, g_rgb, gstride, meta, tanfov0,

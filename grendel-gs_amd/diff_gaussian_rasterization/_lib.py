@@ -12,6 +12,12 @@ LIB_PATH = os.environ.get("GSRASTER_LIB") or os.path.join(_HERE, "libgsraster.so
 c_int, c_float, c_void_p, c_size_t, c_int64 = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
                                                 ctypes.c_int64)
 
+# what the three K11 + Adam entry points take in front of their own tails: P, B, sh_degree, sh_coeffs, xyz, scaling,
+# scale_modifier, rotation .. cams, width, height, radii .. dL_drgb, grad_row_stride (K11's 21 arguments), then
+# exp_avgs .. steps (seven host tables) and grad_scale
+_K11_ADAM_PREFIX = ([c_int] * 4 + [c_void_p, c_void_p, c_float] + [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 6 +
+                    [c_int] + [c_void_p] * 7 + [c_float])
+
 # name -> (restype, argtypes); must list every function of include/gsraster.h (tests/test_abi_cpu.py checks)
 SIGNATURES = {
     "gsr_error_string": (ctypes.c_char_p, [c_int]),
@@ -88,18 +94,12 @@ SIGNATURES = {
     "gsr_preprocess_backward_raw_batched": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float] +
                                             [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 6 + [c_int] +
                                             [c_void_p] * 7),
-    "gsr_preprocess_backward_adam_raw_batched": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float] +
-                                                 [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 6 + [c_int] +
-                                                 [c_void_p] * 7 + [c_float, c_void_p, c_void_p]),
-    "gsr_preprocess_backward_adam_raw_batched_dyn": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float] +
-                                                     [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 6 + [c_int] +
-                                                     [c_void_p] * 7 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_preprocess_backward_adam_raw_batched": (c_int, _K11_ADAM_PREFIX + [c_void_p, c_void_p]),
+    "gsr_preprocess_backward_adam_raw_batched_dyn": (c_int, _K11_ADAM_PREFIX + [c_void_p] * 4),
     "gsr_sparse_step_workspace_bytes": (c_size_t, [c_int]),
-    "gsr_preprocess_backward_adam_raw_batched_sparse": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                                                c_float] + [c_void_p] * 5 + [c_int, c_int] +
-                                                        [c_void_p] * 6 + [c_int] + [c_void_p] * 7 +
-                                                        [c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
-                                                         c_void_p, c_void_p]),
+    "gsr_preprocess_backward_adam_raw_batched_sparse": (c_int, _K11_ADAM_PREFIX + [c_void_p, c_void_p, c_void_p,
+                                                                                    c_size_t, c_void_p, c_void_p,
+                                                                                    c_void_p]),
     "gsr_preprocess_backward_cams_bytes": (c_size_t, [c_int, c_int]),
     "gsr_preprocess_backward_cams": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                              c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_size_t,

@@ -1,6 +1,7 @@
 """CPU: the bookkeeping of FusedAdam(fuse_backward=True) -- which backward passes are deferred, what step(),
 zero_grad(), a second backward and a replaced parameter do with a pending projection backward -- with a stand-in for
-the operator's PendingProjectionBackward (the kernels themselves: tests/test_gpu_loss_and_step.py)."""
+the operator's PendingProjectionBackward (the kernels themselves: tests/test_gpu_loss_and_step.py); and the host-side
+argument checks of the two dense fused entry points, which answer without a device."""
 import pytest
 import torch
 
@@ -214,3 +215,68 @@ def test_operator_hands_the_projection_backward_to_the_optimizer(fake_library, B
     backward_once()
     assert [c[0] for c in calls].count(plain) == 2 and opt._pending is None and opt.materialized_steps == 2
     assert all(p.grad is not None for p in raw)
+
+
+GSR_EINVAL = -1
+
+
+def _dense_args(dyn_entry, **kw):
+    """a well-formed argument list of gsr_preprocess_backward_adam_raw_batched (dyn_entry: of ..._dyn) whose device
+    pointers are made-up addresses: the checks must not dereference them"""
+    import ctypes
+
+    VP, D6, I64 = ctypes.c_void_p * 6, ctypes.c_double * 6, ctypes.c_int64 * 6
+    dev = lambda k: 0x7000_0000 + 0x10000 * k  # 16-byte aligned, never touched
+    a = dict(P=1000, B=2, deg=3, M=16, xyz=dev(1), scaling=dev(2), smod=1.0, rotation=dev(3), f_dc=dev(4), f_rest=dev(5),
+             opacity=dev(6), cams=dev(7), W=320, H=208, radii=dev(8), cov3D=dev(9), clamped=dev(10), g2=dev(11),
+             gco=dev(12), grgb=dev(13), gstride=9, m=VP(*[dev(20 + t) for t in range(6)]),
+             v=VP(*[dev(30 + t) for t in range(6)]), lrs=D6(*[1e-3] * 6), b1=D6(*[0.9] * 6), b2=D6(*[0.999] * 6),
+             eps=D6(*[1e-15] * 6), steps=I64(*[2] * 6), grad_scale=1.0, tanfov0=None)
+    if dyn_entry:
+        a.update(dyn=None, skip=None)
+    a["stream"] = None
+    a.update(kw)
+    return list(a.values())
+
+
+@pytest.mark.parametrize("dyn_entry", [False, True])
+def test_dense_fused_entry_validation_codes_are_returned_without_a_device(dyn_entry):
+    """every case returns before any launch: the host-side argument checks of the two dense fused entry points"""
+    import ctypes
+
+    from diff_gaussian_rasterization import _lib
+
+    f = (_lib.lib.gsr_preprocess_backward_adam_raw_batched_dyn if dyn_entry
+         else _lib.lib.gsr_preprocess_backward_adam_raw_batched)
+    args = lambda **kw: _dense_args(dyn_entry, **kw)
+    VP, I64 = ctypes.c_void_p * 6, ctypes.c_int64 * 6
+    dev = lambda k: 0x7000_0000 + 0x10000 * k
+    for name in ("xyz", "scaling", "rotation", "f_dc", "f_rest", "opacity", "cams", "radii", "cov3D", "clamped", "g2",
+                 "gco", "grgb", "m", "v", "b1", "b2", "eps", "lrs", "steps"):
+        assert f(*args(**{name: None})) == GSR_EINVAL, name
+    for t in range(6):  # a null moment inside either table
+        for tab, base in (("m", 20), ("v", 30)):
+            ptrs = [dev(base + k) for k in range(6)]
+            ptrs[t] = None
+            assert f(*args(**{tab: VP(*ptrs)})) == GSR_EINVAL, (tab, t)
+    assert f(*args(M=4)) == GSR_EINVAL and f(*args(M=15)) == GSR_EINVAL and f(*args(M=17)) == GSR_EINVAL
+    assert f(*args(P=-1)) == GSR_EINVAL and f(*args(B=0)) == GSR_EINVAL and f(*args(W=-320)) == GSR_EINVAL
+    assert f(*args(deg=4)) == GSR_EINVAL
+    for t in range(6):  # steps[t] = 0 without dyn_dev
+        steps = [2] * 6
+        steps[t] = 0
+        assert f(*args(steps=I64(*steps))) == GSR_EINVAL, t
+    # 16-byte accesses: _features_rest, the quaternions and the twelve moment arrays
+    for off in (4, 8, 12):
+        assert f(*args(f_rest=dev(5) + off)) == GSR_EINVAL and f(*args(rotation=dev(3) + off)) == GSR_EINVAL
+    for t in range(6):
+        for tab, base in (("m", 20), ("v", 30)):
+            ptrs = [dev(base + k) for k in range(6)]
+            ptrs[t] += 4
+            assert f(*args(**{tab: VP(*ptrs)})) == GSR_EINVAL, (tab, t)
+    if dyn_entry:  # with dyn_dev lrs / steps may be null, the other checks hold
+        assert f(*args(dyn=dev(41), lrs=None, steps=None, f_rest=dev(5) + 4)) == GSR_EINVAL
+        assert f(*args(dyn=dev(41), lrs=None, steps=None, b1=None)) == GSR_EINVAL
+        assert f(*args(dyn=dev(41), m=VP(dev(20), None, dev(22), dev(23), dev(24), dev(25)))) == GSR_EINVAL
+    assert f(*args(P=0)) == 0
+    assert f(*args(P=0, xyz=None, f_rest=None, m=None, v=None, lrs=None, steps=None)) == 0

@@ -205,7 +205,10 @@ def _assert_shares(active, N):
 
 # ------------------------------------------------------------------------------------------------ 1. bit equality
 @pytest.mark.parametrize("gstride", [0, 9])
-@pytest.mark.parametrize("B,deg,N", [(1, 3, 4099), (3, 3, 4099), (2, 0, 777), (1, 1, 129), (2, 3, 63), (1, 3, 1)])
+@pytest.mark.parametrize("B,deg,N", [(1, 3, 4099), (3, 3, 4099), (2, 0, 777), (1, 1, 129), (2, 3, 63), (1, 3, 1),
+                                     # more cameras than the update's camera queue holds (its refill runs more than once
+                                     # per loop), the list ending in a ragged only / last workgroup
+                                     (5, 3, 300), (4, 1, 129)])
 def test_sparse_step_equals_the_dense_pair_on_active_rows(device, B, deg, N, gstride):
     c, (active, want, dense, _) = _case_expected(B, deg, N, device)
     _assert_shares(active, N)
@@ -259,18 +262,37 @@ def test_edge_words_classify_as_defined(device):
 
 
 # ------------------------------------------------------------------------------------------------ 3. all / none
+def _all_active_case(B, deg, N, device, count=None):
+    """the rows of an N-row scene that some camera sees (the first `count` of them), every gradient word non-zero"""
+    full = _Case(B, deg, N, str(device), zero_rows=False)
+    keep = torch.nonzero((full.radii > 0).any(0)).flatten()[:count]
+    full.N = int(keep.numel())
+    full.params = [t[keep].contiguous() for t in full.params]
+    full.ms, full.vs = [t[keep].contiguous() for t in full.ms], [t[keep].contiguous() for t in full.vs]
+    full.rec = full.rec.reshape(B, N, 9)[:, keep].reshape(B * full.N, 9).contiguous()
+    full.radii, full.cov3D, full.clamped = _forward(full.params, full.packed, deg)
+    return full
+
+
+@pytest.mark.parametrize("gstride", [0, 9])
+def test_list_of_exactly_two_full_workgroups(device, gstride):
+    """all 256 rows of a 256-row scene active: the list fills the grid's two workgroups exactly (no clamped lane)"""
+    B, deg = 3, 3
+    full = _all_active_case(B, deg, 500, device, count=256)
+    assert full.N == 256
+    active, want, dense, _ = full.expected()
+    assert bool(active.all())
+    code, got, act, num = full.run(gstride)
+    assert code == 0 and int(num) == 256 and bool(act.bool().all())
+    _assert_state(got, dense, f"256 of 256 rows active stride={gstride}")
+
+
 def test_all_rows_active_and_no_row_active(device):
     B, deg, N = 2, 3, 777
     c, _ = _case(B, deg, N, str(device))
     # all rows active: a scene in which every row is seen by camera 0, every gradient word non-zero
-    full = _Case(1, deg, 333, str(device), zero_rows=False)
-    keep = torch.nonzero(full.radii[0] > 0).flatten()
-    assert keep.numel() >= 100
-    full.N = int(keep.numel())
-    full.params = [t[keep].contiguous() for t in full.params]
-    full.ms, full.vs = [t[keep].contiguous() for t in full.ms], [t[keep].contiguous() for t in full.vs]
-    full.rec = full.rec[keep].contiguous()
-    full.radii, full.cov3D, full.clamped = _forward(full.params, full.packed, deg)
+    full = _all_active_case(1, deg, 333, device)
+    assert full.N >= 100
     active, want, dense, _ = full.expected()
     assert bool(active.all())
     code, got, act, num = full.run(9)
