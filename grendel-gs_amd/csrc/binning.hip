@@ -25,6 +25,14 @@
 //
 // All primitives are hand-written for wave64: ballot-based stable multisplit inside a wave,
 // LDS per-wave digit tables, LDS digit-ordered staging for coalesced stores.
+//
+// The kernels of this file are the LOOK-BACK pipeline (nine launches) and the generic tile-id sort.  The same lists come
+// out of K3-K4 as one persistent launch and K5-K7 as another (binning_persist.h: short chains, where launches dominate)
+// and out of the row-major pipeline (binning_rows.h: one pass over the pairs, long chains).  Which of them runs is
+// decided on the host, once per call, in binning_host.h: the prepare step tries the persistent kernel and falls back to
+// the look-back chain; the form of the D-chain is a SortPlan (row-major, else (row, column) keys with the persistent
+// sort kernel in front of the two look-back passes, else generic).  The second half of this file holds one launch
+// function per form and the C entry points.
 #include "common.h"
 
 #include <atomic>
@@ -39,6 +47,7 @@
 #endif
 #include "binning_persist.h"
 #include "binning_rows.h"
+#include "binning_host.h"
 
 namespace {
 
@@ -473,436 +482,338 @@ copy_u32_kernel(long long n, const uint32_t *__restrict__ src, uint32_t *__restr
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) dst[j] = src[j];
 }
-
-struct PrepLayout {
-    size_t tt, kA, vA, kB, vB, offsets, segoff, rects, hull, early, thist, ctrl, total;
-    CtrlLayout C;
-};
-PrepLayout prep_layout(int P, int W, int H) {
-    (void)W; (void)H;
-    PrepLayout L;
-    size_t o = 0;
-    const size_t np = align_up((size_t)(P + 1) * 4);
-    L.tt = o; o += np;      // pairs of each Gaussian (| the rows of its rect << 20 on the (row, column) path)
-    L.segoff = o; o += np;  // exclusive scan of hh[sorted id]: the row segments (round 6, binning_rows.h)
-    L.kA = o; o += np;
-    L.vA = o; o += np;
-    L.kB = o; o += np;
-    L.vB = o; o += np;
-    L.offsets = o; o += np;
-    L.rects = o; o += align_up((size_t)(P + 1) * sizeof(TileRect));
-    L.hull = o; o += 256;  // int32 [2]: the row hull of the mask (written by K3, copied into the range table by the sort)
-    L.early = o; o += 256;  // { u64 sum of tiles_touched (K3's atomics), u32 workgroups that added theirs }: zeroed with ctrl
-    L.thist = o; o += align_up(sizeof(uint32_t) * RADIX_REPLICAS * RADIX_MAX_PASSES * RADIX_DIGITS);  // zeroed with ctrl
-    L.ctrl = o;
-    L.C = ctrl_layout(P, 4, true);
-    o += L.C.total;
-    L.total = o;
-    return L;
-}
-// the persistent pipeline's control block shares the space of the look-back pipeline's (one of the two runs per call)
-int persist_grid_bound_p(int P) {
-    const long long nb = radix_blocks(P);
-    return (int)(nb < PERSIST_MAX_GRID_P ? (nb > 0 ? nb : 1) : PERSIST_MAX_GRID_P);
-}
-int persist_grid_bound_s(int64_t D) {
-    const long long nb = radix_blocks(D);
-    return (int)(nb < PERSIST_MAX_GRID_S ? (nb > 0 ? nb : 1) : PERSIST_MAX_GRID_S);
-}
-PrepLayout prep_layout_full(int P, int W, int H) {
-    PrepLayout L = prep_layout(P, W, H);
-    const size_t need = persist_layout_p(persist_grid_bound_p(P)).total;
-    if (need > L.C.total) L.total += need - L.C.total;
-    return L;
-}
-// Pinned, device-mapped result slots (64 per device, two words each): K4's last workgroup stores the pair count and
-// then the call's sequence tag; the host POLLS the tag (a few microseconds after the store lands) instead of paying a
-// stream synchronise (interrupt + wake-up, ~30-40 us measured) -- everything the host launches after this point is on
-// the critical path of the iteration.  If the tag does not show up within ~2 ms the host falls back to
-// hipStreamSynchronize (which also surfaces a faulted kernel).  A call's ticket is its sequence number; slot =
-// ticket % 64, so up to 64 counts can be outstanding per device (gsr_bin_prepare_async / gsr_bin_count_wait).
-constexpr int TOTAL_SLOTS = 64;
-std::mutex g_total_mutex;  // slot table set-up and ticket numbering only
-uint32_t *g_total_word[64] = {};
-uint32_t g_total_seq = 0;
-int total_slot(uint32_t **host, uint32_t *seq_out) {
-    int dev = 0;
-    GSR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return GSR_EINVAL;
-    std::lock_guard<std::mutex> guard(g_total_mutex);
-    if (!g_total_word[dev]) {
-        void *p = nullptr;
-        GSR_HIP(hipHostMalloc(&p, sizeof(uint32_t) * 2 * TOTAL_SLOTS, hipHostMallocDefault));
-        g_total_word[dev] = reinterpret_cast<uint32_t *>(p);
-        memset(p, 0, sizeof(uint32_t) * 2 * TOTAL_SLOTS);
-    }
-    const uint32_t seq = ++g_total_seq ? g_total_seq : ++g_total_seq;  // never 0
-    *seq_out = seq;
-    *host = g_total_word[dev] + 2 * (seq % TOTAL_SLOTS);
-    return 0;
-}
-int slot_of_ticket(uint32_t seq, uint32_t **host) {
-    int dev = 0;
-    GSR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !g_total_word[dev] || seq == 0) return GSR_EINVAL;
-    *host = g_total_word[dev] + 2 * (seq % TOTAL_SLOTS);
-    return 0;
-}
-int wait_total(hipStream_t stream, uint32_t *host_total, uint32_t seq, uint32_t *total) {
-    volatile uint32_t *w = host_total;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (long spins = 0;; spins++) {
-        if (w[1] == seq) {
-            std::atomic_thread_fence(std::memory_order_acquire);
-            *total = w[0];
-            return 0;
-        }
-        if ((spins & 1023) == 1023 &&
-            std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2))
-            break;
-    }
-    GSR_HIP(hipStreamSynchronize(stream));
-    *total = w[0];
-    return w[1] == seq ? 0 : GSR_EINVAL;
-}
-// (row, column) keys + fused emission (emit_scatter_kernel): frames of <= 256 x 256 tiles; GSR_BINNING=generic
-// forces the tile-id path (kept for larger frames) for A/B measurements and tests
-bool yx_path(int gx, int gy) {
-    const char *e = getenv("GSR_BINNING");
-    if (e && strcmp(e, "generic") == 0) return false;
-    return gx <= RADIX_DIGITS && gy <= RADIX_DIGITS;
-}
-std::atomic<int> g_tie_order{0};  // 0: arrival index (the reference), 1: screen position
-int bits_for(int n) {  // bits needed for the values 0 .. n-1 (at least 1)
-    int b = 1;
-    while ((1 << b) < n) b++;
-    return b;
-}
-int tile_bits(int tiles) {  // bits of the largest key value, the sentinel `tiles`
-    int b = 1;
-    while ((1ll << b) <= tiles) b++;
-    return b;
-}
-}  // namespace
-
-// ----------------------------------------------------------------------------------- K3..K7 API
-extern "C" size_t gsr_bin_prepare_bytes(int P, int width, int height) {
-    if (P < 0 || width <= 0 || height <= 0) return 0;
-    return prep_layout_full(P, width, height).total;
-}
-
-namespace {
-// Exact tile culling (binning_persist.h: gsr_tile_mask).  Its cost is K3's -- per Gaussian and tile row of the rect,
-// +27 us per 10^6 Gaussians at 1080p, +37 us at 4K -- its return the D-sized passes' and the composite kernels'.
-// Measured (profiles/r05_tile_cull.txt): D -9..19 %; K3-K7 327 -> 330 us at c1, 713 -> 694 us at 4K; the training steps
-// 1.206 -> 1.204 ms and 2.811 -> 2.799 ms: the composite kernels skip such pairs with one box test per quadrant anyway.
-// Hence OFF by default; "auto" (frames above GSR_TILE_CULL_TILES tiles, default 16384) is a static rule for scenes whose
-// splats cover many tiles -- not a function of earlier views.
-std::atomic<int> g_tile_cull{-1};  // gsr_set_tile_cull: -1 = environment (GSR_TILE_CULL = 0 | 1 | auto, default 0)
-int tile_cull_on(int tiles) {
-    int mode = g_tile_cull.load(std::memory_order_relaxed);
-    if (mode < 0) {
-        static const int env_mode = [] {
-            const char *e = getenv("GSR_TILE_CULL");
-            if (!e || !*e || strcmp(e, "0") == 0) return 0;
-            return strcmp(e, "auto") == 0 ? 2 : 1;
-        }();
-        mode = env_mode;
-    }
-    if (mode != 2) return mode;
-    static const int min_tiles = [] {
-        const char *e = getenv("GSR_TILE_CULL_TILES");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 ? v : 16384;
-    }();
-    return tiles > min_tiles ? 1 : 0;
-}
-
-// what a gsr_bin_prepare_async call was given: kept per count slot so that gsr_bin_count_wait can repeat the call on
-// the look-back pipeline when the persistent kernel gave up at its first barrier (binning_persist.h)
-struct PrepCall {
-    int P, width, height;
-    const float *means2D, *depths;
-    const int32_t *radii;
-    const float *conic_opacity;
-    const uint8_t *compute_locally;
-    void *prep;
-    hipStream_t stream;
-    bool persistent;
-    void *zero_ptr;     // the control block of the tile sort launched behind this prepare step (16-byte aligned), or null
-    size_t zero_bytes;  // a multiple of 16
-};
-PrepCall g_prep_calls[64][TOTAL_SLOTS];
-
-int persist_effective_mode() {
-    const int o = g_persist_override.load(std::memory_order_relaxed);
-    return o >= 0 ? o : persist_mode();
-}
-
+// ------------------------------------------------------------------------------------------ K3-K4: the prepare step
 // K3-K4 on the look-back pipeline: K3, four one-sweep passes, the offsets scan (six launches)
-int prepare_lookback(const PrepCall &c, uint32_t *ticket) {
+int prepare_lookback(const PrepCall &c, const BinFrame &f, BinDevice &d, uint32_t *ticket) {
     const int P = c.P;
     hipStream_t stream = c.stream;
-    const PrepLayout L = prep_layout(P, c.width, c.height);
-    const int gx = (c.width + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (c.height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    char *base = reinterpret_cast<char *>(c.prep);
-    uint32_t *tt = reinterpret_cast<uint32_t *>(base + L.tt);
-    uint32_t *kA = reinterpret_cast<uint32_t *>(base + L.kA), *vA = reinterpret_cast<uint32_t *>(base + L.vA);
-    uint32_t *kB = reinterpret_cast<uint32_t *>(base + L.kB), *vB = reinterpret_cast<uint32_t *>(base + L.vB);
-    uint32_t *offsets = reinterpret_cast<uint32_t *>(base + L.offsets);
-    TileRect *rects = reinterpret_cast<TileRect *>(base + L.rects);
-    char *ctrl = base + L.ctrl;
-
-    GSR_HIP(hipMemsetAsync(base + L.early, 0, (L.ctrl - L.early) + L.C.total, stream));
+    const PrepLayout L = prep_layout(P);
+    const PrepViews v = views(L, c.prep);
+    GSR_HIP(hipMemsetAsync(v.early, 0, (L.ctrl - L.early) + L.C.total, stream));
     const RadixPlan plan = radix_plan(0, 32);
     uint32_t *host_total = nullptr;
     uint32_t seq = 0;
-    int rc = total_slot(&host_total, &seq);
+    int rc = take_ticket(d, &host_total, &seq);
     if (rc) return rc;
-    uint32_t *tile_hist = yx_path(gx, gy) ? reinterpret_cast<uint32_t *>(base + L.thist) : nullptr;
+    uint32_t *tile_hist = f.yx ? v.thist : nullptr;
     // persistent workgroups (mask hull + LDS tables are per-workgroup set-up)
     const int blocks = gsr_div_up(P, TC_THREADS) < TC_BLOCKS ? gsr_div_up(P, TC_THREADS) : TC_BLOCKS;
-    hipLaunchKernelGGL(touch_count_kernel, dim3(blocks), dim3(TC_THREADS), 0, stream, P, gx, gy,
+    hipLaunchKernelGGL(touch_count_kernel, dim3(blocks), dim3(TC_THREADS), 0, stream, P, f.gx, f.gy,
                        reinterpret_cast<const float2 *>(c.means2D), c.depths, c.radii,
-                       reinterpret_cast<const float4 *>(c.conic_opacity), c.compute_locally, plan, tt, kA, vA, rects,
-                       reinterpret_cast<uint32_t *>(ctrl + L.C.ghist), tile_hist,
-                       reinterpret_cast<int32_t *>(base + L.hull), tile_hist ? tile_cull_on(gx * gy) : 0,
-                       reinterpret_cast<unsigned long long *>(base + L.early), host_total, seq,
-                       reinterpret_cast<uint4 *>(c.zero_ptr), c.zero_bytes / 16);
+                       reinterpret_cast<const float4 *>(c.conic_opacity), c.compute_locally, plan, v.tt, v.kA, v.vA, v.rects,
+                       reinterpret_cast<uint32_t *>(v.ctrl + L.C.ghist), tile_hist, v.hull, f.cull, v.early, host_total,
+                       seq, reinterpret_cast<uint4 *>(c.zero_ptr), c.zero_bytes / 16);
     int in_first = 1;
-    rc = radix_sort_pairs(kA, vA, kB, vB, P, plan, ctrl, L.C, &in_first, stream, nullptr);
+    rc = radix_sort_pairs(v.kA, v.vA, v.kB, v.vB, P, plan, v.ctrl, L.C, &in_first, stream, nullptr);
     if (rc) return rc;
     // 4 passes -> back in (kA, vA); the sorted ids stay in vA for K5
-    uint32_t *sorted_ids = in_first ? vA : vB;
+    uint32_t *sorted_ids = in_first ? v.vA : v.vB;
     if (!in_first) {
         hipLaunchKernelGGL(copy_u32_kernel, dim3(gsr_div_up(P, GSR_ONE_DIM_BLOCK)), dim3(GSR_ONE_DIM_BLOCK), 0, stream,
-                           (long long)P, vB, vA);
-        sorted_ids = vA;
+                           (long long)P, v.vB, v.vA);
+        sorted_ids = v.vA;
     }
     if (g_tie_order.load(std::memory_order_relaxed) == 1)
         hipLaunchKernelGGL(depth_tie_fixup_kernel, dim3(gsr_div_up(P, GSR_ONE_DIM_BLOCK)), dim3(GSR_ONE_DIM_BLOCK), 0,
-                           stream, (long long)P, in_first ? kA : kB, sorted_ids,
+                           stream, (long long)P, in_first ? v.kA : v.kB, sorted_ids,
                            reinterpret_cast<const float2 *>(c.means2D));
     const int nbs = gsr_div_up(P, SCAN_TILE);
-    hipLaunchKernelGGL(scan_gather_lookback_kernel, dim3(nbs), dim3(SCAN_THREADS), 0, stream, tt,
-                       tile_hist ? 1 : 0, sorted_ids, offsets,
-                       reinterpret_cast<uint32_t *>(base + L.segoff), (long long)P,
-                       reinterpret_cast<unsigned long long *>(ctrl + L.C.scan_state),
-                       reinterpret_cast<uint32_t *>(ctrl + L.C.tickets), nbs, (uint32_t *)nullptr, seq,
-                       reinterpret_cast<const unsigned long long *>(base + L.early));
+    hipLaunchKernelGGL(scan_gather_lookback_kernel, dim3(nbs), dim3(SCAN_THREADS), 0, stream, v.tt,
+                       tile_hist ? 1 : 0, sorted_ids, v.offsets, v.segoff, (long long)P,
+                       reinterpret_cast<unsigned long long *>(v.ctrl + L.C.scan_state),
+                       reinterpret_cast<uint32_t *>(v.ctrl + L.C.tickets), nbs, (uint32_t *)nullptr, seq, v.early);
     GSR_LAUNCH_CHECK();
     *ticket = seq;
     return 0;
 }
 
-// GSR_BIN_DEPTH_SORT = lsd (read per call): the depth sort of the persistent prepare kernel as four global LSD passes
-// (A/B measurements, tests); default: one global pass by depth bucket + a workgroup-local sort (binning_persist.h)
-bool depth_buckets_on() {
-    const char *e = getenv("GSR_BIN_DEPTH_SORT");
-    return !(e && strcmp(e, "lsd") == 0);
-}
-
 // K3-K4 as ONE persistent launch (binning_persist.h).  -> 0 launched, 1 not applicable here (use the look-back
 // pipeline), otherwise an error
-int prepare_persistent(const PrepCall &c, uint32_t *ticket) {
+int prepare_persistent(const PrepCall &c, const BinFrame &f, const BinHooks &h, BinDevice &d, uint32_t *ticket) {
     if (!(persist_effective_mode() & PERSIST_P) || g_tie_order.load(std::memory_order_relaxed) != 0) return 1;
-    int dev = 0;
-    GSR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return 1;
-    PersistCaps caps;
-    persist_caps(dev, &caps);
+    persist_caps(d);
+    const int grid_p = lowered(h.grid_p, d.grid_p);
     // tiles of 4096 Gaussians, or of 8192 when that brings the launch down to one tile per workgroup
-    const int max_tpw = env_cap("GSR_BIN_MAX_TPW", PP_MAX_TPW + 1) <= PP_MAX_TPW ? env_cap("GSR_BIN_MAX_TPW", PP_MAX_TPW + 1) : 1;
     long long nb = radix_blocks(c.P);
     int items = 4;
-    if (nb > caps.grid_p && (nb + 1) / 2 <= caps.grid_p) {
+    if (nb > grid_p && (nb + 1) / 2 <= grid_p) {
         items = 8;
         nb = (nb + 1) / 2;
     }
-    const int G = (int)(nb < caps.grid_p ? nb : caps.grid_p);
-    if (G <= 0 || nb > (long long)G * max_tpw) return 1;  // (long sorts are bandwidth-bound: look-back pipeline)
-    const long long admit = persist_admit(dev, c.stream);
+    const int G = (int)(nb < grid_p ? nb : grid_p);
+    if (G <= 0 || nb > (long long)G * h.max_tpw) return 1;  // (long sorts are bandwidth-bound: look-back pipeline)
+    const long long admit = persist_admit(d, c.stream);
     if (admit < 0) return 1;
     const int P = c.P;
-    const PrepLayout L = prep_layout(P, c.width, c.height);
+    const PrepLayout L = prep_layout(P);
+    const PrepViews v = views(L, c.prep);
     const PersistLayoutP PL = persist_layout_p(G);
-    const int gx = (c.width + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (c.height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    char *base = reinterpret_cast<char *>(c.prep);
-    char *ctrl = base + L.ctrl;
-    GSR_HIP(hipMemsetAsync(base + L.early, 0, (L.ctrl - L.early) + PL.zero_bytes, c.stream));
+    GSR_HIP(hipMemsetAsync(v.early, 0, (L.ctrl - L.early) + PL.zero_bytes, c.stream));
     uint32_t *host_total = nullptr;
     uint32_t seq = 0;
-    int rc = total_slot(&host_total, &seq);
+    const int rc = take_ticket(d, &host_total, &seq);
     if (rc) return rc;
     PrepPersistArgs a{};
-    a.P = P; a.gx = gx; a.gy = gy;
+    a.P = P; a.gx = f.gx; a.gy = f.gy;
     a.means2D = reinterpret_cast<const float2 *>(c.means2D);
-    a.depths = c.depths;
-    a.radii = c.radii;
     a.conic_opacity = reinterpret_cast<const float4 *>(c.conic_opacity);
-    a.mask = c.compute_locally;
-    a.tt = reinterpret_cast<uint32_t *>(base + L.tt);
-    a.kA = reinterpret_cast<uint32_t *>(base + L.kA); a.vA = reinterpret_cast<uint32_t *>(base + L.vA);
-    a.kB = reinterpret_cast<uint32_t *>(base + L.kB); a.vB = reinterpret_cast<uint32_t *>(base + L.vB);
-    a.offsets = reinterpret_cast<uint32_t *>(base + L.offsets);
-    a.segoff = reinterpret_cast<uint32_t *>(base + L.segoff);
-    a.rects = reinterpret_cast<TileRect *>(base + L.rects);
-    a.tile_hist = yx_path(gx, gy) ? reinterpret_cast<uint32_t *>(base + L.thist) : nullptr;
-    a.cull = a.tile_hist ? tile_cull_on(gx * gy) : 0;
-    a.hull_out = reinterpret_cast<int32_t *>(base + L.hull);
-    a.early = reinterpret_cast<unsigned long long *>(base + L.early);
+    a.depths = c.depths; a.radii = c.radii; a.mask = c.compute_locally;
+    a.tt = v.tt; a.kA = v.kA; a.vA = v.vA; a.kB = v.kB; a.vB = v.vB;
+    a.offsets = v.offsets; a.segoff = v.segoff; a.rects = v.rects;
+    a.tile_hist = f.yx ? v.thist : nullptr;
+    a.cull = f.cull;
+    a.hull_out = v.hull;
+    a.early = v.early;
     a.zero16 = reinterpret_cast<uint4 *>(c.zero_ptr);
     a.zero16_n = c.zero_bytes / 16;
-    const int ngroups = (G + GB_FAN - 1) / GB_FAN;
-    a.sync.leaf = reinterpret_cast<uint32_t *>(ctrl + PL.sync);
-    a.sync.root = a.sync.leaf + (size_t)ngroups * GB_LEAF_STRIDE;
-    a.sync.flags = a.sync.root + GB_LEAF_STRIDE;
-    a.tstamp = timeline_buffer(0, G);
-    a.grp = reinterpret_cast<uint32_t *>(ctrl + PL.grp);
-    a.cnt = reinterpret_cast<uint32_t *>(ctrl + PL.cnt);
-    a.wtot = reinterpret_cast<unsigned long long *>(ctrl + PL.wtot);
-    a.bins = reinterpret_cast<uint32_t *>(ctrl + PL.bins);
-    a.depth_buckets = depth_buckets_on() ? 1 : 0;
-    a.host_total = host_total;
-    a.seq = seq;
-    a.done_word = g_persist_done[dev];
-    a.done_seq = (uint32_t)admit;
+    a.sync = sync_view(v.ctrl + PL.sync, G);
+    a.tstamp = timeline_buffer(h.timeline, 0, G);
+    a.grp = at<uint32_t>(v.ctrl, PL.grp); a.cnt = at<uint32_t>(v.ctrl, PL.cnt);
+    a.wtot = at<unsigned long long>(v.ctrl, PL.wtot); a.bins = at<uint32_t>(v.ctrl, PL.bins);
+    a.depth_buckets = h.depth_buckets ? 1 : 0;
+    a.host_total = host_total; a.seq = seq;
+    a.done_word = d.done; a.done_seq = (uint32_t)admit;
     a.timeout_ticks = 5000000ull;  // 50 ms of the 100 MHz clock at the first barrier
-    a.force_abort = force_abort_env('p') ? 1 : 0;
+    a.force_abort = h.abort_p ? 1 : 0;
     if (items == 4) hipLaunchKernelGGL(bin_prepare_persist_kernel<4>, dim3(G), dim3(PP_THREADS), 0, c.stream, a);
     else hipLaunchKernelGGL(bin_prepare_persist_kernel<8>, dim3(G), dim3(PP_THREADS), 0, c.stream, a);
     GSR_LAUNCH_CHECK();
     *ticket = seq;
     return 0;
 }
-}  // namespace
 
-namespace {
-int prepare_async_impl(int P, int width, int height, const float *means2D, const float *depths, const int32_t *radii,
-                       const float *conic_opacity, const uint8_t *compute_locally, void *prep, size_t prep_bytes,
-                       uint32_t *ticket, gsr_stream_t stream_, void *zero_ptr, size_t zero_bytes);
+// ------------------------------------------------------------------------------------------- K5-K7: the tile sort
+// what the four launch functions are given.  `bounded`: D is a CAPACITY; the kernels read the pair count from the prep
+// workspace (K4's total) and do nothing past it
+struct SortCall {
+    BinFrame f;
+    int P;
+    const uint8_t *mask;
+    PrepViews pv;  // (read only)
+    int64_t D;
+    void *scratch;
+    uint32_t *point_list;
+    int32_t *ranges;
+    hipStream_t stream;
+    bool bounded;
+};
+
+// the row-major pipeline (binning_rows.h): segments by row, their scan, ONE pass over the pairs
+int launch_rows(const SortCall &s, const BinHooks &h, const BinDevice &d) {
+    const BinFrame &f = s.f;
+    const int P = s.P, gx = f.gx, gy = f.gy;
+    const long long D = s.D;
+    const RowsLayout R = rows_layout(D, gx, gy);
+    auto u32 = [&s](size_t off) { return at<uint32_t>(s.scratch, off); };
+    uint32_t *tickets = u32(R.tickets), *seg_key = u32(R.seg_key), *seg_gid = u32(R.seg_gid), *pairoff = u32(R.pairoff);
+    uint32_t *tilebase = u32(R.tilebase);
+    int32_t *tdiff = at<int32_t>(s.scratch, R.tdiff), *chunk_owner = at<int32_t>(s.scratch, R.chunk_owner);
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, (int)(&d - g_bin_devices));
+    const uint32_t *thist = s.pv.thist, *segoff = s.pv.segoff, *offsets = s.pv.offsets;
+    // grids: tiles are taken by ticket inside the kernels, so a grid only has to fill the device (the segment count
+    // is not known on the host, and the pair count only as a capacity in a bounded launch)
+    constexpr int TILE_B = 8 * ROWS_THREADS_B, TILE_D = 8 * ROWS_THREADS_D;
+    auto tickets_of = [](long long tiles) { return (tiles + TICKET_TILES - 1) / TICKET_TILES; };
+    const long long nbB = (D + TILE_B - 1) / TILE_B;
+    const int fill_b = cus * 2, fill_d = cus * h.rows_fill_d;
+    const int grid_b = (int)(tickets_of(nbB) < fill_b ? tickets_of(nbB) : fill_b);
+    const long long nbs = (D + SEGSCAN_TILE - 1) / SEGSCAN_TILE;
+    // (every workgroup costs a ticket -- an atomic on one word, ~15 ns each when hammered -- whether it finds work or not,
+    // and the segment count is typically D / 3..6: a grid of two workgroups per CU loops over the tiles instead)
+    const int grid_c = (int)(tickets_of(nbs) < cus * 2 ? tickets_of(nbs) : cus * 2);
+    const long long nbt = (D + TILE_D - 1) / TILE_D + gy;
+    const int grid_d = (int)(tickets_of(nbt) < fill_d ? tickets_of(nbt) : fill_d);
+    hipLaunchKernelGGL((seg_scatter_kernel<8, ROWS_THREADS_B>), dim3(grid_b), dim3(ROWS_THREADS_B), 0, s.stream, P, D,
+                       f.ybits, s.pv.rects, s.pv.vA, offsets, segoff, thist + 2 * RADIX_DIGITS, u32(R.seg_state), tickets,
+                       seg_key, seg_gid, s.bounded, s.ranges, 2 * gx * gy, s.pv.hull, tdiff,
+                       RADIX_REPLICAS * gy * (gx + 1));
+    hipLaunchKernelGGL(seg_scan_kernel, dim3(grid_c), dim3(SCAN_THREADS), 0, s.stream, P, D, gx, gy, offsets, segoff,
+                       seg_key, pairoff, at<unsigned long long>(s.scratch, R.scan_state), tickets + 1, tdiff, thist,
+                       chunk_owner, s.bounded);
+    hipLaunchKernelGGL(tile_base_kernel, dim3(gy), dim3(GSR_ONE_DIM_BLOCK), 0, s.stream, P, D, gx, gy, offsets, thist,
+                       tdiff, s.mask, tilebase, reinterpret_cast<int2 *>(s.ranges), s.bounded);
+    hipLaunchKernelGGL((pair_scatter_kernel<8, ROWS_THREADS_D>), dim3(grid_d), dim3(ROWS_THREADS_D), 0, s.stream, P, D, gx,
+                       gy, f.xbits, offsets, segoff, seg_key, seg_gid, pairoff, thist, tilebase, chunk_owner, u32(R.pair_state),
+                       tickets + 2, s.point_list, s.bounded);
+    GSR_LAUNCH_CHECK();
+    return 0;
 }
-extern "C" int gsr_bin_prepare_async(int P, int width, int height, const float *means2D, const float *depths,
-                                     const int32_t *radii, const float *conic_opacity, const uint8_t *compute_locally,
-                                     void *prep, size_t prep_bytes, uint32_t *ticket, gsr_stream_t stream_) {
-    return prepare_async_impl(P, width, height, means2D, depths, radii, conic_opacity, compute_locally, prep, prep_bytes,
-                              ticket, stream_, nullptr, 0);
+
+// K5-K7 as ONE persistent launch (binning_persist.h) when the device can hold the grid and no barrier kernel of another
+// stream may still be waiting.  -> 0 launched, 1 not now (the two look-back passes), otherwise an error
+int launch_persist_sort(const SortCall &s, const BinHooks &h, BinDevice &d) {
+    const BinFrame &f = s.f;
+    if (!(persist_effective_mode() & PERSIST_S)) return 1;
+    persist_caps(d);
+    const int grid_s = lowered(h.grid_s, d.grid_s);
+    const long long nbD = radix_blocks(s.D);
+    const int G = (int)(nbD < grid_s ? nbD : grid_s);
+    // long sorts are throughput-bound (VALU: the ranking) and the look-back pipeline, which reads every pair once
+    // less, wins: measured cross-over between 2 and 14 million pairs (profiles/r05_binning_persistent.txt)
+    if (!(G > 0 && d.done && s.D <= h.persist_maxd && !persist_sort_backoff(d, h.abort_s))) return 1;
+    const long long admit = persist_admit(d, s.stream);
+    if (admit < 0) return 1;
+    const SortViews v = views(sort_layout(f, s.D), s.scratch);
+    const PersistLayoutS PS = persist_layout_s(G);
+    SortPersistArgs a{};
+    a.P = s.P; a.gx = f.gx; a.xbits = f.xbits; a.ybits = f.ybits;
+    a.D = s.D; a.bounded = s.bounded ? 1 : 0;
+    a.rects = s.pv.rects; a.sorted_ids = s.pv.vA; a.offsets = s.pv.offsets; a.mask = s.mask;
+    a.kA = v.kA; a.kB = v.kB; a.vB = v.vB; a.point_list = s.point_list;
+    a.ranges = s.ranges; a.ranges_words = 2 * f.gx * f.gy;
+    a.hull = s.pv.hull;
+    a.sync = sync_view(v.ctrl + PS.sync, G);
+    a.tstamp = timeline_buffer(h.timeline, 1, G);
+    a.grp = at<uint32_t>(v.ctrl, PS.grp); a.cnt = at<uint32_t>(v.ctrl, PS.cnt);
+    a.grp_solo = at<uint32_t>(v.ctrl, PS.grp_solo); a.cnt_solo = at<uint32_t>(v.ctrl, PS.cnt_solo);
+    a.done_word = d.done; a.done_seq = (uint32_t)admit;
+    // a quarter of a second at the first barrier, then workgroup 0 sorts the view alone (no trap, no host round
+    // trip: binning_persist.h); GSR_BIN_SORT_TIMEOUT_MS overrides (tests)
+    a.timeout_ticks = 100000ull * (unsigned long long)h.sort_timeout_ms;
+    a.owners_cap = h.owners;
+    a.force_abort = h.abort_s ? 1 : 0;
+    hipLaunchKernelGGL(bin_sort_persist_kernel, dim3(G), dim3(PS_THREADS), 0, s.stream, a);
+    GSR_LAUNCH_CHECK();
+    return 0;
 }
-namespace {
-int prepare_async_impl(int P, int width, int height, const float *means2D, const float *depths, const int32_t *radii,
-                       const float *conic_opacity, const uint8_t *compute_locally, void *prep, size_t prep_bytes,
-                       uint32_t *ticket, gsr_stream_t stream_, void *zero_ptr, size_t zero_bytes) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (P < 0 || width <= 0 || height <= 0 || !ticket) return GSR_EINVAL;
-    *ticket = 0;  // 0: nothing was launched, the count is 0
-    if (P == 0) return 0;
-    if (!means2D || !depths || !radii || !conic_opacity || !compute_locally || !prep) return GSR_EINVAL;
-    if (P > RADIX_MAX_N) return GSR_EINVAL;
-    if (prep_bytes < prep_layout_full(P, width, height).total) return GSR_ENOSPACE;
-    const int gx = (width + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    if (gx > 0xFFFF || gy > 0xFFFF) return GSR_EINVAL;
-    PrepCall c{P, width, height, means2D, depths, radii, conic_opacity, compute_locally, prep, stream, true,
-               zero_ptr, zero_bytes};
-    {
-        int dev0 = 0;
-        GSR_HIP(hipGetDevice(&dev0));
-        const int fault = persist_fault_check(dev0);  // (a barrier fault of an earlier call: reported once)
-        if (fault) return fault;
-    }
-    int rc = prepare_persistent(c, ticket);
-    if (rc == 1) {
-        c.persistent = false;
-        rc = prepare_lookback(c, ticket);
-    }
+
+// (row, column) keys in two look-back passes: pass 0 (column digit) fused with the emission, pairs land in (kB, vB);
+// pass 1 (row digit) -> (kA, point_list); K7
+int launch_lookback_yx(const SortCall &s) {
+    const BinFrame &f = s.f;
+    const SortViews v = views(sort_layout(f, s.D), s.scratch);
+    const long long D = s.D;
+    const uint32_t *thist = s.pv.thist, *offsets = s.pv.offsets;
+    const int nb = (int)radix_blocks(D);
+    const uint32_t *D_dev = s.bounded ? offsets + s.P : nullptr;
+    hipLaunchKernelGGL((emit_scatter_kernel<RADIX_TILE / 512, 512>), dim3(nb), dim3(512), 0, s.stream, s.P, D, f.xbits,
+                       s.pv.rects, s.pv.vA, offsets, thist, v.state, v.tickets + 1, v.kB, v.vB, s.bounded, s.ranges,
+                       2 * f.gx * f.gy, s.pv.hull);
+    hipLaunchKernelGGL((radix_onesweep_kernel<RADIX_TILE / 512, 512>), dim3(nb), dim3(512), 0, s.stream, v.kB, v.vB, v.kA,
+                       s.point_list, D, f.xbits, f.ybits, thist + RADIX_DIGITS, v.state + (size_t)nb * RADIX_DIGITS,
+                       v.tickets + 2, D_dev);
+    hipLaunchKernelGGL(tile_ranges_yx_kernel, dim3(gsr_div_up(gsr_div_up(D, 4), GSR_ONE_DIM_BLOCK)),
+                       dim3(GSR_ONE_DIM_BLOCK), 0, s.stream, D, f.gx, f.xbits, v.kA, s.mask,
+                       reinterpret_cast<int2 *>(s.ranges), D_dev);
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
+// tile-id keys (frames above 256 x 256 tiles): K5, ceil(log2(tiles) / 8) look-back passes, K7
+int launch_generic(const SortCall &s) {
+    const BinFrame &f = s.f;
+    const SortLayout S = sort_layout(f, s.D);
+    const SortViews v = views(S, s.scratch);
+    const RadixPlan radix = radix_plan(0, tile_bits(f.tiles));
+    const long long D = s.D;
+    hipLaunchKernelGGL(emit_pairs_kernel, dim3(gsr_div_up(gsr_div_up(D, EMIT_CHUNK), 4)), dim3(256), 0, s.stream, s.P, D,
+                       f.gx, f.gx * f.gy, s.pv.rects, s.mask, s.pv.vA, s.pv.offsets, radix, v.kA, v.vA, v.ghist);
+    int in_first = 1;
+    // the last pass writes the Gaussian indices straight into point_list
+    const int rc = radix_sort_pairs(v.kA, v.vA, v.kB, v.vB, D, radix, v.ctrl, S.C, &in_first, s.stream, s.point_list);
     if (rc) return rc;
-    int dev = 0;
-    GSR_HIP(hipGetDevice(&dev));
-    c.zero_ptr = nullptr;  // (a repeat through gsr_bin_count_wait must not clear the control block of a sort in flight)
-    c.zero_bytes = 0;
-    if (dev >= 0 && dev < 64) g_prep_calls[dev][*ticket % TOTAL_SLOTS] = c;
+    hipLaunchKernelGGL(tile_ranges_kernel, dim3(gsr_div_up(gsr_div_up(D, 4), GSR_ONE_DIM_BLOCK)),
+                       dim3(GSR_ONE_DIM_BLOCK), 0, s.stream, D, (uint32_t)(f.gx * f.gy), in_first ? v.kA : v.kB,
+                       reinterpret_cast<int2 *>(s.ranges));
+    GSR_HIP(hipMemcpyAsync(s.ranges + 2 * (size_t)f.gx * f.gy, s.pv.hull, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                           s.stream));
+    GSR_LAUNCH_CHECK();
     return 0;
+}
+
+// the plan's form; its zero region has been cleared, or is being cleared by the prepare step in front of it
+int sort_run(const SortCall &s, const BinHooks &h, BinDevice &d, SortForm form) {
+    if (form == SORT_ROWS) return launch_rows(s, h, d);
+    if (form == SORT_GENERIC) return launch_generic(s);
+    const int rc = launch_persist_sort(s, h, d);
+    return rc == 1 ? launch_lookback_yx(s) : rc;
+}
+
+int bin_sort_impl(int P, int width, int height, const uint8_t *compute_locally, const void *prep, int64_t D,
+                  void *scratch, size_t scratch_bytes, uint32_t *point_list, int32_t *ranges, hipStream_t stream,
+                  bool bounded) {
+    if (P < 0 || width <= 0 || height <= 0 || D < 0 || !ranges) return GSR_EINVAL;
+    const BinFrame f = bin_frame(width, height);
+    if (D == 0 || P == 0 || !f.yx)  // (the (row, column) forms clear the table inside their first kernel)
+        GSR_HIP(hipMemsetAsync(ranges, 0, sizeof(int32_t) * 2 * ((size_t)f.gx * f.gy + 1), stream));  // + the hull row: (0, 0)
+    if (D == 0 || P == 0) return 0;
+    if (!compute_locally || !prep || !scratch || !point_list) return GSR_EINVAL;
+    const BinHooks h = read_hooks();
+    const SortPlan p = plan_sort(f, D, scratch_bytes, bounded, h.rows_min);
+    if (p.err) return p.err;
+    BinDevice *d = nullptr;
+    int rc = bin_device(&d);
+    if (!rc) rc = persist_fault_check(*d);
+    if (rc) return rc;
+    GSR_HIP(hipMemsetAsync(reinterpret_cast<char *>(scratch) + p.zero_off, 0, p.zero_bytes, stream));
+    return sort_run({f, P, compute_locally, views(prep_layout(P), const_cast<void *>(prep)), D, scratch, point_list, ranges,
+                     stream, bounded}, h, *d, p.form);
 }
 }  // namespace
 
-extern "C" int gsr_set_depth_tie_order(int mode) {
-    if (mode != 0 && mode != 1) return GSR_EINVAL;
-    g_tie_order.store(mode, std::memory_order_relaxed);
-    return 0;
+// ----------------------------------------------------------------------------------- K3..K7 API
+extern "C" size_t gsr_bin_prepare_bytes(int P, int width, int height) {
+    if (P < 0 || width <= 0 || height <= 0) return 0;
+    return prep_bytes_needed(P);
+}
+
+extern "C" size_t gsr_bin_total_offset(int P, int width, int height) {
+    if (P < 0 || width <= 0 || height <= 0) return 0;
+    return prep_layout(P).offsets + sizeof(uint32_t) * (size_t)P;  // offsets[P]: K4's total
+}
+
+extern "C" size_t gsr_bin_segments_offset(int P, int width, int height) {
+    if (P < 0 || width <= 0 || height <= 0) return 0;
+    return prep_layout(P).segoff + sizeof(uint32_t) * (size_t)P;  // segoff[P]: the row segments R
+}
+
+extern "C" size_t gsr_bin_sort_bytes(int P, int64_t num_rendered, int width, int height) {
+    (void)P;
+    if (num_rendered < 0 || width <= 0 || height <= 0) return 0;
+    return sort_layout(bin_frame(width, height), num_rendered).total;
+}
+
+extern "C" int64_t gsr_bin_sort_capacity(int P, size_t scratch_bytes, int width, int height) {
+    (void)P;
+    if (width <= 0 || height <= 0) return 0;
+    const BinFrame f = bin_frame(width, height);
+    if (!f.yx) return 0;  // bounded launches exist for the (row, column) path only
+    int64_t lo = 0, hi = RADIX_MAX_N;  // largest D whose layout fits scratch_bytes
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo + 1) / 2;
+        if (sort_layout(f, mid).total <= scratch_bytes) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 extern "C" int gsr_bin_count_wait(uint32_t ticket, int64_t *num_rendered_host, gsr_stream_t stream_) {
     if (!num_rendered_host) return GSR_EINVAL;
     *num_rendered_host = 0;
     if (ticket == 0) return 0;
-    uint32_t *host_total = nullptr;
-    int rc = slot_of_ticket(ticket, &host_total);
+    BinDevice *d = nullptr;
+    int rc = bin_device(&d);
     if (rc) return rc;
+    if (!d->total_word) return GSR_EINVAL;  // (no ticket was ever taken on this device)
     uint32_t total = 0;
-    rc = wait_total(reinterpret_cast<hipStream_t>(stream_), host_total, ticket, &total);
+    rc = wait_total(reinterpret_cast<hipStream_t>(stream_), slot_of_ticket(*d, ticket), ticket, &total);
     if (rc) return rc;
     if (total == PAIRS_ABORTED) {
         // the persistent kernel gave up at its first barrier (the device is shared with another barrier kernel): the
         // same call again on the look-back pipeline.  A gsr_bin_sort_bounded launched meanwhile has written nothing
         // (it saw a count above any capacity): GSR_ERETRY tells the caller to sort again
-        int dev = 0;
-        GSR_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64) return GSR_EINVAL;
-        PrepCall c = g_prep_calls[dev][ticket % TOTAL_SLOTS];
+        PrepCall c = d->calls[ticket % TOTAL_SLOTS];
         if (!c.persistent) return GSR_EINVAL;
         c.persistent = false;
         uint32_t again = 0;
-        rc = prepare_lookback(c, &again);
+        rc = prepare_lookback(c, bin_frame(c.width, c.height), *d, &again);
         if (rc) return rc;
-        rc = slot_of_ticket(again, &host_total);
-        if (rc) return rc;
-        rc = wait_total(c.stream, host_total, again, &total);
+        rc = wait_total(c.stream, slot_of_ticket(*d, again), again, &total);
         if (rc) return rc;
         *num_rendered_host = (int64_t)total;
         return GSR_ERETRY;
     }
     *num_rendered_host = (int64_t)total;
-    return 0;
-}
-
-extern "C" int gsr_set_tile_cull(int mode) {
-    if (mode < -1 || mode > 2) return GSR_EINVAL;
-    g_tile_cull.store(mode, std::memory_order_relaxed);
-    return 0;
-}
-
-extern "C" int gsr_bin_timeline(int which, unsigned long long *out, int max_words, int *grid) {
-    if (which < 0 || which > 1 || !out || !grid || max_words < 0) return GSR_EINVAL;
-    *grid = g_timeline_grid[which];
-    if (!g_timeline[which]) return 0;
-    const size_t n = (size_t)g_timeline_grid[which] * 32;
-    GSR_HIP(hipDeviceSynchronize());
-    GSR_HIP(hipMemcpy(out, g_timeline[which], sizeof(unsigned long long) * (n < (size_t)max_words ? n : (size_t)max_words),
-                      hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int gsr_bin_persist_status(uint32_t *out4) {
-    if (!out4) return GSR_EINVAL;
-    int dev = 0;
-    GSR_HIP(hipGetDevice(&dev));
-    out4[0] = out4[1] = out4[2] = out4[3] = 0;
-    if (dev < 0 || dev >= 64 || !g_persist_done[dev]) return 0;
-    const volatile uint32_t *w = g_persist_done[dev];
-    out4[0] = w[0]; out4[1] = w[1]; out4[2] = w[2]; out4[3] = w[3];
-    return 0;
-}
-
-extern "C" int gsr_set_bin_persistent(int mode) {
-    if (mode < -1 || mode > 3) return GSR_EINVAL;
-    g_persist_override.store(mode, std::memory_order_relaxed);
-    {  // an explicit choice also ends the back-off that follows a one-workgroup recovery of the sort kernel
-        std::lock_guard<std::mutex> guard(g_persist_mutex);
-        for (int dev = 0; dev < 64; dev++) {
-            if (!g_persist_done[dev]) continue;
-            g_persist_solo_seen[dev] = reinterpret_cast<volatile uint32_t *>(g_persist_done[dev])[3];
-            g_persist_backoff[dev] = 0;
-        }
-    }
     return 0;
 }
 
@@ -915,254 +826,9 @@ extern "C" int gsr_bin_prepare(int P, int width, int height, const float *means2
     const int rc = gsr_bin_prepare_async(P, width, height, means2D, depths, radii, conic_opacity, compute_locally, prep,
                                          prep_bytes, &ticket, stream_);
     if (rc) return rc;
-    {
-        const int rw = gsr_bin_count_wait(ticket, num_rendered_host, stream_);
-        return rw == GSR_ERETRY ? 0 : rw;  // (no sort has been launched for this count yet)
-    }
+    const int rw = gsr_bin_count_wait(ticket, num_rendered_host, stream_);
+    return rw == GSR_ERETRY ? 0 : rw;  // (no sort has been launched for this count yet)
 }
-
-namespace {
-struct SortLayout {
-    size_t kA, vA, kB, vB, ctrl, total;
-    CtrlLayout C;
-};
-SortLayout sort_layout(int64_t D, int passes, int gx = 0, int gy = 0) {
-    SortLayout L;
-    size_t o = 0;
-    const size_t nd = align_up((size_t)(D + 1) * 4);
-    L.kA = o; o += nd;
-    L.vA = o; o += nd;
-    L.kB = o; o += nd;
-    L.vB = o; o += nd;
-    L.ctrl = o;
-    L.C = ctrl_layout(D, passes, false);
-    const size_t need = persist_layout_s(persist_grid_bound_s(D)).total;  // (either pipeline's control block)
-    o += L.C.total > need ? L.C.total : need;
-    if (gx > 0 && gy > 0) {  // the row-major pipeline (binning_rows.h) lays the same scratch out its own way
-        const size_t rows = rows_layout(D, gx, gy).total;
-        if (rows > o) o = rows;
-    }
-    L.total = o;
-    return L;
-}
-
-// K5-K7 with one D-sized pass (binning_rows.h): on by default where it applies -- frames of <= 256 x 256 tiles, uncut rects
-std::atomic<int> g_rows_override{-1};  // gsr_set_bin_rowmajor: -1 = environment (GSR_BIN_ROWS = 0 | 1, default 1)
-// ... from ~5 million pairs on: below, its four launches (three latency chains of one tile each) lose to the persistent sort
-// kernel / the two look-back passes -- measured (tools/binbench.py, K5-K7 alone, exact sizes): 1.8 M pairs 71 against 54 us,
-// 5.6 M 107 against 101 us, 13.6 M 157 against 188 us (profiles/r06_rows_pipeline.txt).  GSR_BIN_ROWS_MIN overrides
-// (tests set 1 to run it on small scenes).
-long long rows_min_pairs() {
-    const char *e = getenv("GSR_BIN_ROWS_MIN");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? v : (5ll << 20);
-}
-bool rows_path(int gx, int gy, long long D = -1) {
-    if (D >= 0 && D < rows_min_pairs()) return false;
-    int mode = g_rows_override.load(std::memory_order_relaxed);
-    if (mode < 0) {
-        static const int env_mode = [] {
-            const char *e = getenv("GSR_BIN_ROWS");
-            return (e && *e == '0') ? 0 : 1;
-        }();
-        mode = env_mode;
-    }
-    return mode == 1 && yx_path(gx, gy) && !tile_cull_on(gx * gy);
-}
-}  // namespace
-
-#ifdef GSR_ROWS_TS
-extern "C" int gsr_debug_rows_ts(unsigned long long *out, int words) {
-    GSR_HIP(hipDeviceSynchronize());
-    GSR_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rows_ts), sizeof(unsigned long long) * (size_t)words));
-    return 0;
-}
-extern "C" int gsr_debug_rows_ts2(unsigned long long *out, int words) {
-    GSR_HIP(hipDeviceSynchronize());
-    GSR_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rows_ts2), sizeof(unsigned long long) * (size_t)words));
-    return 0;
-}
-#endif
-
-extern "C" int gsr_set_bin_rowmajor(int mode) {
-    if (mode < -1 || mode > 1) return GSR_EINVAL;
-    g_rows_override.store(mode, std::memory_order_relaxed);
-    return 0;
-}
-
-extern "C" size_t gsr_bin_sort_bytes(int P, int64_t num_rendered, int width, int height) {
-    (void)P;
-    if (num_rendered < 0 || width <= 0 || height <= 0) return 0;
-    const int gx = (width + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    const int passes = radix_plan(0, tile_bits(gx * gy)).passes;
-    // (the (row, column) path always runs 2 passes; the row-major pipeline's layout fits the same buffer)
-    return sort_layout(num_rendered, passes < 2 ? 2 : passes, yx_path(gx, gy) ? gx : 0, gy).total;
-}
-
-namespace {
-// `bounded`: D is a CAPACITY; the kernels read the pair count from the prep workspace (K4's total) and do nothing past it
-int bin_sort_impl(int P, int width, int height, const uint8_t *compute_locally, const void *prep, int64_t D,
-                  void *scratch, size_t scratch_bytes, uint32_t *point_list, int32_t *ranges, hipStream_t stream,
-                  bool bounded, bool ctrl_zeroed = false) {
-    if (P < 0 || width <= 0 || height <= 0 || D < 0 || !ranges) return GSR_EINVAL;
-    const int gx = (width + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    if (D == 0 || P == 0 || !yx_path(gx, gy))  // (the (row, column) path clears the table inside its first kernel)
-        GSR_HIP(hipMemsetAsync(ranges, 0, sizeof(int32_t) * 2 * ((size_t)gx * gy + 1), stream));  // + the hull row: (0, 0)
-    if (D == 0 || P == 0) return 0;
-    if (!compute_locally || !prep || !scratch || !point_list) return GSR_EINVAL;
-    if (D > RADIX_MAX_N) return GSR_EINVAL;
-    const RadixPlan plan = radix_plan(0, tile_bits(gx * gy));
-    const SortLayout S = sort_layout(D, plan.passes < 2 ? 2 : plan.passes, yx_path(gx, gy) ? gx : 0, gy);
-    if (scratch_bytes < S.total) return GSR_ENOSPACE;
-    const PrepLayout L = prep_layout(P, width, height);
-    const char *pbase = reinterpret_cast<const char *>(prep);
-    const uint32_t *sorted_ids = reinterpret_cast<const uint32_t *>(pbase + L.vA);
-    const uint32_t *offsets = reinterpret_cast<const uint32_t *>(pbase + L.offsets);
-    const TileRect *rects = reinterpret_cast<const TileRect *>(pbase + L.rects);
-    char *sbase = reinterpret_cast<char *>(scratch);
-    uint32_t *kA = reinterpret_cast<uint32_t *>(sbase + S.kA), *vA = reinterpret_cast<uint32_t *>(sbase + S.vA);
-    uint32_t *kB = reinterpret_cast<uint32_t *>(sbase + S.kB), *vB = reinterpret_cast<uint32_t *>(sbase + S.vB);
-    char *ctrl = sbase + S.ctrl;
-
-    if (bounded && !yx_path(gx, gy)) return GSR_EINVAL;
-    {
-        int dev0 = 0;
-        GSR_HIP(hipGetDevice(&dev0));
-        const int fault = persist_fault_check(dev0);
-        if (fault) return fault;
-    }
-    if (rows_path(gx, gy, D)) {
-        // ---- the row-major pipeline (binning_rows.h): segments by row, their scan, ONE pass over the pairs
-        const RowsLayout R = rows_layout(D, gx, gy);
-        if (scratch_bytes < R.total) return GSR_ENOSPACE;
-        if (!ctrl_zeroed) GSR_HIP(hipMemsetAsync(sbase + R.ctrl, 0, R.ctrl_bytes, stream));
-        const int xbits = bits_for(gx), ybits = bits_for(gy);
-        const uint32_t *thist = reinterpret_cast<const uint32_t *>(pbase + L.thist);
-        const uint32_t *segoff = reinterpret_cast<const uint32_t *>(pbase + L.segoff);
-        uint32_t *tickets = reinterpret_cast<uint32_t *>(sbase + R.tickets);
-        uint32_t *seg_key = reinterpret_cast<uint32_t *>(sbase + R.seg_key);
-        uint32_t *seg_gid = reinterpret_cast<uint32_t *>(sbase + R.seg_gid);
-        uint32_t *pairoff = reinterpret_cast<uint32_t *>(sbase + R.pairoff);
-        int32_t *tdiff = reinterpret_cast<int32_t *>(sbase + R.tdiff);
-        // grids: tiles are taken by ticket inside the kernels, so a grid only has to fill the device (the segment count
-        // is not known on the host, and the pair count only as a capacity in a bounded launch)
-        int dev = 0, cus = 256;
-        GSR_HIP(hipGetDevice(&dev));
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        constexpr int TILE_B = 8 * ROWS_THREADS_B, TILE_D = 8 * ROWS_THREADS_D;
-        auto tickets_of = [](long long tiles) { return (tiles + TICKET_TILES - 1) / TICKET_TILES; };
-        const long long nbB = (D + TILE_B - 1) / TILE_B;
-        const int fill_b = cus * 2, fill_d = cus * env_cap("GSR_ROWS_FILL_D", 4);  // (env: A/B measurements only)
-        const int grid_b = (int)(tickets_of(nbB) < fill_b ? tickets_of(nbB) : fill_b);
-        const long long nbs = (D + SEGSCAN_TILE - 1) / SEGSCAN_TILE;
-        // (every workgroup costs a ticket -- an atomic on one word, ~15 ns each when hammered -- whether it finds work or not,
-        // and the segment count is typically D / 3..6: a grid of two workgroups per CU loops over the tiles instead)
-        const int grid_c = (int)(tickets_of(nbs) < cus * 2 ? tickets_of(nbs) : cus * 2);
-        const long long nbt = (D + TILE_D - 1) / TILE_D + gy;
-        const int grid_d = (int)(tickets_of(nbt) < fill_d ? tickets_of(nbt) : fill_d);
-        uint32_t *tilebase = reinterpret_cast<uint32_t *>(sbase + R.tilebase);
-        int32_t *chunk_owner = reinterpret_cast<int32_t *>(sbase + R.chunk_owner);
-        hipLaunchKernelGGL((seg_scatter_kernel<8, ROWS_THREADS_B>), dim3(grid_b), dim3(ROWS_THREADS_B), 0, stream, P, (long long)D,
-                           ybits, rects, sorted_ids, offsets, segoff, thist + 2 * RADIX_DIGITS,
-                           reinterpret_cast<uint32_t *>(sbase + R.seg_state), tickets, seg_key, seg_gid, bounded, ranges,
-                           2 * gx * gy, reinterpret_cast<const int32_t *>(pbase + L.hull), tdiff, RADIX_REPLICAS * gy * (gx + 1));
-        hipLaunchKernelGGL(seg_scan_kernel, dim3(grid_c), dim3(SCAN_THREADS), 0, stream, P, (long long)D, gx, gy, offsets,
-                           segoff, seg_key, pairoff, reinterpret_cast<unsigned long long *>(sbase + R.scan_state),
-                           tickets + 1, tdiff, thist, chunk_owner, bounded);
-        hipLaunchKernelGGL(tile_base_kernel, dim3(gy), dim3(GSR_ONE_DIM_BLOCK), 0, stream, P, (long long)D, gx, gy, offsets,
-                           thist, tdiff, compute_locally, tilebase, reinterpret_cast<int2 *>(ranges), bounded);
-        hipLaunchKernelGGL((pair_scatter_kernel<8, ROWS_THREADS_D>), dim3(grid_d), dim3(ROWS_THREADS_D), 0, stream, P,
-                           (long long)D, gx, gy, xbits, offsets, segoff, seg_key, seg_gid, pairoff, thist, tilebase,
-                           chunk_owner, reinterpret_cast<uint32_t *>(sbase + R.pair_state), tickets + 2, point_list,
-                           bounded);
-        GSR_LAUNCH_CHECK();
-        return 0;
-    }
-    if (yx_path(gx, gy) && (persist_effective_mode() & PERSIST_S)) {
-        // K5-K7 as ONE persistent launch (binning_persist.h) when the device can hold the grid and no barrier kernel of
-        // another stream may still be waiting
-        int dev = 0;
-        GSR_HIP(hipGetDevice(&dev));
-        PersistCaps caps;
-        const bool dev_ok = dev >= 0 && dev < 64;
-        if (dev_ok) persist_caps(dev, &caps);
-        const long long nbD = radix_blocks(D);
-        const int G = (int)(nbD < caps.grid_s ? nbD : caps.grid_s);
-        // long sorts are throughput-bound (VALU: the ranking) and the look-back pipeline, which reads every pair once
-        // less, wins: measured cross-over between 2 and 14 million pairs (profiles/r05_binning_persistent.txt)
-        const long long max_pairs = env_cap("GSR_BIN_PERSIST_MAXD", 0x7fffffff) == 0x7fffffff ? PERSIST_SORT_MAX_PAIRS
-                                                                                        : env_cap("GSR_BIN_PERSIST_MAXD", 0x7fffffff);
-        const bool want = dev_ok && G > 0 && g_persist_done[dev] && D <= max_pairs && !persist_sort_backoff(dev);
-        const long long admit = want ? persist_admit(dev, stream) : -1;
-        if (admit >= 0) {
-            const PersistLayoutS PS = persist_layout_s(G);
-            if (!ctrl_zeroed) GSR_HIP(hipMemsetAsync(ctrl, 0, PS.zero_bytes, stream));
-            SortPersistArgs a{};
-            a.P = P; a.gx = gx; a.xbits = bits_for(gx); a.ybits = bits_for(gy);
-            a.D = D; a.bounded = bounded ? 1 : 0;
-            a.rects = rects; a.sorted_ids = sorted_ids; a.offsets = offsets; a.mask = compute_locally;
-            a.kA = kA; a.kB = kB; a.vB = vB; a.point_list = point_list;
-            a.ranges = ranges; a.ranges_words = 2 * gx * gy;
-            a.hull = reinterpret_cast<const int32_t *>(pbase + L.hull);
-            const int ngroups = (G + GB_FAN - 1) / GB_FAN;
-            a.sync.leaf = reinterpret_cast<uint32_t *>(ctrl + PS.sync);
-            a.sync.root = a.sync.leaf + (size_t)ngroups * GB_LEAF_STRIDE;
-            a.sync.flags = a.sync.root + GB_LEAF_STRIDE;
-            a.tstamp = timeline_buffer(1, G);
-            a.grp = reinterpret_cast<uint32_t *>(ctrl + PS.grp);
-            a.cnt = reinterpret_cast<uint32_t *>(ctrl + PS.cnt);
-            a.grp_solo = reinterpret_cast<uint32_t *>(ctrl + PS.grp_solo);
-            a.cnt_solo = reinterpret_cast<uint32_t *>(ctrl + PS.cnt_solo);
-            a.done_word = g_persist_done[dev];
-            a.done_seq = (uint32_t)admit;
-            // a quarter of a second at the first barrier, then workgroup 0 sorts the view alone (no trap, no host round
-            // trip: binning_persist.h); GSR_BIN_SORT_TIMEOUT_MS overrides (tests)
-            a.timeout_ticks = 100000ull * (unsigned long long)env_cap("GSR_BIN_SORT_TIMEOUT_MS", 250);
-            a.owners_cap = env_cap("GSR_BIN_OWNERS", PS_OWNERS);
-            a.force_abort = force_abort_env('s') ? 1 : 0;
-            hipLaunchKernelGGL(bin_sort_persist_kernel, dim3(G), dim3(PS_THREADS), 0, stream, a);
-            GSR_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if (!ctrl_zeroed) GSR_HIP(hipMemsetAsync(ctrl, 0, S.C.total, stream));
-    if (yx_path(gx, gy)) {
-        const int xbits = bits_for(gx), ybits = bits_for(gy);
-        const uint32_t *thist = reinterpret_cast<const uint32_t *>(pbase + L.thist);
-        const int nb = (int)radix_blocks(D);
-        const uint32_t *D_dev = bounded ? offsets + P : nullptr;
-        uint32_t *tickets = reinterpret_cast<uint32_t *>(ctrl + S.C.tickets);
-        uint32_t *state = reinterpret_cast<uint32_t *>(ctrl + S.C.radix_state);
-        // pass 0 (column digit) fused with the emission: pairs land in (kB, vB); pass 1 (row digit) -> (kA, point_list)
-        hipLaunchKernelGGL((emit_scatter_kernel<RADIX_TILE / 512, 512>), dim3(nb), dim3(512), 0, stream, P, (long long)D,
-                           xbits, rects, sorted_ids, offsets, thist, state, tickets + 1, kB, vB, bounded, ranges,
-                           2 * gx * gy, reinterpret_cast<const int32_t *>(pbase + L.hull));
-        hipLaunchKernelGGL((radix_onesweep_kernel<RADIX_TILE / 512, 512>), dim3(nb), dim3(512), 0, stream, kB, vB, kA,
-                           point_list, (long long)D, xbits, ybits, thist + RADIX_DIGITS,
-                           state + (size_t)nb * RADIX_DIGITS, tickets + 2, D_dev);
-        hipLaunchKernelGGL(tile_ranges_yx_kernel, dim3(gsr_div_up(gsr_div_up(D, 4), GSR_ONE_DIM_BLOCK)),
-                           dim3(GSR_ONE_DIM_BLOCK), 0, stream, (long long)D, gx, xbits, kA, compute_locally,
-                           reinterpret_cast<int2 *>(ranges), D_dev);
-        GSR_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(emit_pairs_kernel, dim3(gsr_div_up(gsr_div_up(D, EMIT_CHUNK), 4)), dim3(256), 0, stream, P,
-                       (long long)D, gx, gx * gy, rects, compute_locally, sorted_ids, offsets, plan, kA, vA,
-                       reinterpret_cast<uint32_t *>(ctrl + S.C.ghist));
-    int in_first = 1;
-    // the last pass writes the Gaussian indices straight into point_list
-    int rc = radix_sort_pairs(kA, vA, kB, vB, D, plan, ctrl, S.C, &in_first, stream, point_list);
-    if (rc) return rc;
-    const uint32_t *ks = in_first ? kA : kB;
-    hipLaunchKernelGGL(tile_ranges_kernel, dim3(gsr_div_up(gsr_div_up(D, 4), GSR_ONE_DIM_BLOCK)),
-                       dim3(GSR_ONE_DIM_BLOCK), 0, stream, (long long)D, (uint32_t)(gx * gy), ks,
-                       reinterpret_cast<int2 *>(ranges));
-    GSR_HIP(hipMemcpyAsync(ranges + 2 * (size_t)gx * gy, pbase + L.hull, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                           stream));
-    GSR_LAUNCH_CHECK();
-    return 0;
-}
-}  // namespace
 
 extern "C" int gsr_bin_sort(int P, int width, int height, const uint8_t *compute_locally, const void *prep,
                             int64_t D, void *scratch, size_t scratch_bytes, uint32_t *point_list, int32_t *ranges,
@@ -1183,7 +849,8 @@ extern "C" int gsr_bin_sort_bounded(int P, int width, int height, const uint8_t 
 // then -- when `capacity` > 0 -- gsr_bin_sort_bounded into (scratch, point_list).  Nothing waits: *ticket names the
 // pair count for gsr_bin_count_wait, which the caller may call after it has launched the kernels that consume the
 // lists (they read the ranges, never the count) -- round 6: the host no longer stands between K3-K7 and K8.
-// *sorted = 1 when the bounded sort was launched.
+// *sorted = 1 when the bounded sort was launched.  The sort is planned BEFORE the prepare step is launched: that step's
+// first kernel clears the plan's zero region (no fill launch between the steps), and the same plan runs behind it.
 extern "C" int gsr_bin_speculative_async(int P, int width, int height, const float *means2D, const float *depths,
                                          const int32_t *radii, const float *conic_opacity,
                                          const uint8_t *compute_locally, void *prep, size_t prep_bytes,
@@ -1191,59 +858,118 @@ extern "C" int gsr_bin_speculative_async(int P, int width, int height, const flo
                                          int32_t *ranges, uint32_t *ticket, int *sorted, gsr_stream_t stream_) {
     if (!ticket || !sorted) return GSR_EINVAL;
     *sorted = 0;
-    // the tile sort's control block (either pipeline's: they share the space) is cleared by the prepare step's first
-    // kernel instead of by a fill launch between the two steps
-    void *zero_ptr = nullptr;
-    size_t zero_bytes = 0;
-    const bool spec = capacity > 0 && scratch && point_list && P > 0 && width > 0 && height > 0;
-    if (spec) {
-        const int gx = (width + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-        if (yx_path(gx, gy) && capacity <= RADIX_MAX_N) {
-            const RadixPlan plan = radix_plan(0, tile_bits(gx * gy));
-            const SortLayout S = sort_layout(capacity, plan.passes < 2 ? 2 : plan.passes, gx, gy);
-            if (scratch_bytes >= S.total && rows_path(gx, gy, capacity)) {
-                const RowsLayout RL = rows_layout(capacity, gx, gy);
-                zero_ptr = reinterpret_cast<char *>(scratch) + RL.ctrl;
-                zero_bytes = ((RL.ctrl_bytes + 15) / 16) * 16;
-                if (RL.ctrl + zero_bytes > scratch_bytes || (RL.ctrl & 15)) { zero_ptr = nullptr; zero_bytes = 0; }
-            } else if (scratch_bytes >= S.total) {
-                const size_t zp = persist_layout_s(persist_grid_bound_s(capacity)).zero_bytes;
-                zero_ptr = reinterpret_cast<char *>(scratch) + S.ctrl;
-                zero_bytes = (((S.C.total > zp ? S.C.total : zp) + 15) / 16) * 16;
-                if (S.ctrl + zero_bytes > scratch_bytes || (S.ctrl & 15)) { zero_ptr = nullptr; zero_bytes = 0; }
-            }
-        }
-    }
-    int rc = prepare_async_impl(P, width, height, means2D, depths, radii, conic_opacity, compute_locally, prep, prep_bytes,
-                                ticket, stream_, zero_ptr, zero_bytes);
+    if (P < 0 || width <= 0 || height <= 0) return GSR_EINVAL;
+    *ticket = 0;  // 0: nothing was launched, the count is 0
+    if (P == 0) return 0;
+    if (!means2D || !depths || !radii || !conic_opacity || !compute_locally || !prep) return GSR_EINVAL;
+    if (P > RADIX_MAX_N) return GSR_EINVAL;
+    if (prep_bytes < prep_bytes_needed(P)) return GSR_ENOSPACE;
+    const BinFrame f = bin_frame(width, height);
+    if (f.gx > 0xFFFF || f.gy > 0xFFFF) return GSR_EINVAL;
+    BinDevice *d = nullptr;
+    int rc = bin_device(&d);
+    if (!rc) rc = persist_fault_check(*d);
     if (rc) return rc;
-    if (capacity > 0 && *ticket != 0 && scratch && point_list) {
-        rc = bin_sort_impl(P, width, height, compute_locally, prep, capacity, scratch, scratch_bytes, point_list, ranges,
-                           reinterpret_cast<hipStream_t>(stream_), true, zero_ptr != nullptr);
-        if (rc) return rc;
-        *sorted = 1;
+    const BinHooks h = read_hooks();
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const bool sort = capacity > 0 && scratch && point_list;
+    const SortPlan p = sort ? plan_sort(f, capacity, scratch_bytes, true, h.rows_min) : SortPlan{GSR_EINVAL};
+    PrepCall c{P, width, height, means2D, depths, radii, conic_opacity, compute_locally, prep, stream, true, nullptr, 0};
+    if (!p.err) {
+        c.zero_ptr = reinterpret_cast<char *>(scratch) + p.zero_off;
+        c.zero_bytes = p.zero_bytes;
+    }
+    rc = prepare_persistent(c, f, h, *d, ticket);
+    if (rc == 1) {  // (not applicable here: the look-back pipeline)
+        c.persistent = false;
+        rc = prepare_lookback(c, f, *d, ticket);
+    }
+    if (rc) return rc;
+    d->calls[*ticket % TOTAL_SLOTS] = c;
+    d->calls[*ticket % TOTAL_SLOTS].zero_ptr = nullptr;  // (a repeat through gsr_bin_count_wait must not clear the
+    d->calls[*ticket % TOTAL_SLOTS].zero_bytes = 0;      // control block of a sort in flight)
+    if (!sort) return 0;
+    if (!ranges) return GSR_EINVAL;
+    if (!f.yx) GSR_HIP(hipMemsetAsync(ranges, 0, sizeof(int32_t) * 2 * ((size_t)f.gx * f.gy + 1), stream));
+    if (p.err) return p.err;
+    rc = sort_run({f, P, compute_locally, views(prep_layout(P), prep), capacity, scratch, point_list, ranges, stream, true},
+                  h, *d, p.form);
+    if (rc) return rc;
+    *sorted = 1;
+    return 0;
+}
+
+extern "C" int gsr_bin_prepare_async(int P, int width, int height, const float *means2D, const float *depths,
+                                     const int32_t *radii, const float *conic_opacity, const uint8_t *compute_locally,
+                                     void *prep, size_t prep_bytes, uint32_t *ticket, gsr_stream_t stream_) {
+    int sorted = 0;
+    return gsr_bin_speculative_async(P, width, height, means2D, depths, radii, conic_opacity, compute_locally, prep,
+                                     prep_bytes, 0, nullptr, 0, nullptr, nullptr, ticket, &sorted, stream_);
+}
+
+extern "C" int gsr_set_depth_tie_order(int mode) {
+    if (mode != 0 && mode != 1) return GSR_EINVAL;
+    g_tie_order.store(mode, std::memory_order_relaxed);
+    return 0;
+}
+
+extern "C" int gsr_set_tile_cull(int mode) {
+    if (mode < -1 || mode > 2) return GSR_EINVAL;
+    g_tile_cull.store(mode, std::memory_order_relaxed);
+    return 0;
+}
+
+extern "C" int gsr_set_bin_rowmajor(int mode) {
+    if (mode < -1 || mode > 1) return GSR_EINVAL;
+    g_rows_override.store(mode, std::memory_order_relaxed);
+    return 0;
+}
+
+extern "C" int gsr_set_bin_persistent(int mode) {
+    if (mode < -1 || mode > 3) return GSR_EINVAL;
+    g_persist_override.store(mode, std::memory_order_relaxed);
+    // an explicit choice also ends the back-off that follows a one-workgroup recovery of the sort kernel
+    std::lock_guard<std::mutex> guard(g_bin_mutex);
+    for (BinDevice &d : g_bin_devices) {
+        if (!d.done) continue;
+        d.solo_seen = reinterpret_cast<volatile uint32_t *>(d.done)[3];
+        d.backoff = 0;
     }
     return 0;
 }
 
-extern "C" size_t gsr_bin_total_offset(int P, int width, int height) {
-    if (P < 0 || width <= 0 || height <= 0) return 0;
-    return prep_layout(P, width, height).offsets + sizeof(uint32_t) * (size_t)P;  // offsets[P]: K4's total
+extern "C" int gsr_bin_persist_status(uint32_t *out4) {
+    if (!out4) return GSR_EINVAL;
+    BinDevice *d = nullptr;
+    const int rc = bin_device(&d);
+    if (rc && rc != GSR_EINVAL) return rc;
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (rc || !d->done) return 0;  // (a device beyond the table has no persistent launches)
+    const volatile uint32_t *w = d->done;
+    out4[0] = w[0]; out4[1] = w[1]; out4[2] = w[2]; out4[3] = w[3];
+    return 0;
 }
 
-extern "C" size_t gsr_bin_segments_offset(int P, int width, int height) {
-    if (P < 0 || width <= 0 || height <= 0) return 0;
-    return prep_layout(P, width, height).segoff + sizeof(uint32_t) * (size_t)P;  // segoff[P]: the row segments R
+extern "C" int gsr_bin_timeline(int which, unsigned long long *out, int max_words, int *grid) {
+    if (which < 0 || which > 1 || !out || !grid || max_words < 0) return GSR_EINVAL;
+    *grid = g_timeline_grid[which];
+    if (!g_timeline[which]) return 0;
+    const size_t n = (size_t)g_timeline_grid[which] * 32;
+    GSR_HIP(hipDeviceSynchronize());
+    GSR_HIP(hipMemcpy(out, g_timeline[which], sizeof(unsigned long long) * (n < (size_t)max_words ? n : (size_t)max_words),
+                      hipMemcpyDeviceToHost));
+    return 0;
 }
 
-extern "C" int64_t gsr_bin_sort_capacity(int P, size_t scratch_bytes, int width, int height) {
-    if (width <= 0 || height <= 0) return 0;
-    const int gx = (width + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    if (!yx_path(gx, gy)) return 0;  // bounded launches exist for the (row, column) path only
-    int64_t lo = 0, hi = RADIX_MAX_N;  // largest D with gsr_bin_sort_bytes(P, D, ...) <= scratch_bytes
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (gsr_bin_sort_bytes(P, mid, width, height) <= scratch_bytes) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+#ifdef GSR_ROWS_TS
+extern "C" int gsr_debug_rows_ts(unsigned long long *out, int words) {
+    GSR_HIP(hipDeviceSynchronize());
+    GSR_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rows_ts), sizeof(unsigned long long) * (size_t)words));
+    return 0;
 }
+extern "C" int gsr_debug_rows_ts2(unsigned long long *out, int words) {
+    GSR_HIP(hipDeviceSynchronize());
+    GSR_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rows_ts2), sizeof(unsigned long long) * (size_t)words));
+    return 0;
+}
+#endif

@@ -1726,192 +1726,4 @@ bin_sort_persist_kernel(const SortPersistArgs a) {
     GSR_TS(9);
 }
 
-// ------------------------------------------------------------------------------------------ host side
-struct PersistLayoutP {  // inside the control block of the prepare workspace
-    size_t sync, grp, bins, cnt, wtot, zero_bytes, total;
-};
-inline PersistLayoutP persist_layout_p(int G) {
-    PersistLayoutP L;
-    const int ngroups = (G + GB_FAN - 1) / GB_FAN;
-    size_t o = 0;
-    L.sync = o; o += align_up(sizeof(uint32_t) * grid_sync_words(G));
-    L.grp = o; o += align_up(sizeof(uint32_t) * (BK_PASS + 1) * (size_t)ngroups * RADIX_DIGITS);
-    L.bins = o; o += align_up(sizeof(uint32_t) * (BK_BINS + 2));  // bin counts, { ~min, max } key (bucket path)
-    L.zero_bytes = o;  // [0, zero_bytes) is cleared before every launch
-    L.cnt = o; o += align_up(sizeof(uint32_t) * (BK_PASS + 1) * (size_t)G * RADIX_DIGITS);
-    L.wtot = o; o += align_up(sizeof(unsigned long long) * (size_t)G);
-    L.total = o;
-    return L;
-}
-struct PersistLayoutS {
-    size_t sync, grp, grp_solo, cnt, cnt_solo, zero_bytes, total;
-};
-inline PersistLayoutS persist_layout_s(int G) {
-    PersistLayoutS L;
-    const int ngroups = (G + GB_FAN - 1) / GB_FAN;
-    size_t o = 0;
-    L.sync = o; o += align_up(sizeof(uint32_t) * grid_sync_words(G));
-    L.grp = o; o += align_up(sizeof(uint32_t) * 2 * (size_t)ngroups * RADIX_DIGITS);
-    L.grp_solo = o; o += align_up(sizeof(uint32_t) * 2 * RADIX_DIGITS);  // (workgroup 0 alone after an aborted first barrier)
-    L.zero_bytes = o;
-    L.cnt = o; o += align_up(sizeof(uint32_t) * 2 * (size_t)G * RADIX_DIGITS);
-    L.cnt_solo = o; o += align_up(sizeof(uint32_t) * 2 * RADIX_DIGITS);
-    L.total = o;
-    return L;
-}
-constexpr int PERSIST_MAX_GRID_P = 1024;  // upper bounds used to size workspaces (CUs x workgroups per CU of any part)
-constexpr int PERSIST_MAX_GRID_S = 4096;
-constexpr long long PERSIST_SORT_MAX_PAIRS = 6ll << 20;  // above: the look-back tile sort (GSR_BIN_PERSIST_MAXD overrides)
-
-// what the device holds at once, per kernel (queried once per device)
-struct PersistCaps {
-    int grid_p = 0, grid_s = 0;  // 0: unavailable
-    bool init = false;
-};
-std::mutex g_persist_mutex;
-PersistCaps g_persist_caps[64];
-uint32_t *g_persist_done[64] = {};       // pinned: { sequence number of the last launch past its last barrier, fault code,
-                                         // faults (barrier_fault), solo recoveries of the sort kernel }
-uint32_t g_persist_faults_seen[64] = {}; // faults already reported to a caller
-uint32_t g_persist_solo_seen[64] = {};   // recoveries already answered with a back-off
-int g_persist_backoff[64] = {};          // sort calls that still take the look-back tile sort after a recovery
-bool g_persist_faulted[64] = {};         // a barrier after the first timed out once: look-back pipeline from then on
-uint32_t g_persist_seq[64] = {};         // last sequence number handed out
-hipStream_t g_persist_stream[64] = {};   // stream of that launch
-bool g_persist_any[64] = {};
-
-enum { PERSIST_OFF = 0, PERSIST_P = 1, PERSIST_S = 2 };
-int persist_mode() {  // GSR_BIN_PERSIST = 0 | 1 (default) | p | s : A/B measurements and shared devices
-    static const int mode = [] {
-        const char *e = getenv("GSR_BIN_PERSIST");
-        if (!e || !*e || strcmp(e, "1") == 0) return PERSIST_P | PERSIST_S;
-        if (strcmp(e, "p") == 0) return (int)PERSIST_P;
-        if (strcmp(e, "s") == 0) return (int)PERSIST_S;
-        return (int)PERSIST_OFF;
-    }();
-    return mode;
-}
-std::atomic<int> g_persist_override{-1};  // gsr_set_bin_persistent: -1 = environment
-
-// Diagnostics (GSR_BIN_TIMELINE=1): one device buffer per kernel, [grid][32] stamps of the 100 MHz clock taken by thread 0
-// of every workgroup at the phase boundaries of the LAST launch; read with gsr_bin_timeline.
-unsigned long long *g_timeline[2] = {nullptr, nullptr};
-int g_timeline_grid[2] = {0, 0};
-unsigned long long *timeline_buffer(int which, int G) {
-    const char *e = getenv("GSR_BIN_TIMELINE");  // (read per call: a test switches it on for the launches it looks at)
-    if (!(e && *e == '1')) return nullptr;
-    if (!g_timeline[which]) {
-        void *p = nullptr;
-        if (hipMalloc(&p, sizeof(unsigned long long) * 32 * PERSIST_MAX_GRID_S) != hipSuccess) return nullptr;
-        g_timeline[which] = reinterpret_cast<unsigned long long *>(p);
-    }
-    (void)hipMemset(g_timeline[which], 0, sizeof(unsigned long long) * 32 * (size_t)G);
-    g_timeline_grid[which] = G;
-    return g_timeline[which];
-}
-
-// test hooks (read per call): GSR_BIN_GRID_P / GSR_BIN_GRID_S cap the grids (many tiles per workgroup on small scenes),
-// GSR_BIN_OWNERS caps the chunk-owner table
-int env_cap(const char *name, int dflt) {
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    const int v = atoi(e);
-    return v > 0 && v < dflt ? v : dflt;
-}
-
-int persist_caps(int dev, PersistCaps *out) {
-    std::lock_guard<std::mutex> guard(g_persist_mutex);
-    PersistCaps &c = g_persist_caps[dev];
-    if (!c.init) {
-        c.init = true;
-        int cus = 0, per_p = 0, per_p8 = 0, per_s = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_p, bin_prepare_persist_kernel<4>, PP_THREADS, 0) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_p8, bin_prepare_persist_kernel<8>, PP_THREADS, 0) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_s, bin_sort_persist_kernel, PS_THREADS, 0) == hipSuccess) {
-            // one prepare workgroup per CU (16 waves: the latency chain of a tile wants the CU to itself); the sort
-            // fills the device (four per CU when the registers allow)
-            c.grid_p = (per_p >= 1 && per_p8 >= 1) ? (cus < PERSIST_MAX_GRID_P ? cus : PERSIST_MAX_GRID_P) : 0;
-            const long long gs = (long long)cus * (per_s < 4 ? per_s : 4);
-            c.grid_s = per_s >= 1 ? (int)(gs < PERSIST_MAX_GRID_S ? gs : PERSIST_MAX_GRID_S) : 0;
-        }
-        void *p = nullptr;
-        if (hipHostMalloc(&p, 64, hipHostMallocDefault) == hipSuccess) {
-            memset(p, 0, 64);
-            g_persist_done[dev] = reinterpret_cast<uint32_t *>(p);
-        } else {
-            c.grid_p = c.grid_s = 0;
-        }
-        (void)hipGetLastError();
-    }
-    *out = c;
-    out->grid_p = env_cap("GSR_BIN_GRID_P", c.grid_p);
-    out->grid_s = env_cap("GSR_BIN_GRID_S", c.grid_s);
-    return 0;
-}
-
-// May a barrier kernel be launched on `stream` now?  Yes when the previous one ran on the same stream (stream order
-// serialises them) or has passed its last barrier.  -> sequence number to publish (0 inside a stream capture: a replay
-// cannot be tracked -- graphs replay on the stream that owns the device's binning), or -1: use the look-back pipeline.
-long long persist_admit(int dev, hipStream_t stream) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return 0;
-    (void)hipGetLastError();
-    std::lock_guard<std::mutex> guard(g_persist_mutex);
-    if (g_persist_faulted[dev]) return -1;
-    if (g_persist_any[dev] && g_persist_stream[dev] != stream) {
-        // (round 6: the host now has a view's pair count ~20 us into its prepare kernel, so a caller that alternates
-        // views between two streams arrives here while the other stream's ~100 us kernel is still running; giving up at
-        // once sent every second view down the nine launches of the look-back pipeline -- measured 2140 -> 1410 views/s.
-        // A bounded wait for that kernel's last barrier costs the host what the count poll used to cost it.)
-        const volatile uint32_t *done = reinterpret_cast<volatile uint32_t *>(g_persist_done[dev]);
-        if (*done != g_persist_seq[dev]) {
-            const auto t0 = std::chrono::steady_clock::now();
-            while (*done != g_persist_seq[dev]) {
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(250)) return -1;
-            }
-        }
-    }
-    uint32_t s = ++g_persist_seq[dev];
-    if (s == 0) s = ++g_persist_seq[dev];
-    g_persist_stream[dev] = stream;
-    g_persist_any[dev] = true;
-    return (long long)s;
-}
-
-// Has a persistent kernel of this device reported a barrier fault (barrier_fault) that no caller has been told about?
-// -> GSR_EFAULT once per fault; the device keeps to the look-back pipeline afterwards.
-int persist_fault_check(int dev) {
-    if (dev < 0 || dev >= 64 || !g_persist_done[dev]) return 0;
-    std::lock_guard<std::mutex> guard(g_persist_mutex);
-    const uint32_t faults = reinterpret_cast<volatile uint32_t *>(g_persist_done[dev])[2];
-    if (faults == g_persist_faults_seen[dev]) return 0;
-    g_persist_faults_seen[dev] = faults;
-    g_persist_faulted[dev] = true;
-    return GSR_EFAULT;
-}
-
-// test hook: GSR_BIN_FORCE_ABORT = p | s | ps (read per call): the named kernels' first barrier aborts
-bool force_abort_env(char which) {
-    const char *e = getenv("GSR_BIN_FORCE_ABORT");
-    return e && strchr(e, which) != nullptr;
-}
-
-// The sort kernel finished a view with workgroup 0 alone (the grid could not become resident within the time-out): the
-// next calls take the look-back tile sort instead of waiting out the time-out again.
-bool persist_sort_backoff(int dev) {
-    std::lock_guard<std::mutex> guard(g_persist_mutex);
-    const uint32_t solo = reinterpret_cast<volatile uint32_t *>(g_persist_done[dev])[3];
-    if (solo != g_persist_solo_seen[dev]) {
-        g_persist_solo_seen[dev] = solo;
-        g_persist_backoff[dev] = force_abort_env('s') ? 0 : 64;  // (a forced abort is a test: keep the kernel in use)
-    }
-    if (g_persist_backoff[dev] > 0) {
-        g_persist_backoff[dev]--;
-        return true;
-    }
-    return false;
-}
-
-
 }  // namespace

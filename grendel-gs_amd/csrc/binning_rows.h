@@ -570,30 +570,4 @@ pair_scatter_kernel(int P, long long Dcap, int gx, int gy, int xbits, const uint
     }
 }
 
-// ------------------------------------------------------------------------------------------------- host side
-struct RowsLayout {
-    size_t seg_key, seg_gid, pairoff, tdiff, tilebase, chunk_owner, ctrl, tickets, scan_state, seg_state, pair_state,
-        ctrl_bytes, total;
-};
-inline RowsLayout rows_layout(int64_t D, int gx, int gy) {
-    RowsLayout L;
-    size_t o = 0;
-    const size_t nr = align_up((size_t)(D + 1) * 4);  // R <= D segments
-    L.seg_key = o; o += nr;
-    L.seg_gid = o; o += nr;
-    L.pairoff = o; o += nr;
-    // (one replica per XCD, cleared by seg_scatter_kernel)
-    L.tdiff = o; o += align_up(sizeof(int32_t) * RADIX_REPLICAS * (size_t)gy * (size_t)(gx + 1));
-    L.tilebase = o; o += align_up(sizeof(uint32_t) * (size_t)gx * gy);
-    L.chunk_owner = o; o += align_up(sizeof(int32_t) * (size_t)(radix_blocks(D) + gy + 1) * (RADIX_TILE / PS_CHUNK));
-    L.ctrl = o;  // [ctrl, ctrl + ctrl_bytes) is zero before the first kernel
-    L.tickets = o; o += 256;
-    L.scan_state = o; o += align_up(sizeof(unsigned long long) * (size_t)((D + SEGSCAN_TILE - 1) / SEGSCAN_TILE + 2));
-    L.seg_state = o; o += align_up(sizeof(uint32_t) * (size_t)(radix_blocks(D) + 1) * RADIX_DIGITS);
-    L.pair_state = o; o += align_up(sizeof(uint32_t) * (size_t)(radix_blocks(D) + gy + 1) * RADIX_DIGITS);
-    L.ctrl_bytes = o - L.ctrl;
-    L.total = o;
-    return L;
-}
-
 }  // namespace

@@ -954,21 +954,30 @@ def _debug_overlap(name, t):
                   file=__import__("sys").stderr, flush=True)
 
 
+def _bin_workspaces(means2D, depths, radii, conic_opacity, compute_locally, width, height):
+    """what every K3-K7 call starts with -> (P, dev, ranges, prep, args): the range table, the prepare workspace and the
+    ten leading arguments of gsr_bin_prepare_async / gsr_bin_speculative_async"""
+    P = means2D.shape[0]
+    dev = means2D.device
+    tiles = ((width + BLOCK_X - 1) // BLOCK_X) * ((height + BLOCK_Y - 1) // BLOCK_Y)
+    # tiles + 1 rows: the last one receives the row hull of the mask (the band), which K8 / K10 read through the same
+    # pointer; callers see the per-tile rows
+    ranges = torch.empty((tiles + 1, 2), dtype=torch.int32, device=dev)[:tiles]
+    prep_bytes = lib.gsr_bin_prepare_bytes(P, width, height)
+    prep = torch.empty((max(prep_bytes, 4),), dtype=torch.uint8, device=dev)
+    args = (P, width, height, _ptr(means2D), _ptr(depths), _ptr(radii), _ptr(conic_opacity), _ptr(compute_locally),
+            _ptr(prep), prep_bytes)
+    return P, dev, ranges, prep, args
+
+
 def _bin_gaussians_captured(cap_ctx, means2D, depths, radii, conic_opacity, compute_locally, width, height):
     """K3-K7 inside a hipGraph capture: the tile sort is launched for a CAPACITY taken from earlier iterations, the pair
     count stays on the device (copied to a pinned word the host reads after the replay) and a count above the capacity
     raises FLAG_PAIRS instead of a re-sort.  Returns the capacity as D."""
-    P = means2D.shape[0]
-    dev = means2D.device
-    gx, gy = (width + BLOCK_X - 1) // BLOCK_X, (height + BLOCK_Y - 1) // BLOCK_Y
-    ranges = torch.empty((gx * gy + 1, 2), dtype=torch.int32, device=dev)[:gx * gy]
-    prep_bytes = lib.gsr_bin_prepare_bytes(P, width, height)
-    prep = torch.empty((max(prep_bytes, 4),), dtype=torch.uint8, device=dev)
+    P, dev, ranges, prep, args = _bin_workspaces(means2D, depths, radii, conic_opacity, compute_locally, width, height)
     stream = _stream()
     ticket = ctypes.c_uint32(0)
-    check(lib.gsr_bin_prepare_async(P, width, height, _ptr(means2D), _ptr(depths), _ptr(radii), _ptr(conic_opacity),
-                                    _ptr(compute_locally), _ptr(prep), prep_bytes, ctypes.byref(ticket), stream),
-          "gsr_bin_prepare_async")
+    check(lib.gsr_bin_prepare_async(*args, ctypes.byref(ticket), stream), "gsr_bin_prepare_async")
     cap = cap_ctx.pair_capacity(dev)
     if int(lib.gsr_bin_sort_capacity(P, lib.gsr_bin_sort_bytes(P, cap, width, height), width, height)) < cap:
         raise RuntimeError("graph capture: frames above 256 x 256 tiles have no bounded tile sort")
@@ -1041,14 +1050,7 @@ def bin_gaussians(means2D, depths, radii, conic_opacity, compute_locally, width,
     can reach alpha >= 1/255 somewhere in the tile's neighbourhood (see include/gsraster.h)."""
     if _CAPTURE[0] is not None:
         return _bin_gaussians_captured(_CAPTURE[0], means2D, depths, radii, conic_opacity, compute_locally, width, height)
-    P = means2D.shape[0]
-    dev = means2D.device
-    gx, gy = (width + BLOCK_X - 1) // BLOCK_X, (height + BLOCK_Y - 1) // BLOCK_Y
-    # tiles + 1 rows: the last one receives the row hull of the mask (the band), which K8 / K10 read through the same
-    # pointer; callers see the per-tile rows
-    ranges = torch.empty((gx * gy + 1, 2), dtype=torch.int32, device=dev)[:gx * gy]
-    prep_bytes = lib.gsr_bin_prepare_bytes(P, width, height)
-    prep = torch.empty((max(prep_bytes, 4),), dtype=torch.uint8, device=dev)
+    P, dev, ranges, prep, args = _bin_workspaces(means2D, depths, radii, conic_opacity, compute_locally, width, height)
     if _DEBUG_RANGES:
         _debug_overlap("prep", prep)
         _debug_overlap("means2D", means2D)
@@ -1066,9 +1068,7 @@ def bin_gaussians(means2D, depths, radii, conic_opacity, compute_locally, width,
     if _zhx_on(cuda_args):
         # the native timer log wants the reference's two stages apart (analyze_statistic.py:1972-1991): two host calls
         with zhx_range(cuda_args, "24 updateDistributedStatLocally.updateTileTouched time"):
-            check(lib.gsr_bin_prepare_async(P, width, height, _ptr(means2D), _ptr(depths), _ptr(radii),
-                                            _ptr(conic_opacity), _ptr(compute_locally), _ptr(prep), prep_bytes,
-                                            ctypes.byref(ticket), stream), "gsr_bin_prepare_async")
+            check(lib.gsr_bin_prepare_async(*args, ctypes.byref(ticket), stream), "gsr_bin_prepare_async")
         if cap > 0 and ticket.value != 0:
             with zhx_range(cuda_args, "50 SortPairs time"):
                 check(lib.gsr_bin_sort_bounded(P, width, height, _ptr(compute_locally), _ptr(prep), cap, _ptr(kept),
@@ -1077,9 +1077,7 @@ def bin_gaussians(means2D, depths, radii, conic_opacity, compute_locally, width,
             sorted_.value = 1
     else:
         # ONE host-side call: K3-K4 and the tile sort at the scratch's capacity (include/gsraster.h)
-        check(lib.gsr_bin_speculative_async(P, width, height, _ptr(means2D), _ptr(depths), _ptr(radii),
-                                            _ptr(conic_opacity), _ptr(compute_locally), _ptr(prep), prep_bytes,
-                                            cap if cap > 0 else 0, _ptr(kept) if cap > 0 else None,
+        check(lib.gsr_bin_speculative_async(*args, cap if cap > 0 else 0, _ptr(kept) if cap > 0 else None,
                                             kept.numel() if cap > 0 else 0, _ptr(point_list) if cap > 0 else None,
                                             _ptr(ranges), ctypes.byref(ticket), ctypes.byref(sorted_), stream),
               "gsr_bin_speculative_async")

@@ -89,7 +89,7 @@ def _prepare(inp, mask, monkeypatch, lsd):
     dgr.check(lib.gsr_bin_count_wait(ticket.value, ctypes.byref(D), stream), "gsr_bin_count_wait")
     torch.cuda.synchronize()
     t, G = _timeline()
-    # the workspace: tiles_touched at 0, segoff one (P + 1)-word array further, the sorted ids two more (csrc/binning.hip:
+    # the workspace: tiles_touched at 0, segoff one (P + 1)-word array further, the sorted ids two more (csrc/binning_host.h:
     # prep_layout); the two totals sit behind their arrays at the offsets the library names
     words = prep.view(torch.int32)
     off_o = lib.gsr_bin_total_offset(P, W, H) // 4 - P

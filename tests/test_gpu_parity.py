@@ -327,7 +327,10 @@ def test_late_pair_count_equals_the_polled_path_and_survives_an_overflow(device)
         dgr.release_workspaces()
 
 
-def _binning_views(device, W=333, H=211):
+_BINNING_VIEWS = ((3000, 0.02, 5), (9000, 0.03, 6), (20000, 0.06, 7), (9000, 0.05, 8))  # (Gaussians, scale, seed)
+
+
+def _binning_views(device, W=333, H=211, specs=_BINNING_VIEWS, ragged=False):
     from oracle import cref as C
 
     cam = S.orbit_cameras(4, W, H)[1]
@@ -336,10 +339,109 @@ def _binning_views(device, W=333, H=211):
         g = S.make_gaussians(N, W, H, seed=seed, scale_coef=sc)
         m2, rgb, co, radii, depths, _, _ = C.preprocess_forward(*[g[k] for k in KEYS], **cam_kwargs(cam))
         mask = _full_mask(cam)
-        mask[1, :] = False
+        if ragged:  # (the mask of test_persistent_binning_equals_the_lookback_pipeline)
+            mask[2, :] = False
+            mask[-1, ::2] = False
+        else:
+            mask[1, :] = False
         return [t.to(device) for t in (m2, depths, radii, co, mask.view(-1).to(torch.uint8))]
 
-    return [inputs(3000, 0.02, 5), inputs(9000, 0.03, 6), inputs(20000, 0.06, 7), inputs(9000, 0.05, 8)]
+    return [inputs(*spec) for spec in specs]
+
+
+def _tile_lists(pl, rg):
+    """-> (entries per tile, the tiles' lists one after the other in tile order)"""
+    n = (rg[:, 1] - rg[:, 0]).long()
+    first = torch.repeat_interleave(rg[:, 0].long() - (torch.cumsum(n, 0) - n), n)
+    return n, pl[first + torch.arange(int(n.sum()), device=pl.device)]
+
+
+def test_sort_forms_alternate_on_one_kept_scratch(device, monkeypatch):
+    """Every form of K5-K7 -- row-major, persistent sort kernel, the two look-back passes, the generic tile-id sort -- on
+    ONE grow-only scratch that the form before it left dirty, with no release_workspaces() in between: what production
+    does whenever a capacity crosses the row-major threshold or PendingPairs.finish() sorts again at an exact size.
+    Each form lays the scratch out its own way and needs its own control block zero before its first kernel, so a form
+    that trusts a region another form's plan cleared fails here.  Pair count, ranges and point_list must be bit-identical
+    to a run on fresh workspaces with the look-back pipeline and the sized sort, every time.  The views are the first
+    two of test_persistent_binning_equals_the_lookback_pipeline, mask included (row 2 and half of the last row are not
+    local): the ones whose oracle pair counts are 36 245 and 203 904.  Of the forms, the persistent one can be seen to
+    have run: the device's done word advances by one per admitted barrier kernel, 3 prepare + 3 sort launches per leg,
+    and stands still in every other leg (a quiet admission refusal would turn the leg into a second look-back run).
+
+    The generic form is held to that in two parts, because it cannot meet it literally on a mask with tiles inside the
+    row hull that are not computed locally (this one has a whole row and half of another): the (row, column) forms keep
+    the pairs of such tiles in place behind an empty range, the tile-id sort moves them behind the last tile (sentinel
+    key), so the same lists start at other offsets -- measured on the parent: the last tile's range is (151152, 151230)
+    against (141980, 142058).  Its pair count, every tile's length and every tile's list must equal the reference's, and
+    count, ranges and point_list must be bit-identical to the generic form's own run on fresh workspaces."""
+    import diff_gaussian_rasterization as dgr
+
+    W, H = 333, 211
+    small, large = _binning_views(device, W, H, _BINNING_VIEWS[:2], ragged=True)
+    views = {"small": small, "large": large}
+    monkeypatch.setenv("GSR_BIN_PERSIST_MAXD", "1000000000")  # (the sort kernel whatever the pair count)
+    monkeypatch.setenv("GSR_BIN_ROWS_MIN", "1")               # (the row-major pipeline whatever the pair count)
+
+    def rows():
+        dgr.set_bin_rowmajor(True)
+
+    def persistent():
+        dgr.set_bin_rowmajor(False)
+        dgr.set_bin_persistent("both")
+
+    def lookback():
+        dgr.set_bin_persistent("off")
+
+    def generic():  # (no bounded sort: capacity 0, the sized sort on the same scratch)
+        monkeypatch.setenv("GSR_BINNING", "generic")
+
+    def fresh_reference():
+        dgr.release_workspaces()
+        out = {}
+        for name, x in views.items():
+            pl, rg, D = dgr.bin_gaussians(*x, W, H)
+            out[name] = (pl.clone(), rg.clone(), D)
+        return out
+
+    try:
+        dgr.set_bin_persistent("off")
+        dgr.set_bin_rowmajor(False)
+        dgr.set_speculative_sort(False)
+        generic()
+        ref_generic = fresh_reference()
+        monkeypatch.delenv("GSR_BINNING")
+        ref = fresh_reference()
+        print("pairs:", {name: r[2] for name, r in ref.items()})
+        assert ref["small"][2] > 2 * 4096, "every pass of the small view must have more than one radix tile"
+        assert ref["large"][2] > ref["small"][2]
+        for name in views:
+            assert ref_generic[name][2] == ref[name][2], name
+            n, lists = _tile_lists(*ref[name][:2])
+            gn, glists = _tile_lists(*ref_generic[name][:2])
+            assert torch.equal(gn, n) and torch.equal(glists, lists), name
+        dgr.set_speculative_sort(True)
+        for rnd in range(2):
+            for form in (rows, persistent, lookback, rows, generic):
+                form()
+                torch.cuda.synchronize()
+                done = dgr.bin_persist_status()["done"]
+                for name in ("large", "small", "large"):
+                    pl, rg, D = dgr.bin_gaussians(*views[name], W, H)
+                    rpl, rrg, rD = (ref_generic if form is generic else ref)[name]
+                    assert D == rD, (rnd, form.__name__, name)
+                    assert torch.equal(rg, rrg), (rnd, form.__name__, name)
+                    assert pl.numel() == D and torch.equal(pl, rpl), (rnd, form.__name__, name)
+                torch.cuda.synchronize()
+                launched = (dgr.bin_persist_status()["done"] - done) & 0xFFFFFFFF
+                print(rnd, form.__name__, "persistent launches:", launched)
+                assert launched == (6 if form is persistent else 0), (rnd, form.__name__, launched)
+                monkeypatch.delenv("GSR_BINNING", raising=False)
+    finally:
+        monkeypatch.delenv("GSR_BINNING", raising=False)
+        dgr.set_bin_persistent("env")
+        dgr.set_bin_rowmajor("env")
+        dgr.set_speculative_sort(True)
+        dgr.release_workspaces()
 
 
 @pytest.mark.parametrize("which,grid_s", [("s", None), ("s", 5), ("p", None), ("ps", 3)])
