@@ -84,11 +84,22 @@ __device__ __forceinline__ bool loss_band(const int *__restrict__ band, int rows
 constexpr int HV = (TW + 16) / 4;  // aligned 4-element vectors per halo row: columns [ox - 8, ox + TW + 8)
 static_assert(HH * HV <= LT, "one halo vector per thread");
 
-template <bool VEC>
+// Per-camera exposure (EXPO; include/gsraster.h: gsr_l1_ssim_forward_exposure): E = [A | b], 12 floats row-major [3,4] in
+// device memory, x'[c] = A[c][0] x[0] + A[c][1] x[1] + A[c][2] x[2] + b[c] for the pixels INSIDE the band; the zero padding
+// of the window is a padding of x' (0, not b).  One fixed fma chain, so that the forward's staging and the backward's
+// recomputation form the same bits, and an identity E hands x[c] through unchanged.
+__device__ __forceinline__ float expo_apply(const float *e, float x0, float x1, float x2) {
+    return fmaf(e[0], x0, fmaf(e[1], x1, fmaf(e[2], x2, e[3])));
+}
+
+// EXPO: the halo tile is staged as (x', y) from the three channels of the pixel; everything behind the staging is the
+// same code.  `expo` is not looked at by the plain instantiations.
+template <bool VEC, bool EXPO>
 __global__ void __launch_bounds__(LT)
 l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restrict__ image, long long img_cstride,
                        const uint8_t *__restrict__ gt, float *__restrict__ partials, float *__restrict__ M1,
-                       float *__restrict__ M2, float *__restrict__ M3, const int *__restrict__ band) {
+                       float *__restrict__ M2, float *__restrict__ M3, const int *__restrict__ band,
+                       const float *__restrict__ expo) {
     __shared__ v2f sXY[HH][HW + 1];     // (x, y): rendered band / ground truth
     __shared__ v2f hAB[HH][HSTR];       // horizontal pass of (x, y)
     __shared__ v2f hCD[HH][HSTR];       // ... of (x^2, y^2)
@@ -105,6 +116,12 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
     const int tid = threadIdx.x;
     const float *img_c = image + (long long)c * img_cstride + row_off;
     const uint8_t *gt_c = gt + (size_t)c * rows_cap * W;
+    float e[4] = {0.f, 0.f, 0.f, 0.f};
+    if (EXPO) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) e[i] = expo[4 * c + i];
+    }
+    const float *img_0 = image + row_off;  // EXPO: channel k of a pixel at img_0 + k * img_cstride
     if (VEC) {
         if (tid < HH * HV) {
             const int ly = tid / HV, q = tid - ly * HV;
@@ -112,7 +129,16 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
             float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
             uchar4 y = make_uchar4(0, 0, 0, 0);
             if (gy >= 0 && gy < rows && gx0 >= 0 && gx0 < W) {  // W % 4 == 0: a vector is inside or outside as a whole
-                x = *reinterpret_cast<const float4 *>(img_c + (size_t)gy * W + gx0);
+                if (EXPO) {
+                    const float *p = img_0 + (size_t)gy * W + gx0;
+                    const float4 x0 = *reinterpret_cast<const float4 *>(p);
+                    const float4 x1 = *reinterpret_cast<const float4 *>(p + img_cstride);
+                    const float4 x2 = *reinterpret_cast<const float4 *>(p + 2 * img_cstride);
+                    x = make_float4(expo_apply(e, x0.x, x1.x, x2.x), expo_apply(e, x0.y, x1.y, x2.y),
+                                    expo_apply(e, x0.z, x1.z, x2.z), expo_apply(e, x0.w, x1.w, x2.w));
+                } else {
+                    x = *reinterpret_cast<const float4 *>(img_c + (size_t)gy * W + gx0);
+                }
                 y = *reinterpret_cast<const uchar4 *>(gt_c + (size_t)gy * W + gx0);
             }
             const float xs[4] = {x.x, x.y, x.z, x.w};
@@ -129,7 +155,12 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
             const int gy = oy + ly - 5, gx = ox + lx - 5;
             v2f v = {0.f, 0.f};
             if (gy >= 0 && gy < rows && gx >= 0 && gx < W) {
-                v.x = img_c[(size_t)gy * W + gx];
+                if (EXPO) {
+                    const float *p = img_0 + (size_t)gy * W + gx;
+                    v.x = expo_apply(e, p[0], p[img_cstride], p[2 * img_cstride]);
+                } else {
+                    v.x = img_c[(size_t)gy * W + gx];
+                }
                 v.y = (float)gt_c[(size_t)gy * W + gx] * (1.0f / 255.0f);
             }
             sXY[ly][lx] = v;
@@ -368,6 +399,199 @@ __global__ void __launch_bounds__(256) l1_ssim_finalize_kernel(int nb, const flo
     }
 }
 
+// The backward with an exposure: ONE workgroup per 32x32 tile walks the three channels (the plain kernel's staging and
+// separable passes per channel), so that a thread holds g'[c] = dL/dx'[c] of its pixels for all c at once:
+//   grad_image[k] = sum_c A[c][k] g'[c]  (accumulated channel by channel in registers, stored once at the end),
+//   dL/dA[c][k] = sum_pixels g'[c] x[k],  dL/db[c] = sum_pixels g'[c]:  12 sums per workgroup, published as one row of
+// expo_partials (indexed by tile like the forward's sums; workgroups above a device band's tile count publish zeros) and
+// added up by exposure_finalize_kernel in a fixed order in fp64 -- no atomics, no scratch image, no second pass.
+template <bool VEC>
+__global__ void __launch_bounds__(LT)
+l1_ssim_backward_exposure_kernel(int rows, int W, int gxT, int gyT, const float *__restrict__ image, long long img_cstride,
+                                 const uint8_t *__restrict__ gt, const float *__restrict__ M1,
+                                 const float *__restrict__ M2, const float *__restrict__ M3,
+                                 const float *__restrict__ grad_l1_sum, const float *__restrict__ grad_ssim_sum,
+                                 float scale_l1, float scale_ssim, float *__restrict__ grad_image, long long grad_cstride,
+                                 const int *__restrict__ band, const float *__restrict__ expo,
+                                 float *__restrict__ expo_partials) {
+    __shared__ float sM[3][HH][HW + 1];
+    __shared__ float hor[3][HH][HSTR];
+    __shared__ float red[12][LT / 64];
+    int c0, ox, oy, nwg;
+    long long row_off;
+    const int rows_cap = rows;
+    if (!loss_band(band, rows_cap, W, gxT, rows, gyT, nwg, row_off)) {  // (the grid is one workgroup per tile)
+        if (threadIdx.x < 12) expo_partials[12 * (size_t)blockIdx.x + threadIdx.x] = 0.f;
+        return;
+    }
+    const int tile_id = loss_tile(gxT, gyT, c0, ox, oy, nwg);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tx = tid % TW, ty0 = (tid / TW) * VO;
+    const int gx = ox + tx;
+    const float gl1 = grad_l1_sum[0] * scale_l1, gss = grad_ssim_sum[0] * scale_ssim;
+    float xin[3][VO], gout[3][VO];
+    bool ok[VO];
+#pragma unroll
+    for (int o = 0; o < VO; o++) {
+        const int gy = oy + ty0 + o;
+        ok[o] = gx < W && gy < rows;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            xin[k][o] = ok[o] ? image[(long long)k * img_cstride + row_off + (size_t)gy * W + gx] : 0.f;
+            gout[k][o] = 0.f;
+        }
+    }
+#pragma unroll 1
+    for (int c = 0; c < 3; c++) {
+        const size_t cbase = (size_t)c * rows_cap * W;
+        if (VEC) {
+            if (tid < HH * HV) {
+                const int ly = tid / HV, q = tid - ly * HV;
+                const int gy = oy + ly - 5, gx0 = ox - 8 + 4 * q;
+                float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, d = a;
+                if (gy >= 0 && gy < rows && gx0 >= 0 && gx0 < W) {
+                    const size_t o = cbase + (size_t)gy * W + gx0;
+                    a = *reinterpret_cast<const float4 *>(M1 + o);
+                    b = *reinterpret_cast<const float4 *>(M2 + o);
+                    d = *reinterpret_cast<const float4 *>(M3 + o);
+                }
+                const float as[4] = {a.x, a.y, a.z, a.w}, bs[4] = {b.x, b.y, b.z, b.w}, ds[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int lx = 4 * q - 3 + i;
+                    if (lx >= 0 && lx < HW) {
+                        sM[0][ly][lx] = as[i];
+                        sM[1][ly][lx] = bs[i];
+                        sM[2][ly][lx] = ds[i];
+                    }
+                }
+            }
+        } else {
+            for (int idx = tid; idx < HH * HW; idx += LT) {
+                const int ly = idx / HW, lx = idx % HW;
+                const int gy = oy + ly - 5, gxh = ox + lx - 5;
+                float a = 0.f, b = 0.f, d = 0.f;
+                if (gy >= 0 && gy < rows && gxh >= 0 && gxh < W) {
+                    const size_t o = cbase + (size_t)gy * W + gxh;
+                    a = M1[o];
+                    b = M2[o];
+                    d = M3[o];
+                }
+                sM[0][ly][lx] = a;
+                sM[1][ly][lx] = b;
+                sM[2][ly][lx] = d;
+            }
+        }
+        __syncthreads();  // (also: every thread is past the previous channel's reads of `hor`)
+        for (int task = tid; task < HH * (TW / 4); task += LT) {
+            const int r = task / (TW / 4), cx0 = (task % (TW / 4)) * 4;
+#pragma unroll
+            for (int m = 0; m < 3; m++) {
+                float v[14];
+#pragma unroll
+                for (int i = 0; i < 14; i++) v[i] = sM[m][r][cx0 + i];
+#pragma unroll
+                for (int o = 0; o < 4; o++) {
+                    float a = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 11; k++) a = fmaf(WIN[k], v[o + k], a);
+                    hor[m][r][cx0 + o] = a;
+                }
+            }
+        }
+        __syncthreads();
+        float cv[3][VO];
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            float v[10 + VO];
+#pragma unroll
+            for (int i = 0; i < 10 + VO; i++) v[i] = hor[m][ty0 + i][tx];
+#pragma unroll
+            for (int o = 0; o < VO; o++) {
+                float a = 0.f;
+#pragma unroll
+                for (int k = 0; k < 11; k++) a = fmaf(WIN[k], v[o + k], a);
+                cv[m][o] = a;
+            }
+        }
+        float e[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) e[i] = expo[4 * c + i];
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int o = 0; o < VO; o++) {
+            float gp = 0.f;
+            if (ok[o]) {
+                const int gy = oy + ty0 + o;
+                const float x = expo_apply(e, xin[0][o], xin[1][o], xin[2][o]);
+                const float y = (float)gt[cbase + (size_t)gy * W + gx] * (1.0f / 255.0f);
+                const float d = x - y;
+                const float sgn = (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f);
+                // the plain kernel's gl1 * sgn + gss * (cv0 + 2 x cv1 + y cv2) with its roundings spelled out (every product
+                // and sum rounded, taps above as fma): with an identity E this kernel writes the plain kernel's bits
+                const float inner = __fadd_rn(__fadd_rn(cv[0][o], __fmul_rn(__fmul_rn(2.f, x), cv[1][o])),
+                                              __fmul_rn(y, cv[2][o]));
+                gp = __fadd_rn(__fmul_rn(gl1, sgn), __fmul_rn(gss, inner));
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                gout[k][o] = fmaf(e[k], gp, gout[k][o]);
+                s[k] = fmaf(gp, xin[k][o], s[k]);
+            }
+            s[3] += gp;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            float v = s[j];
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+            if (lane == 0) red[4 * c + j][wave] = v;
+        }
+    }
+    __syncthreads();
+    if (tid < 12) {
+        float r = 0.f;
+        for (int w = 0; w < LT / 64; w++) r += red[tid][w];
+        expo_partials[12 * (size_t)tile_id + tid] = r;
+    }
+#pragma unroll
+    for (int o = 0; o < VO; o++) {
+        if (!ok[o]) continue;
+        const int gy = oy + ty0 + o;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            grad_image[(long long)k * grad_cstride + row_off + (size_t)gy * W + gx] = gout[k][o];
+    }
+}
+
+// one workgroup: out12[j] = the sum of column j of the [nrows][12] partial rows, added in a fixed order in fp64 and
+// rounded once (21 groups of 12 threads walk the rows 21 apart, then the 21 group sums are added in order)
+constexpr int EXPO_GROUPS = 21;
+__global__ void __launch_bounds__(256) exposure_finalize_kernel(int nrows, const float *__restrict__ partials,
+                                                                 float *__restrict__ out12) {
+    __shared__ double red[EXPO_GROUPS][12];
+    const int t = threadIdx.x;
+    if (t < 12 * EXPO_GROUPS) {
+        const long long n = 12LL * nrows;
+        double a = 0.0;
+        for (long long i0 = t; i0 < n; i0 += 12 * EXPO_GROUPS * 8) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) v[u] = partials[min(i0 + 12 * EXPO_GROUPS * u, n - 1)];
+#pragma unroll
+            for (int u = 0; u < 8; u++)
+                if (i0 + 12 * EXPO_GROUPS * u < n) a += (double)v[u];
+        }
+        red[t / 12][t % 12] = a;
+    }
+    __syncthreads();
+    if (t < 12) {
+        double r = 0.0;
+        for (int g = 0; g < EXPO_GROUPS; g++) r += red[g][t];
+        out12[t] = (float)r;
+    }
+}
+
 }  // namespace
 
 static inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
@@ -379,7 +603,7 @@ extern "C" int gsr_l1_ssim_num_partials(int channels, int rows, int width) {
 
 static int l1_ssim_forward_impl(int channels, int rows, int width, const float *image, int64_t image_channel_stride,
                                 const uint8_t *gt, float *partials, float *dm_dmu1, float *dm_dE11, float *dm_dE12,
-                                const int *band, gsr_stream_t stream) {
+                                const int *band, const float *expo, gsr_stream_t stream) {
     if (channels <= 0 || rows < 0 || width <= 0) return GSR_EINVAL;
     if (rows == 0) return 0;
     if (!image || !gt || !partials) return GSR_EINVAL;
@@ -387,14 +611,10 @@ static int l1_ssim_forward_impl(int channels, int rows, int width, const float *
     const int gxT = gsr_div_up(width, TS), gyT = gsr_div_up(rows, TS);
     const dim3 grid(gxT * gyT * channels);
     const bool vec = width % 4 == 0 && image_channel_stride % 4 == 0 && aligned_to(image, 16) && aligned_to(gt, 4);
-    if (vec)
-        hipLaunchKernelGGL(l1_ssim_forward_kernel<true>, grid, dim3(LT), 0, reinterpret_cast<hipStream_t>(stream), rows,
-                           width, gxT, gyT, image, (long long)image_channel_stride, gt, partials, dm_dmu1, dm_dE11,
-                           dm_dE12, band);
-    else
-        hipLaunchKernelGGL(l1_ssim_forward_kernel<false>, grid, dim3(LT), 0, reinterpret_cast<hipStream_t>(stream), rows,
-                           width, gxT, gyT, image, (long long)image_channel_stride, gt, partials, dm_dmu1, dm_dE11,
-                           dm_dE12, band);
+    auto kernel = expo ? (vec ? l1_ssim_forward_kernel<true, true> : l1_ssim_forward_kernel<false, true>)
+                       : (vec ? l1_ssim_forward_kernel<true, false> : l1_ssim_forward_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(LT), 0, reinterpret_cast<hipStream_t>(stream), rows, width, gxT, gyT, image,
+                       (long long)image_channel_stride, gt, partials, dm_dmu1, dm_dE11, dm_dE12, band, expo);
     GSR_LAUNCH_CHECK();
     return 0;
 }
@@ -403,7 +623,7 @@ extern "C" int gsr_l1_ssim_forward(int channels, int rows, int width, const floa
                                    const uint8_t *gt, float *partials, float *dm_dmu1, float *dm_dE11,
                                    float *dm_dE12, gsr_stream_t stream) {
     return l1_ssim_forward_impl(channels, rows, width, image, image_channel_stride, gt, partials, dm_dmu1, dm_dE11,
-                                dm_dE12, nullptr, stream);
+                                dm_dE12, nullptr, nullptr, stream);
 }
 
 extern "C" int gsr_l1_ssim_forward_band(int channels, int rows_capacity, int width, const float *image,
@@ -412,7 +632,7 @@ extern "C" int gsr_l1_ssim_forward_band(int channels, int rows_capacity, int wid
                                         gsr_stream_t stream) {
     if (!band_rows || rows_capacity <= 0) return GSR_EINVAL;
     return l1_ssim_forward_impl(channels, rows_capacity, width, image, image_channel_stride, gt, partials, dm_dmu1,
-                                dm_dE11, dm_dE12, band_rows, stream);
+                                dm_dE11, dm_dE12, band_rows, nullptr, stream);
 }
 
 static int l1_ssim_backward_impl(int channels, int rows, int width, const float *image,
@@ -468,6 +688,51 @@ extern "C" int gsr_l1_ssim_finalize(int num_partials, const float *partials, flo
     if (num_partials < 0 || !out3 || (num_partials > 0 && !partials) || !aligned_to(partials, 8)) return GSR_EINVAL;
     hipLaunchKernelGGL(l1_ssim_finalize_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        num_partials, partials, c_l1, c_ssim, bias, inv_n, out3);
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- exposure (N1x)
+extern "C" int gsr_l1_ssim_exposure_num_partials(int rows, int width) {
+    if (rows <= 0 || width <= 0) return 0;
+    return gsr_div_up(rows, TS) * gsr_div_up(width, TS);
+}
+
+extern "C" int gsr_l1_ssim_forward_exposure(int channels, int rows_capacity, int width, const float *image,
+                                            int64_t image_channel_stride, const uint8_t *gt, float *partials,
+                                            float *dm_dmu1, float *dm_dE11, float *dm_dE12, const int32_t *band_rows,
+                                            const float *exposure, gsr_stream_t stream) {
+    if (channels != 3 || !exposure) return GSR_EINVAL;
+    if (band_rows && rows_capacity <= 0) return GSR_EINVAL;
+    return l1_ssim_forward_impl(channels, rows_capacity, width, image, image_channel_stride, gt, partials, dm_dmu1,
+                                dm_dE11, dm_dE12, band_rows, exposure, stream);
+}
+
+extern "C" int gsr_l1_ssim_backward_exposure(int channels, int rows_capacity, int width, const float *image,
+                                             int64_t image_channel_stride, const uint8_t *gt, const float *dm_dmu1,
+                                             const float *dm_dE11, const float *dm_dE12, const float *grad_l1_sum,
+                                             const float *grad_ssim_sum, float scale_l1, float scale_ssim,
+                                             float *grad_image, int64_t grad_channel_stride, const int32_t *band_rows,
+                                             const float *exposure, float *exposure_partials, float *grad_exposure,
+                                             gsr_stream_t stream) {
+    const int rows = rows_capacity;
+    if (channels != 3 || rows < 0 || width <= 0 || (band_rows && rows <= 0)) return GSR_EINVAL;
+    if (!exposure || !exposure_partials || !grad_exposure) return GSR_EINVAL;
+    if (!image || !gt || !dm_dmu1 || !dm_dE11 || !dm_dE12 || !grad_l1_sum || !grad_ssim_sum || !grad_image)
+        return GSR_EINVAL;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int gxT = gsr_div_up(width, TS), gyT = gsr_div_up(rows, TS);
+    if (rows > 0) {
+        const bool vec = width % 4 == 0 && aligned_to(dm_dmu1, 16) && aligned_to(dm_dE11, 16) && aligned_to(dm_dE12, 16);
+        auto kernel = vec ? l1_ssim_backward_exposure_kernel<true> : l1_ssim_backward_exposure_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3(gxT * gyT), dim3(LT), 0, st, rows, width, gxT, gyT, image,
+                           (long long)image_channel_stride, gt, dm_dmu1, dm_dE11, dm_dE12, grad_l1_sum, grad_ssim_sum,
+                           scale_l1, scale_ssim, grad_image, (long long)grad_channel_stride, band_rows, exposure,
+                           exposure_partials);
+        GSR_LAUNCH_CHECK();
+    }
+    // (no rows: no partial rows, the 12 sums are zeros)
+    hipLaunchKernelGGL(exposure_finalize_kernel, dim3(1), dim3(256), 0, st, gxT * gyT, exposure_partials, grad_exposure);
     GSR_LAUNCH_CHECK();
     return 0;
 }

@@ -27,7 +27,7 @@ from . import _lib
 from ._lib import check, lib
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "_C", "load_image_tiles_by_pos",
-           "merge_image_tiles_by_pos", "set_timing_mode", "fused_l1_ssim_band", "fused_band_loss", "fused_activations", "pack_camera",
+           "merge_image_tiles_by_pos", "set_timing_mode", "fused_l1_ssim_band", "fused_band_loss", "fused_band_loss_exposure", "fused_activations", "pack_camera",
            "preprocess_gaussians_raw_batched", "knn_mean_dist2", "group_rows", "gather_rows", "densify_plan", "densify_move", "exchange_need",
            "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "densify_stats",
            "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing", "image_metrics", "metrics_from_sums"]
@@ -1502,6 +1502,86 @@ def fused_band_loss(image, gt_u8, y0, y1, lambda_dssim, n, band_rows=None):
     """-> (loss, Ll1, ssim) of rows [y0, y1) of image [C,H,W]; n = H*W*3 of the full image.  band_rows (int32 [2] on
     the device): the rows are device data and gt_u8 is a [C, capacity, W] buffer (see _FusedBandLoss.forward)"""
     return _FusedBandLoss.apply(image, gt_u8, int(y0), int(y1), float(lambda_dssim), float(n), band_rows)
+
+
+class _FusedBandLossExposure(torch.autograd.Function):
+    """_FusedBandLoss of x' = A x + b, E = [A | b] the [3,4] exposure of the camera (include/gsraster.h, N1x): x' is
+    formed inside the forward's staging and recomputed by the backward, which writes dL/dimage = A^T g' and reduces the 12
+    sums of dL/dE (per-tile rows + a fixed-order fp64 finalize).  Same launch count as _FusedBandLoss plus that
+    finalize; `exposure` is read on the device.  Returns (loss, Ll1, ssim); the last two are detached."""
+
+    @staticmethod
+    def forward(ctx, image, exposure, gt_u8, y0, y1, lambda_dssim, n, band_rows=None):
+        if not image.is_cuda or not exposure.is_cuda:
+            raise RuntimeError("fused_band_loss_exposure: device tensors required (no CPU fallback)")
+        ctx.set_materialize_grads(False)
+        image = image.float().contiguous()
+        C, H, W = image.shape
+        if C != 3 or tuple(exposure.shape) != (3, 4):
+            raise ValueError(f"exposure compensation needs a [3,H,W] image and a [3,4] exposure, got "
+                             f"{tuple(image.shape)} and {tuple(exposure.shape)}")
+        exposure = exposure.float().contiguous()
+        gt_u8 = gt_u8.contiguous()
+        dyn = band_rows is not None
+        if dyn and (band_rows.dtype != torch.int32 or not band_rows.is_cuda or band_rows.numel() < 2):
+            raise ValueError("band_rows must be an int32 device tensor { y0, y1 }")
+        rows = int(gt_u8.shape[1]) if dyn else y1 - y0
+        if gt_u8.dtype != torch.uint8 or tuple(gt_u8.shape) != (C, rows, W):
+            raise ValueError(f"gt band must be uint8 [{C},{rows},{W}], got {gt_u8.dtype} {tuple(gt_u8.shape)}")
+        dev = image.device
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        nb = lib.gsr_l1_ssim_num_partials(C, rows, W)
+        partials = torch.empty((max(nb, 1), 2), dtype=torch.float32, device=dev)
+        maps = torch.empty((3, C, rows, W), dtype=torch.float32, device=dev) if need_grad else None
+        out3 = torch.empty((3,), dtype=torch.float32, device=dev)
+        c_l1, c_ssim = (1.0 - lambda_dssim) / n, -lambda_dssim / n
+        m = [_ptr(maps[i]) if need_grad else None for i in range(3)]
+        with _on(dev):
+            with kernel_timer.range("l1_ssim_forward", Px=rows * W):
+                img_ptr = _ptr(image) if dyn else ctypes.c_void_p(image.data_ptr() + 4 * y0 * W)
+                check(lib.gsr_l1_ssim_forward_exposure(C, rows, W, img_ptr, H * W, _ptr(gt_u8), _ptr(partials), m[0],
+                                                       m[1], m[2], _ptr(band_rows), _ptr(exposure), _stream()),
+                      "gsr_l1_ssim_forward_exposure")
+            check(lib.gsr_l1_ssim_finalize(nb, _ptr(partials), c_l1, c_ssim, lambda_dssim, 1.0 / n, _ptr(out3),
+                                           _stream()), "gsr_l1_ssim_finalize")
+        ctx.y0, ctx.y1, ctx.coef, ctx.band_rows = y0, y1, (c_l1, c_ssim), band_rows
+        if need_grad:
+            ctx.save_for_backward(image, exposure, gt_u8, maps)
+        loss, Ll1, ssim = out3[0], out3[1], out3[2]
+        ctx.mark_non_differentiable(Ll1, ssim)
+        return loss, Ll1, ssim
+
+    @staticmethod
+    def backward(ctx, g_loss, _g1, _g2):
+        if g_loss is None:
+            return None, None, None, None, None, None, None, None
+        image, exposure, gt_u8, maps = ctx.saved_tensors
+        C, H, W = image.shape
+        y0, y1 = ctx.y0, ctx.y1
+        dyn = ctx.band_rows is not None
+        rows = int(gt_u8.shape[1]) if dyn else y1 - y0
+        dev = image.device
+        g_loss = g_loss if (g_loss.dtype == torch.float32 and g_loss.is_contiguous()) else g_loss.float().contiguous()
+        grad = torch.empty_like(image) if (rows == H and not dyn) else torch.zeros_like(image)
+        grad_e = torch.empty((3, 4), dtype=torch.float32, device=dev)
+        ne = lib.gsr_l1_ssim_exposure_num_partials(rows, W)
+        e_partials = torch.empty((max(ne, 1), 12), dtype=torch.float32, device=dev)
+        off = 0 if dyn else 4 * y0 * W
+        with _on(dev), kernel_timer.range("l1_ssim_backward", Px=rows * W):
+            check(lib.gsr_l1_ssim_backward_exposure(C, rows, W, ctypes.c_void_p(image.data_ptr() + off), H * W,
+                                                    _ptr(gt_u8), _ptr(maps[0]), _ptr(maps[1]), _ptr(maps[2]),
+                                                    _ptr(g_loss), _ptr(g_loss), float(ctx.coef[0]), float(ctx.coef[1]),
+                                                    ctypes.c_void_p(grad.data_ptr() + off), H * W, _ptr(ctx.band_rows),
+                                                    _ptr(exposure), _ptr(e_partials), _ptr(grad_e), _stream()),
+                  "gsr_l1_ssim_backward_exposure")
+        return grad, grad_e, None, None, None, None, None, None
+
+
+def fused_band_loss_exposure(image, exposure, gt_u8, y0, y1, lambda_dssim, n, band_rows=None):
+    """fused_band_loss of the exposure-compensated band x' = A x + b (exposure = [A | b], float32 [3,4] on the device;
+    include/gsraster.h, N1x) -> (loss, Ll1, ssim), with gradients for `image` and `exposure`"""
+    return _FusedBandLossExposure.apply(image, exposure, gt_u8, int(y0), int(y1), float(lambda_dssim), float(n),
+                                        band_rows)
 
 
 # ------------------------------------------------------------------------- a19: fused activations

@@ -23,6 +23,7 @@ import utils.general_utils as utils
 from diff_gaussian_rasterization import capturing as _capturing
 from diff_gaussian_rasterization import current_stream as _current_stream
 from diff_gaussian_rasterization import fused_band_loss as _FUSED_LOSS
+from diff_gaussian_rasterization import fused_band_loss_exposure as _FUSED_LOSS_EXPOSURE
 from diff_gaussian_rasterization import fused_l1_ssim_band as _FUSED
 
 
@@ -135,6 +136,21 @@ def load_camera_from_cpu_to_all_gpu_for_eval(batched_cameras, batched_strategies
 
 
 # ------------------------------------------------------------------------------------- loss
+_EXPOSURE_MODEL = [None]
+
+
+def set_exposure_model(model):
+    """model (exposure.ExposureModel) or None.  With a model, batched_loss_computation takes the loss of every camera on
+    x' = A x + b with model.of(camera) (fused into the loss kernels: fused_band_loss_exposure) and the backward fills the
+    model's gradient; with None (the default) the path is the plain one, call for call.  final_system_loss_computation
+    and evaluation stay uncompensated.  A graphed iteration refuses to capture while a model is set (graphed_step.py)."""
+    _EXPOSURE_MODEL[0] = model
+
+
+def get_exposure_model():
+    return _EXPOSURE_MODEL[0]
+
+
 def _timings_wanted():
     """HIP events around the loss only when somebody reads the timing (workload_division.timings_have_consumer)"""
     from gaussian_renderer.workload_division import timings_have_consumer
@@ -206,8 +222,13 @@ def batched_loss_computation(batched_image, batched_cameras, batched_compute_loc
             cap = _capturing()
             if cap is not None:  # (a hipGraph capture: device timestamps instead of events, graphed_step.py)
                 cap.stamp("loss0", id(stats))
-            loss, Ll1, ssim = _FUSED_LOSS(image, camera.original_image, y0, y1, args.lambda_dssim,
-                                          utils.get_num_pixels() * 3, band_rows)
+            model = _EXPOSURE_MODEL[0]
+            if model is None:
+                loss, Ll1, ssim = _FUSED_LOSS(image, camera.original_image, y0, y1, args.lambda_dssim,
+                                              utils.get_num_pixels() * 3, band_rows)
+            else:
+                loss, Ll1, ssim = _FUSED_LOSS_EXPOSURE(image, model.of(camera), camera.original_image, y0, y1,
+                                                       args.lambda_dssim, utils.get_num_pixels() * 3, band_rows)
             if cap is not None:
                 cap.stamp("loss1", id(stats))
             if timed:

@@ -556,6 +556,14 @@ class GraphedIteration:
         if not self.enabled:
             self.stats["eager"] += 1
             return self.body(cameras, strategies, tasks)
+        from gaussian_renderer.loss_distribution import get_exposure_model
+
+        if get_exposure_model() is not None:
+            # a replay would have to read the camera's row of the exposure parameter as device data (a follow-up): nothing
+            # is warmed up or captured
+            raise RuntimeError("GraphedIteration: an exposure model is set (loss_distribution.set_exposure_model); "
+                               "exposure compensation is not captured -- run it eagerly "
+                               "(GraphedIteration(..., enabled=False) or call the body directly)")
         for camera in cameras:
             if any(torch.is_tensor(t) and t.requires_grad for t in
                    (camera.world_view_transform, camera.full_proj_transform, camera.camera_center)):

@@ -371,6 +371,47 @@ int gsr_l1_ssim_finalize(int num_partials, const float *partials, float c_l1, fl
                          float *out3, gsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N1x  per-camera exposure compensation fused into N1.  `exposure` E = [A | b]: 12 floats on the device, row-major
+ * [3,4], read by the kernels (a captured launch serves changing values).  For every pixel INSIDE the band
+ *   x'[c] = A[c][0] x[0] + A[c][1] x[1] + A[c][2] x[2] + b[c]     (no clamp)
+ * and the loss is N1's band-local loss of x' against the ground truth: same window, constants, y = u8 * (1/255f), sums
+ * and derivative maps.  The zero padding of the SSIM window is a padding of x': outside the band's rows and the image's
+ * columns x' is exactly 0 -- not b, and not a transform of what lies in memory there.  Gradients, with
+ * g'[c] = dL/dx'[c] (what gsr_l1_ssim_backward writes for its input):
+ *   dL/dx[k] = sum_c A[c][k] g'[c],   dL/dA[c][k] = sum_pixels g'[c] x[k],   dL/db[c] = sum_pixels g'[c].
+ * There is no reference call site (the reference has no exposure model); the arbiter is the fp64 torch restatement of
+ * the lines above (tests/test_gpu_exposure_loss.py).  channels must be 3.
+ *
+ * gsr_l1_ssim_forward_exposure: the arguments of gsr_l1_ssim_forward_band plus `exposure`.  band_rows == NULL selects
+ * the static form: `image` then points at the band's first row and rows_capacity is the row count.  Partials: layout
+ * and count of the plain launch of the same shape (gsr_l1_ssim_num_partials; gsr_l1_ssim_finalize adds them up).  With
+ * an identity E every output is bit-equal to the plain launch's.  No reference call site; arbiter as above.
+ * GSR_EINVAL before any device work: channels != 3, a null exposure / image / gt / partials, one or two null maps. */
+int gsr_l1_ssim_forward_exposure(int channels, int rows_capacity, int width, const float *image,
+                                 int64_t image_channel_stride, const uint8_t *gt, float *partials, float *dm_dmu1,
+                                 float *dm_dE11, float *dm_dE12, const int32_t *band_rows, const float *exposure,
+                                 gsr_stream_t stream);
+/* The number of 12-float rows gsr_l1_ssim_backward_exposure writes to exposure_partials: one per 32x32 tile of the
+ * band (of the capacity, for a device band).  Pure host arithmetic; exists for the exposure model only (no reference
+ * call site). */
+int gsr_l1_ssim_exposure_num_partials(int rows, int width);
+/* gsr_l1_ssim_backward_exposure: the arguments of gsr_l1_ssim_backward_band (band_rows optional as in the forward) plus
+ * `exposure`, exposure_partials [gsr_l1_ssim_exposure_num_partials(rows_capacity, width)][12] (scratch, fully written:
+ * per tile the sums dL/dA[c][k] at [4c + k], dL/db[c] at [4c + 3]; the rows above a device band's own tile count
+ * receive zeros) and grad_exposure (12 floats, row-major [3,4], fully overwritten).  One workgroup per tile recomputes
+ * x' at its pixels, walks the three channels for g', writes grad_image = A^T g' (the band's rows of all three
+ * channels) and publishes its 12 sums; a second launch adds the rows in a fixed order in fp64 and rounds each sum
+ * once: no atomics, bit-identical from run to run.  The definition is the one at the head of this section; no reference
+ * call site, the arbiter is the fp64 torch restatement.  GSR_EINVAL before any device work: channels != 3, a null
+ * exposure / exposure_partials / grad_exposure or any null pointer gsr_l1_ssim_backward refuses. */
+int gsr_l1_ssim_backward_exposure(int channels, int rows_capacity, int width, const float *image,
+                                  int64_t image_channel_stride, const uint8_t *gt, const float *dm_dmu1,
+                                  const float *dm_dE11, const float *dm_dE12, const float *grad_l1_sum,
+                                  const float *grad_ssim_sum, float scale_l1, float scale_ssim, float *grad_image,
+                                  int64_t grad_channel_stride, const int32_t *band_rows, const float *exposure,
+                                  float *exposure_partials, float *grad_exposure, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N1e  fused evaluation metrics of one row band, forward only -- what training_report prints
  * (train_internal.py:471-478: clamp both, l1_loss(...).mean(), psnr(...).mean()), the per-channel PSNR of
  * utils/image_utils.py:19-21, and the SSIM / PSNR metrics.py:78-79 takes of the saved PNGs -- as SUMS over the rows
