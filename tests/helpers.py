@@ -155,3 +155,54 @@ def assert_elem_close(got, ref64, ref32, K=8, what=""):
                              f"{r64.reshape(-1)[worst].item():.9g}, error / unit = {ratio:.3g} > K = {K} "
                              f"(unit = {unit:.3g})")
     return ratio
+
+
+# ---------------------------------------------------------------------------- row-wise check against fp64
+ROW_UNIT_FLOOR = 4.0 * 2.0 ** -24    # four half-ulps of the row's largest value
+ROW_UNIT_CAP = 4096.0 * 2.0 ** -24   # 2.4e-4: a case whose reference is worse conditioned than this gets other inputs
+
+
+def rows_unit(ref64, ref32):
+    """the worst per-row relative error of a plain fp32 implementation on these inputs: max(ROW_UNIT_FLOOR, max over the
+    rows with s_i > 0 of e32_i / s_i), s_i = max_c |ref64[i,c]|, e32_i = max_c |ref32[i,c] - ref64[i,c]|.  ref32 is the
+    same reference code run in float32 on the CPU, never the kernel's result."""
+    r64, r32 = ref64.detach().double().cpu(), ref32.detach().double().cpu()
+    assert r64.shape == r32.shape, f"shape {tuple(r64.shape)} != {tuple(r32.shape)}"
+    if r64.numel() == 0:
+        return ROW_UNIT_FLOOR
+    r64, r32 = r64.reshape(r64.shape[0], -1), r32.reshape(r32.shape[0], -1)
+    s = r64.abs().amax(dim=1)
+    e32 = (r32 - r64).abs().amax(dim=1)
+    assert not bool(torch.isnan(s).any() | torch.isnan(e32).any()), "NaN in the reference"
+    live = s > 0
+    worst = float((e32[live] / s[live]).max()) if bool(live.any()) else 0.0
+    return max(ROW_UNIT_FLOOR, worst)
+
+
+def assert_rows_close(got, ref64, ref32, K=8, what=""):
+    """every row i of [N, ...] tensors (flattened to [N, C]), nothing excluded:
+        max_c |got[i,c] - ref64[i,c]| <= K * unit * s_i,   s_i = max_c |ref64[i,c]|,   unit = rows_unit(ref64, ref32);
+    a row with s_i == 0 must be exactly zero in `got`; a NaN fails.  unit <= ROW_UNIT_CAP is asserted before `got` is
+    looked at (a cap on the case's conditioning, not a measurement).  -> (unit, worst err_i / (unit * s_i))"""
+    unit = rows_unit(ref64, ref32)
+    assert unit <= ROW_UNIT_CAP, (f"{what}: the fp32 reference is off by {unit / 2.0 ** -24:.0f} x 2^-24 of a row's largest "
+                                  f"value, over the cap of {ROW_UNIT_CAP / 2.0 ** -24:.0f}: change the inputs of this case")
+    g, r64 = got.detach().double().cpu(), ref64.detach().double().cpu()
+    assert g.shape == r64.shape, f"{what}: shape {tuple(g.shape)} != {tuple(r64.shape)}"
+    if r64.numel() == 0:
+        return unit, 0.0
+    g, r64 = g.reshape(g.shape[0], -1), r64.reshape(r64.shape[0], -1)
+    s = r64.abs().amax(dim=1, keepdim=True)
+    err = (g - r64).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)
+    # ratio per element; on a zero row any non-zero (or NaN) entry is infinitely far off
+    ratio = torch.where(s > 0, err / (unit * s.clamp(min=1e-300)),
+                        torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
+    worst = int(ratio.reshape(-1).argmax())
+    i, c = divmod(worst, ratio.shape[1])
+    w = float(ratio[i, c])
+    if not w <= K:
+        raise AssertionError(f"{what}: row {i}, column {c}: got {float(g[i, c]):.9g}, fp64 reference "
+                             f"{float(r64[i, c]):.9g}, error / (unit * row max) = {w:.3g} > K = {K} "
+                             f"(unit = {unit:.3g}, row max = {float(s[i, 0]):.3g})")
+    return unit, w
