@@ -41,7 +41,7 @@ int gsr_preprocess_forward(int P, int sh_degree, int sh_coeffs, const float *mea
     return gsr_launch_preprocess_forward(P, sh_degree, sh_coeffs, means3D, scales, scale_modifier, rotations, shs,
                                          nullptr, opacities, viewmatrix, projmatrix, campos, width, height, tanfovx, tanfovy,
                                          means2D, depths, radii, cov3D, conic_opacity, rgb, clamped,
-                                         reinterpret_cast<hipStream_t>(stream));
+                                         gsr_antialiasing_mode(), reinterpret_cast<hipStream_t>(stream));
 }
 
 int gsr_preprocess_backward(int P, int sh_degree, int sh_coeffs, const float *means3D, const float *scales,
@@ -55,6 +55,7 @@ int gsr_preprocess_backward(int P, int sh_degree, int sh_coeffs, const float *me
         height <= 0 || !(tanfovx > 0.f) || !(tanfovy > 0.f) || grad_row_stride < 0)
         return GSR_EINVAL;
     if (P == 0) return 0;
+    if (gsr_antialiasing_mode() != 0) return GSR_EINVAL;  // needs the opacity: gsr_preprocess_backward_aa
     if (!means3D || !scales || !rotations || !shs || !viewmatrix || !projmatrix || !campos || !radii || !cov3D ||
         !clamped || !dL_dmeans2D || !dL_dconic_opacity || !dL_drgb || !dL_dmeans3D || !dL_dscales || !dL_drotations ||
         !dL_dshs || !dL_dopacities)
@@ -62,7 +63,31 @@ int gsr_preprocess_backward(int P, int sh_degree, int sh_coeffs, const float *me
     return gsr_launch_preprocess_backward(P, sh_degree, sh_coeffs, means3D, scales, scale_modifier, rotations, shs,
                                           nullptr, nullptr, viewmatrix, projmatrix, campos, width, height, tanfovx, tanfovy, radii,
                                           cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride,
-                                          dL_dmeans3D, dL_dscales, dL_drotations, dL_dshs, nullptr, dL_dopacities,
+                                          dL_dmeans3D, dL_dscales, dL_drotations, dL_dshs, nullptr, dL_dopacities, 0,
+                                          reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_preprocess_backward_aa(int P, int sh_degree, int sh_coeffs, const float *means3D, const float *scales,
+                               float scale_modifier, const float *rotations, const float *shs, const float *opacities,
+                               const float *viewmatrix, const float *projmatrix, const float *campos, int width,
+                               int height, float tanfovx, float tanfovy, const int32_t *radii, const float *cov3D,
+                               const uint8_t *clamped, const float *dL_dmeans2D, const float *dL_dconic_opacity,
+                               const float *dL_drgb, int grad_row_stride, float *dL_dmeans3D, float *dL_dscales,
+                               float *dL_drotations, float *dL_dshs, float *dL_dopacities, gsr_stream_t stream) {
+    if (P < 0 || sh_degree < 0 || sh_degree > 3 || sh_coeffs < (sh_degree + 1) * (sh_degree + 1) || width <= 0 ||
+        height <= 0 || !(tanfovx > 0.f) || !(tanfovy > 0.f) || grad_row_stride < 0)
+        return GSR_EINVAL;
+    if (P == 0) return 0;
+    const int aa = gsr_antialiasing_mode();
+    if (!means3D || !scales || !rotations || !shs || (aa && !opacities) || !viewmatrix || !projmatrix || !campos ||
+        !radii || !cov3D || !clamped || !dL_dmeans2D || !dL_dconic_opacity || !dL_drgb || !dL_dmeans3D || !dL_dscales ||
+        !dL_drotations || !dL_dshs || !dL_dopacities)
+        return GSR_EINVAL;
+    return gsr_launch_preprocess_backward(P, sh_degree, sh_coeffs, means3D, scales, scale_modifier, rotations, shs,
+                                          nullptr, aa ? opacities : nullptr, viewmatrix, projmatrix, campos, width,
+                                          height, tanfovx, tanfovy, radii, cov3D, clamped, dL_dmeans2D,
+                                          dL_dconic_opacity, dL_drgb, grad_row_stride, dL_dmeans3D, dL_dscales,
+                                          dL_drotations, dL_dshs, nullptr, dL_dopacities, aa,
                                           reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -82,7 +107,7 @@ int gsr_preprocess_forward_raw(int P, int sh_degree, int sh_coeffs, const float 
     return gsr_launch_preprocess_forward(P, sh_degree, sh_coeffs, xyz, scaling, scale_modifier, rotation, features_dc,
                                          features_rest, opacity, viewmatrix, projmatrix, campos, width, height,
                                          tanfovx, tanfovy, means2D, depths, radii, cov3D, conic_opacity, rgb, clamped,
-                                         reinterpret_cast<hipStream_t>(stream));
+                                         gsr_antialiasing_mode(), reinterpret_cast<hipStream_t>(stream));
 }
 
 int gsr_preprocess_backward_raw(int P, int sh_degree, int sh_coeffs, const float *xyz, const float *scaling,
@@ -106,7 +131,8 @@ int gsr_preprocess_backward_raw(int P, int sh_degree, int sh_coeffs, const float
                                           features_rest, opacity, viewmatrix, projmatrix, campos, width, height,
                                           tanfovx, tanfovy, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity,
                                           dL_drgb, grad_row_stride, dL_dxyz, dL_dscaling, dL_drotation, dL_dfeatures_dc,
-                                          dL_dfeatures_rest, dL_dopacity, reinterpret_cast<hipStream_t>(stream));
+                                          dL_dfeatures_rest, dL_dopacity, gsr_antialiasing_mode(),
+                                          reinterpret_cast<hipStream_t>(stream));
 }
 
 int gsr_get_local2j_ids_bool(int P, int width, int height, int world_size, const float *means2D,

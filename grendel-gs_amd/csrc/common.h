@@ -132,7 +132,7 @@ int gsr_launch_preprocess_forward(int P, int D, int M, const float *means3D, con
                                   const float *opacities,
                                   const float *viewmatrix, const float *projmatrix, const float *campos, int W, int H,
                                   float tanfovx, float tanfovy, float *means2D, float *depths, int32_t *radii,
-                                  float *cov3D, float *conic_opacity, float *rgb, uint8_t *clamped,
+                                  float *cov3D, float *conic_opacity, float *rgb, uint8_t *clamped, int aa,
                                   hipStream_t stream);
 int gsr_launch_preprocess_backward(int P, int D, int M, const float *means3D, const float *scales,
                                    float scale_modifier, const float *rotations, const float *shs,
@@ -140,7 +140,11 @@ int gsr_launch_preprocess_backward(int P, int D, int M, const float *means3D, co
                                    int H, float tanfovx, float tanfovy, const int32_t *radii, const float *cov3D,
                                    const uint8_t *clamped, const float *dL_dmeans2D, const float *dL_dconic_opacity,
                                    const float *dL_drgb, int grad_row_stride, float *dL_dmeans3D, float *dL_dscales, float *dL_drotations,
-                                   float *dL_dshs, float *dL_dshs_rest, float *dL_dopacities, hipStream_t stream);
+                                   float *dL_dshs, float *dL_dshs_rest, float *dL_dopacities, int aa,
+                                   hipStream_t stream);
+// `aa` above: the anti-aliasing mode that the entry point read with gsr_antialiasing_mode(), once per call.  With
+// aa = 1 and activated inputs (shs_rest == NULL) the backward reads the ACTIVATED opacity through `opacities_raw`.
+int gsr_antialiasing_mode();
 int gsr_launch_local2j(int P, int W, int H, int ws, const float *means2D, const int32_t *radii, const int32_t *div,
                        uint8_t *out, hipStream_t stream);
 

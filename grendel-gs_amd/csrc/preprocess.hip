@@ -10,6 +10,7 @@
 // off so that integer outputs (radii, tile rects) are reproducible against a plain C evaluation.
 #include "common.h"
 
+#include <atomic>
 #include <initializer_list>
 #include <type_traits>
 
@@ -152,18 +153,30 @@ __device__ __forceinline__ void cov3d_unpack(const float *cv, float (&S)[3][3]) 
     S[2][0] = cv[2]; S[2][1] = cv[4]; S[2][2] = cv[5];
 }
 
-// cov2D = T Sigma T^T + 0.3 I = [[a, b], [b, c]]; ST0 / ST1 = Sigma T^T's columns, which the backward needs again
+// cov2D = T Sigma T^T + 0.3 I = [[a, b], [b, c]]; ST0 / ST1 = Sigma T^T's columns, which the backward needs again.
+// a0, c0: the diagonal BEFORE the dilation, for the anti-aliased variant (taken here, not a - 0.3f afterwards: that
+// difference has lost a0's low bits wherever a0 < 0.3); a caller that does not use them pays nothing.
 __device__ __forceinline__ void cov2d_abc(const float (&S)[3][3], const float (&T)[2][3], float (&ST0)[3],
-                                          float (&ST1)[3], float &a, float &b, float &c) {
+                                          float (&ST1)[3], float &a, float &b, float &c, float &a0, float &c0) {
 #pragma unroll
     for (int r = 0; r < 3; r++) {
         ST0[r] = S[r][0] * T[0][0] + S[r][1] * T[0][1] + S[r][2] * T[0][2];
         ST1[r] = S[r][0] * T[1][0] + S[r][1] * T[1][1] + S[r][2] * T[1][2];
     }
-    a = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2] + 0.3f;
+    a0 = T[0][0] * ST0[0] + T[0][1] * ST0[1] + T[0][2] * ST0[2];
+    a = a0 + 0.3f;
     b = T[0][0] * ST1[0] + T[0][1] * ST1[1] + T[0][2] * ST1[2];
-    c = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2] + 0.3f;
+    c0 = T[1][0] * ST1[0] + T[1][1] * ST1[1] + T[1][2] * ST1[2];
+    c = c0 + 0.3f;
 }
+
+// ---- anti-aliasing (the 2D Mip filter; include/gsraster.h: gsr_set_antialiasing).  AA is a template argument of every
+// piece and kernel below that it reaches: the AA = false instantiations are the code without it, instruction for
+// instruction.  q = det0 / det, the share of the dilated splat's energy that the undilated one had; the opacity is
+// scaled by rho = sqrt(max(AA_QMIN, q)), 0.005 <= rho < 1.
+constexpr float AA_QMIN = 0.000025f;
+__device__ __forceinline__ float aa_q(float a0, float b, float c0, float det) { return (a0 * c0 - b * b) / det; }
+__device__ __forceinline__ float aa_rho(float q) { return sqrtf(fmaxf(AA_QMIN, q)); }
 
 // The geometry of one (Gaussian, camera) pair in front of the near plane (the caller culls t[2] <= 0.2 BEFORE it loads
 // what Sigma is made of): conic, radius and pixel centre.  false: culled (singular cov2D, or a rect of no tiles); g is
@@ -173,7 +186,9 @@ struct Geom2D {
     int rad;
     float2 xy;
     float conic[3];
+    float rho;  // AA: the opacity's factor (1 otherwise)
 };
+template <bool AA>
 __device__ __forceinline__ bool project_geometry(const Cam &cam, float tanfovx, float tanfovy, float fx, float fy, int W,
                                                  int H, int gx, int gy, const float (&p)[3], const float (&t)[3],
                                                  const float (&S)[3][3], Geom2D &g) {
@@ -183,10 +198,11 @@ __device__ __forceinline__ bool project_geometry(const Cam &cam, float tanfovx, 
     float T[2][3], tc[3];
     bool xin, yin;
     compute_T(t, cam.v, fx, fy, tanfovx, tanfovy, T, tc, xin, yin);
-    float ST0[3], ST1[3], a, b, c;
-    cov2d_abc(S, T, ST0, ST1, a, b, c);
+    float ST0[3], ST1[3], a, b, c, a0, c0;
+    cov2d_abc(S, T, ST0, ST1, a, b, c, a0, c0);
     const float det = a * c - b * b;
     const float det_inv = 1.f / det;
+    g.rho = AA ? aa_rho(aa_q(a0, b, c0, det)) : 1.f;
     const float mid = 0.5f * (a + c);
     const float lam = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
     g.rad = (int)ceilf(3.f * sqrtf(lam));
@@ -226,20 +242,28 @@ struct Cov2DGrad {
     float dT0[3], dT1[3];
     float dt[3], tc[3];  // dL/dt, and t with the Jacobian's clamp
     float dmean[3];      // dt through the view matrix: the pair's cov2D part of dL/dmean
+    float rho;           // AA: the forward's factor of the opacity, recomputed (1 otherwise)
 };
+// AA: gop = dL/dconic_opacity.w times the uncompensated opacity.  With w = gop / (2 rho) = dL/dq, w dq/d(a, b, c) joins
+// the conic's dL/d(a, b, c) before these feed dcov, dT and dt -- unless the forward clamped q (q <= AA_QMIN: rho is then
+// a constant).  dq/d(a, b, c) in closed form, h = det - det0 = 0.3 (a0 + c0) + 0.09 (the quotient rule's
+// c0 det - det0 c cancels for large splats, q -> 1), over the TRUE det^2, not the conic part's det^2 + 1e-7.
+template <bool AA = false>
 __device__ __forceinline__ Cov2DGrad cov2d_backward(const float *v, float fx, float fy, float tanfovx, float tanfovy,
                                                     const float (&p)[3], const float (&S)[3][3], float gA, float gB,
-                                                    float gC) {
+                                                    float gC, float gop = 0.f) {
     Cov2DGrad o;
     float t[3];
     view_transform(v, p, t);
     float T[2][3];
     bool xin, yin;
     compute_T(t, v, fx, fy, tanfovx, tanfovy, T, o.tc, xin, yin);
-    float ST0[3], ST1[3], a, b, c;
-    cov2d_abc(S, T, ST0, ST1, a, b, c);
+    float ST0[3], ST1[3], a, b, c, a0, c0;
+    cov2d_abc(S, T, ST0, ST1, a, b, c, a0, c0);
     const float denom = a * c - b * b;
     const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+    const float q = AA ? aa_q(a0, b, c0, denom) : 1.f;
+    o.rho = AA ? aa_rho(q) : 1.f;
     float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
 #pragma unroll
     for (int e = 0; e < 6; e++) o.dcov[e] = 0.f;
@@ -248,6 +272,13 @@ __device__ __forceinline__ Cov2DGrad cov2d_backward(const float *v, float fx, fl
         dL_da = denom2inv * (-c * c * gA + b * c * gB + (denom - a * c) * gC);
         dL_dc = denom2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
         dL_db = denom2inv * (2.f * b * c * gA - (denom + 2.f * b * b) * gB + 2.f * a * b * gC);
+        if (AA && q > AA_QMIN) {
+            const float w = gop / (2.f * o.rho), di = 1.f / denom;
+            const float h = 0.3f * (a0 + c0) + 0.09f;
+            dL_da += w * ((0.3f * (c0 * c0 + b * b) + 0.09f * c0) * di * di);
+            dL_dc += w * ((0.3f * (a0 * a0 + b * b) + 0.09f * a0) * di * di);
+            dL_db += w * ((-2.f * b * h) * di * di);
+        }
         o.dcov[0] = T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc;
         o.dcov[3] = T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc;
         o.dcov[5] = T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc;
@@ -450,7 +481,7 @@ __device__ __forceinline__ void cov3d_backward(const float4 qraw, const float (&
 // opacity logits, SH split into _features_dc [N,1,3] = `shs` and _features_rest [N,M-1,3] = `shs_rest`) and the
 // getters' activations (scene/gaussian_model.py:109-129: exp, normalize, sigmoid, cat) are applied in
 // registers -- no activated copies of the 59 floats per Gaussian are written to / re-read from HBM.
-template <int DEG, bool RAW>
+template <int DEG, bool RAW, bool AA>
 __global__ void __launch_bounds__(GSR_ONE_DIM_BLOCK)
 preprocess_forward_kernel(int P, int M, const float *__restrict__ means3D, const float *__restrict__ scales,
                           float scale_modifier, const float *__restrict__ rotations, const float *__restrict__ shs,
@@ -491,7 +522,7 @@ preprocess_forward_kernel(int P, int M, const float *__restrict__ means3D, const
         float S[3][3];
         cov3d_from_scale_rot(q, s, S);
         Geom2D g;
-        if (!project_geometry(cam, tanfovx, tanfovy, fx, fy, W, H, gx, gy, p, t, S, g)) break;
+        if (!project_geometry<AA>(cam, tanfovx, tanfovy, fx, fy, W, H, gx, gy, p, t, S, g)) break;
 
         float shl[(DEG + 1) * (DEG + 1) * 3];
         const float *shp = shs + (size_t)i * M * 3;
@@ -523,6 +554,7 @@ preprocess_forward_kernel(int P, int M, const float *__restrict__ means3D, const
         cov[0] = S[0][0]; cov[1] = S[0][1]; cov[2] = S[0][2];
         cov[3] = S[1][1]; cov[4] = S[1][2]; cov[5] = S[2][2];
         co = make_float4(g.conic[0], g.conic[1], g.conic[2], RAW ? sigmoidf(opacities[i]) : opacities[i]);
+        if (AA) co.w *= g.rho;
     } while (false);
 
     radii[i] = radius;
@@ -807,7 +839,8 @@ struct K11In {
     float grgb[3];
     uint8_t cl[3];
 };
-template <bool RAW>
+// (AA with activated inputs: `opacities_raw` is the activated opacity, which the factor's gradient needs)
+template <bool RAW, bool AA = false>
 __device__ __forceinline__ K11In k11_load(size_t i, const float *__restrict__ means3D, const float *__restrict__ scales,
                                           const float *__restrict__ rotations, const float *__restrict__ shs,
                                           const float *__restrict__ opacities_raw, const int32_t *__restrict__ radii,
@@ -825,7 +858,7 @@ __device__ __forceinline__ K11In k11_load(size_t i, const float *__restrict__ me
         in.cl[e] = clamped[3 * i + e];
         in.grgb[e] = dL_drgb[(gstride ? gstride : 3) * i + e];
     }
-    in.op = RAW ? opacities_raw[i] : 0.f;
+    in.op = (RAW || AA) ? opacities_raw[i] : 0.f;
     in.q = *reinterpret_cast<const float4 *>(rotations + 4 * i);
 #pragma unroll
     for (int e = 0; e < 6; e++) in.cv[e] = cov3D[6 * i + e];
@@ -834,7 +867,24 @@ __device__ __forceinline__ K11In k11_load(size_t i, const float *__restrict__ me
     return in;
 }
 
-template <int DEG, bool RAW, bool ADAM = false>
+// dL/dopacity of one row from g = the summed dL/dconic_opacity.w (AA: each camera's times its rho): through the sigmoid
+// for the raw forms, into the fused step's slot 13 or to HBM
+template <bool RAW, bool ADAM>
+__device__ __forceinline__ void k11_opacity_out(float op, float g, const int i, float (&sp)[14], float (&sg)[14],
+                                                float *__restrict__ dL_dopacities) {
+    if (ADAM) {
+        const float so = sigmoidf(op);
+        sp[13] = op;
+        sg[13] = g * so * (1.0f - so);
+    } else if (RAW) {
+        const float so = sigmoidf(op);
+        dL_dopacities[i] = g * so * (1.0f - so);
+    } else {
+        dL_dopacities[i] = g;
+    }
+}
+
+template <int DEG, bool RAW, bool ADAM = false, bool AA = false>
 __device__ __forceinline__ void
 preprocess_backward_body(const K11In &in, float (&sp)[14], float (&sg)[14], const int i,
                          const float *__restrict__ rest_in, float *__restrict__ rest_out, int M, float scale_modifier,
@@ -884,21 +934,14 @@ preprocess_backward_body(const K11In &in, float (&sp)[14], float (&sg)[14], cons
     const float p[3] = {in.p[0], in.p[1], in.p[2]};
     const float4 gco = in.gco;
     const float gA = gco.x, gB = gco.y, gC = gco.z;
-    if (ADAM) {
-        const float so = sigmoidf(in.op);
-        sp[13] = in.op;
-        sg[13] = gco.w * so * (1.0f - so);
-    } else if (RAW) {
-        const float so = sigmoidf(in.op);
-        dL_dopacities[i] = gco.w * so * (1.0f - so);
-    } else {
-        dL_dopacities[i] = gco.w;
-    }
+    if (!AA) k11_opacity_out<RAW, ADAM>(in.op, gco.w, i, sp, sg, dL_dopacities);
 
     // ---- conic -> cov2D -> (cov3D, t)
     float S[3][3];
     cov3d_unpack(in.cv, S);
-    const Cov2DGrad cg = cov2d_backward(cam.v, fx, fy, tanfovx, tanfovy, p, S, gA, gB, gC);
+    const Cov2DGrad cg = cov2d_backward<AA>(cam.v, fx, fy, tanfovx, tanfovy, p, S, gA, gB, gC,
+                                            AA ? gco.w * (RAW ? sigmoidf(in.op) : in.op) : 0.f);
+    if (AA) k11_opacity_out<RAW, ADAM>(in.op, gco.w * cg.rho, i, sp, sg, dL_dopacities);
     float dmean[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) dmean[k] = cg.dmean[k];
@@ -995,7 +1038,7 @@ preprocess_backward_body(const K11In &in, float (&sp)[14], float (&sg)[14], cons
 // _features_rest (and of its gradient) are contiguous in HBM; per-lane rows are 180 bytes apart, so reading them
 // lane by lane touches a different cache line in every lane of every load.  They are staged through LDS with
 // coalesced 16-byte accesses instead (row stride 45 words: conflict-free), both ways.
-template <int DEG, bool RAW>
+template <int DEG, bool RAW, bool AA>
 __global__ void __launch_bounds__(K11_BLOCK, K11_WAVES_PER_EU)
 preprocess_backward_kernel(int P, int M, const float *__restrict__ means3D, const float *__restrict__ scales,
                            float scale_modifier, const float *__restrict__ rotations, const float *__restrict__ shs,
@@ -1015,33 +1058,33 @@ preprocess_backward_kernel(int P, int M, const float *__restrict__ means3D, cons
         __shared__ float s_rest[K11_BLOCK * REST_W];
         if (M == 16) {  // block-uniform
             RestStage st = rest_stage_issue(shs_rest, P);
-            const K11In in = k11_load<RAW>(ic, means3D, scales, rotations, shs, opacities_raw, radii, cov3D, clamped,
-                                           dL_dmeans2D, dL_dconic_opacity, dL_drgb, gstride);
+            const K11In in = k11_load<RAW, AA>(ic, means3D, scales, rotations, shs, opacities_raw, radii, cov3D, clamped,
+                                               dL_dmeans2D, dL_dconic_opacity, dL_drgb, gstride);
             __builtin_amdgcn_sched_barrier(0);  // every load of the lane is issued before the first result is used
             rest_stage_commit(s_rest, st, shs_rest, P);
             __syncthreads();
             if (i < P)
-                preprocess_backward_body<DEG, RAW>(in, ad, ad2, i, s_rest + threadIdx.x * REST_W,
-                                                   s_rest + threadIdx.x * REST_W, M, scale_modifier, shs, view, proj,
-                                                   campos, W, H, tanfovx, tanfovy, dL_dmeans3D, dL_dscales,
-                                                   dL_drotations, dL_dshs, dL_dopacities);
+                preprocess_backward_body<DEG, RAW, false, AA>(in, ad, ad2, i, s_rest + threadIdx.x * REST_W,
+                                                              s_rest + threadIdx.x * REST_W, M, scale_modifier, shs,
+                                                              view, proj, campos, W, H, tanfovx, tanfovy, dL_dmeans3D,
+                                                              dL_dscales, dL_drotations, dL_dshs, dL_dopacities);
             __syncthreads();
             rest_stage_out(s_rest, dL_dshs_rest, P);
             return;
         }
     }
     if (i >= P) return;
-    const K11In in = k11_load<RAW>(ic, means3D, scales, rotations, shs, opacities_raw, radii, cov3D, clamped, dL_dmeans2D,
-                                   dL_dconic_opacity, dL_drgb, gstride);
-    preprocess_backward_body<DEG, RAW>(in, ad, ad2, i, RAW ? shs_rest + (size_t)i * (M - 1) * 3 : nullptr,
-                                       RAW ? dL_dshs_rest + (size_t)i * (M - 1) * 3 : nullptr, M, scale_modifier, shs,
-                                       view, proj, campos, W, H, tanfovx, tanfovy, dL_dmeans3D, dL_dscales,
-                                       dL_drotations, dL_dshs, dL_dopacities);
+    const K11In in = k11_load<RAW, AA>(ic, means3D, scales, rotations, shs, opacities_raw, radii, cov3D, clamped,
+                                       dL_dmeans2D, dL_dconic_opacity, dL_drgb, gstride);
+    preprocess_backward_body<DEG, RAW, false, AA>(in, ad, ad2, i, RAW ? shs_rest + (size_t)i * (M - 1) * 3 : nullptr,
+                                                  RAW ? dL_dshs_rest + (size_t)i * (M - 1) * 3 : nullptr, M,
+                                                  scale_modifier, shs, view, proj, campos, W, H, tanfovx, tanfovy,
+                                                  dL_dmeans3D, dL_dscales, dL_drotations, dL_dshs, dL_dopacities);
 }
 
 // K11 + Adam, one camera, 16-coefficient model (the launcher checks): the same body with the stores replaced by the
 // optimizer update (K11Adam above).  Own kernel name so that traces and counters tell the fused launch apart.
-template <int DEG>
+template <int DEG, bool AA>
 __global__ void __launch_bounds__(K11_BLOCK, K11_WAVES_PER_EU)
 preprocess_backward_adam_kernel(int P, float *__restrict__ xyz, float *__restrict__ scaling, float scale_modifier,
                                 float *__restrict__ rotation, float *__restrict__ f_dc, float *__restrict__ f_rest,
@@ -1064,10 +1107,10 @@ preprocess_backward_adam_kernel(int P, float *__restrict__ xyz, float *__restric
     __syncthreads();
     float sp[14], sg[14];
     if (i < P)
-        preprocess_backward_body<DEG, true, true>(in, sp, sg, i, s_rest + threadIdx.x * REST_W,
-                                                  s_rest + threadIdx.x * REST_W, 16, scale_modifier, f_dc, view, proj,
-                                                  campos, W, H, tanfovx, tanfovy, nullptr, nullptr, nullptr, nullptr,
-                                                  nullptr);
+        preprocess_backward_body<DEG, true, true, AA>(in, sp, sg, i, s_rest + threadIdx.x * REST_W,
+                                                      s_rest + threadIdx.x * REST_W, 16, scale_modifier, f_dc, view,
+                                                      proj, campos, W, H, tanfovx, tanfovy, nullptr, nullptr, nullptr,
+                                                      nullptr, nullptr);
     __syncthreads();
     rest_adam_out(s_rest, f_rest, ad, P);
     __syncthreads();  // the stage is free: the moments of the small tensors go through it
@@ -1096,7 +1139,7 @@ __device__ __forceinline__ Cam load_cam_packed(const float *__restrict__ c) {
     return cam;
 }
 
-template <int DEG>
+template <int DEG, bool AA>
 __global__ void __launch_bounds__(GSR_ONE_DIM_BLOCK)
 preprocess_forward_batched_kernel(int P, int B, int M, const float *__restrict__ xyz, const float *__restrict__ scaling,
                                   float scale_modifier, const float *__restrict__ rotation,
@@ -1150,12 +1193,12 @@ preprocess_forward_batched_kernel(int P, int B, int M, const float *__restrict__
         do {
             if (t[2] <= 0.2f) break;  // near-plane cull
             Geom2D g;
-            if (!project_geometry(cam, tanfovx, tanfovy, fx, fy, W, H, gx, gy, p, t, S, g)) break;
+            if (!project_geometry<AA>(cam, tanfovx, tanfovy, fx, fy, W, H, gx, gy, p, t, S, g)) break;
             shade<DEG>(cam.c, p, shl, col, cl);
             radius = g.rad;
             xy = g.xy;
             depth = t[2];
-            co = make_float4(g.conic[0], g.conic[1], g.conic[2], op);
+            co = make_float4(g.conic[0], g.conic[1], g.conic[2], AA ? op * g.rho : op);
         } while (false);
         const size_t o = (size_t)bc * P + i;
         radii[o] = radius;
@@ -1307,7 +1350,7 @@ __device__ __forceinline__ void sa_rest_adam_out(const float *__restrict__ s_res
     }
 }
 
-template <int DEG, bool ADAM, typename ROWS = DenseRows>
+template <int DEG, bool ADAM, bool AA, typename ROWS = DenseRows>
 __device__ __forceinline__ void
 preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ xyz,
                                    const float *__restrict__ scaling, float scale_modifier,
@@ -1396,6 +1439,7 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
 #pragma unroll
     for (int k = 0; k < NC * 3; k++) dsh[k] = 0.f;
     float dop = 0.f;
+    const float op_act = AA ? sigmoidf(oraw) : 0.f;  // AA: the uncompensated opacity, for the factor's gradient
 
     // Two loops over the cameras (round 6): the colour part first -- its 48 accumulators and the coefficients it reads
     // from the LDS stage are dead before the geometry part starts, whose covariance chain then has the registers to
@@ -1456,8 +1500,10 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
         const float fx = W / (2.0f * tanfovx), fy = H / (2.0f * tanfovy);
         const float4 gco = cin.gco;
         const float gA = gco.x, gB = gco.y, gC = gco.z;
-        dop += gco.w;
-        const Cov2DGrad cg = cov2d_backward(cam.v, fx, fy, tanfovx, tanfovy, p, S, gA, gB, gC);
+        if (!AA) dop += gco.w;
+        const Cov2DGrad cg = cov2d_backward<AA>(cam.v, fx, fy, tanfovx, tanfovy, p, S, gA, gB, gC,
+                                                AA ? gco.w * op_act : 0.f);
+        if (AA) dop += gco.w * cg.rho;
         if (cg.live) {
 #pragma unroll
             for (int e = 0; e < 6; e++) dcov[e] += cg.dcov[e];
@@ -1529,7 +1575,7 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
     }
 }
 
-template <int DEG>
+template <int DEG, bool AA>
 __global__ void __launch_bounds__(K11_BLOCK, K11B_WAVES_PER_EU)
 preprocess_backward_batched_kernel(int P, int B, int M, const float *__restrict__ xyz,
                                    const float *__restrict__ scaling, float scale_modifier,
@@ -1542,13 +1588,13 @@ preprocess_backward_batched_kernel(int P, int B, int M, const float *__restrict_
                                    int gstride, float *__restrict__ dL_dxyz, float *__restrict__ dL_dscaling,
                                    float4 *__restrict__ dL_drotation, float *__restrict__ dL_ddc,
                                    float *__restrict__ dL_drest, float *__restrict__ dL_dopacity) {
-    preprocess_backward_batched_body<DEG, false>(P, B, M, xyz, scaling, scale_modifier, rotation, f_dc, f_rest, opacity,
-                                                 cams, W, H, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity,
-                                                 dL_drgb, gstride, dL_dxyz, dL_dscaling, dL_drotation, dL_ddc, dL_drest,
-                                                 dL_dopacity, K11Adam{});
+    preprocess_backward_batched_body<DEG, false, AA>(P, B, M, xyz, scaling, scale_modifier, rotation, f_dc, f_rest,
+                                                     opacity, cams, W, H, radii, cov3D, clamped, dL_dmeans2D,
+                                                     dL_dconic_opacity, dL_drgb, gstride, dL_dxyz, dL_dscaling,
+                                                     dL_drotation, dL_ddc, dL_drest, dL_dopacity, K11Adam{});
 }
 
-template <int DEG>
+template <int DEG, bool AA>
 __global__ void __launch_bounds__(K11_BLOCK, K11B_WAVES_PER_EU)
 preprocess_backward_adam_batched_kernel(int P, int B, float *__restrict__ xyz, float *__restrict__ scaling,
                                         float scale_modifier, float *__restrict__ rotation,
@@ -1560,10 +1606,10 @@ preprocess_backward_adam_batched_kernel(int P, int B, float *__restrict__ xyz, f
                                         const float *__restrict__ dL_drgb, int gstride, const K11Adam ad_in) {
     if (ad_in.skip && *ad_in.skip) return;
     const K11Adam ad = k11_adam_resolve(ad_in);
-    preprocess_backward_batched_body<DEG, true>(P, B, 16, xyz, scaling, scale_modifier, rotation, f_dc, f_rest, opacity,
-                                                cams, W, H, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity,
-                                                dL_drgb, gstride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                ad);
+    preprocess_backward_batched_body<DEG, true, AA>(P, B, 16, xyz, scaling, scale_modifier, rotation, f_dc, f_rest,
+                                                    opacity, cams, W, H, radii, cov3D, clamped, dL_dmeans2D,
+                                                    dL_dconic_opacity, dL_drgb, gstride, nullptr, nullptr, nullptr,
+                                                    nullptr, nullptr, nullptr, ad);
 }
 
 // ------------------------------------------------------------------- sparse (lazy) K11 + Adam
@@ -1650,7 +1696,7 @@ sparse_adam_classify_kernel(int P, int B, const int32_t *__restrict__ radii, con
             list[s_base + s_cnt[j * NW + wave] + rank[j]] = (uint32_t)(row0 + (size_t)j * SA_CBLOCK + threadIdx.x);
 }
 
-template <int DEG>
+template <int DEG, bool AA>
 __global__ void __launch_bounds__(K11_BLOCK, K11B_WAVES_PER_EU)
 sparse_adam_update_kernel(int P, int B, float *__restrict__ xyz, float *__restrict__ scaling, float scale_modifier,
                           float *__restrict__ rotation, float *__restrict__ f_dc, float *__restrict__ f_rest,
@@ -1666,10 +1712,10 @@ sparse_adam_update_kernel(int P, int B, float *__restrict__ xyz, float *__restri
     if ((size_t)blockIdx.x * K11_BLOCK >= count) return;  // (uniform) past the list: at a tenth of the rows active, nine
                                                           // workgroups of ten
     const K11Adam ad = k11_adam_resolve(ad_in);
-    preprocess_backward_batched_body<DEG, true>(P, B, 16, xyz, scaling, scale_modifier, rotation, f_dc, f_rest, opacity,
-                                                cams, W, H, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity,
-                                                dL_drgb, gstride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                ad, ListRows{list, count});
+    preprocess_backward_batched_body<DEG, true, AA>(P, B, 16, xyz, scaling, scale_modifier, rotation, f_dc, f_rest,
+                                                    opacity, cams, W, H, radii, cov3D, clamped, dL_dmeans2D,
+                                                    dL_dconic_opacity, dL_drgb, gstride, nullptr, nullptr, nullptr,
+                                                    nullptr, nullptr, nullptr, ad, ListRows{list, count});
 }
 
 // ------------------------------------------------------------------- K11c: camera (pose) gradients
@@ -1892,18 +1938,33 @@ local2j_kernel(int P, int W, int H, int ws, const float2 *__restrict__ means2D, 
         case 2: { constexpr int DEG = 2; __VA_ARGS__; } break; \
         default: { constexpr int DEG = 3; __VA_ARGS__; } break; \
     }
+// ... and over the anti-aliasing variant: `aa` is what the entry point read from the switch, ONCE, on the host
+#define GSR_DISPATCH_DEG_AA(D, aa, ...)                                     \
+    if (aa) { constexpr bool AA = true; GSR_DISPATCH_DEG(D, __VA_ARGS__) }  \
+    else { constexpr bool AA = false; GSR_DISPATCH_DEG(D, __VA_ARGS__) }
+
+// gsr_set_antialiasing: process-wide, like the binning switches (g_tile_cull, g_tie_order in binning_host.h).  Every
+// K1 / K11 entry point loads it once per call and picks the instantiation; what is already enqueued or captured keeps
+// the kernel it was launched with.
+static std::atomic<int> g_antialiasing{0};
+int gsr_antialiasing_mode() { return g_antialiasing.load(std::memory_order_relaxed); }
+extern "C" int gsr_set_antialiasing(int mode) {
+    if (mode != 0 && mode != 1) return GSR_EINVAL;
+    return g_antialiasing.exchange(mode, std::memory_order_relaxed);
+}
 
 int gsr_launch_preprocess_forward(int P, int D, int M, const float *means3D, const float *scales, float scale_modifier,
                                   const float *rotations, const float *shs, const float *shs_rest,
                                   const float *opacities,
                                   const float *viewmatrix, const float *projmatrix, const float *campos, int W, int H,
                                   float tanfovx, float tanfovy, float *means2D, float *depths, int32_t *radii,
-                                  float *cov3D, float *conic_opacity, float *rgb, uint8_t *clamped,
+                                  float *cov3D, float *conic_opacity, float *rgb, uint8_t *clamped, int aa,
                                   hipStream_t stream) {
     if (P == 0) return 0;
     const dim3 grid(gsr_div_up(P, GSR_ONE_DIM_BLOCK)), block(GSR_ONE_DIM_BLOCK);
 #define GSR_FWD(RAWF)                                                                                              \
-    GSR_DISPATCH_DEG(D, hipLaunchKernelGGL((preprocess_forward_kernel<DEG, RAWF>), grid, block, 0, stream, P, M,   \
+    GSR_DISPATCH_DEG_AA(D, aa, hipLaunchKernelGGL((preprocess_forward_kernel<DEG, RAWF, AA>), grid, block, 0,      \
+                                           stream, P, M,                                                           \
                                            means3D, scales, scale_modifier, rotations, shs, shs_rest, opacities,   \
                                            viewmatrix, projmatrix, campos, W, H, tanfovx, tanfovy,                 \
                                            reinterpret_cast<float2 *>(means2D), depths, radii, cov3D,              \
@@ -1920,12 +1981,13 @@ int gsr_launch_preprocess_backward(int P, int D, int M, const float *means3D, co
                                    int H, float tanfovx, float tanfovy, const int32_t *radii, const float *cov3D,
                                    const uint8_t *clamped, const float *dL_dmeans2D, const float *dL_dconic_opacity,
                                    const float *dL_drgb, int grad_row_stride, float *dL_dmeans3D, float *dL_dscales, float *dL_drotations,
-                                   float *dL_dshs, float *dL_dshs_rest, float *dL_dopacities,
+                                   float *dL_dshs, float *dL_dshs_rest, float *dL_dopacities, int aa,
                                    hipStream_t stream) {
     if (P == 0) return 0;
     const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
 #define GSR_BWD(RAWF)                                                                                              \
-    GSR_DISPATCH_DEG(D, hipLaunchKernelGGL((preprocess_backward_kernel<DEG, RAWF>), grid, block, 0, stream, P, M,  \
+    GSR_DISPATCH_DEG_AA(D, aa, hipLaunchKernelGGL((preprocess_backward_kernel<DEG, RAWF, AA>), grid, block, 0,     \
+                                           stream, P, M,                                                           \
                                            means3D, scales, scale_modifier, rotations, shs, shs_rest,              \
                                            opacities_raw, viewmatrix, projmatrix, campos, W, H, tanfovx, tanfovy,  \
                                            radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb,           \
@@ -1962,8 +2024,8 @@ extern "C" int gsr_preprocess_forward_raw_batched(int P, int B, int sh_degree, i
         !radii || !cov3D || !conic_opacity || !rgb || !clamped)
         return GSR_EINVAL;
     const dim3 grid(gsr_div_up(P, GSR_ONE_DIM_BLOCK)), block(GSR_ONE_DIM_BLOCK);
-    GSR_DISPATCH_DEG(sh_degree,
-                     hipLaunchKernelGGL(preprocess_forward_batched_kernel<DEG>, grid, block, 0,
+    GSR_DISPATCH_DEG_AA(sh_degree, gsr_antialiasing_mode(),
+                     hipLaunchKernelGGL((preprocess_forward_batched_kernel<DEG, AA>), grid, block, 0,
                                         reinterpret_cast<hipStream_t>(stream), P, B, sh_coeffs, xyz, scaling,
                                         scale_modifier, rotation, features_dc, features_rest, opacity, cams, width,
                                         height, reinterpret_cast<float2 *>(means2D), depths, radii, cov3D,
@@ -1990,8 +2052,8 @@ extern "C" int gsr_preprocess_backward_raw_batched(int P, int B, int sh_degree, 
         !dL_dfeatures_dc || !dL_dfeatures_rest || !dL_dopacity)
         return GSR_EINVAL;
     const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
-    GSR_DISPATCH_DEG(sh_degree,
-                     hipLaunchKernelGGL(preprocess_backward_batched_kernel<DEG>, grid, block, 0,
+    GSR_DISPATCH_DEG_AA(sh_degree, gsr_antialiasing_mode(),
+                     hipLaunchKernelGGL((preprocess_backward_batched_kernel<DEG, AA>), grid, block, 0,
                                         reinterpret_cast<hipStream_t>(stream), P, B, sh_coeffs, xyz, scaling,
                                         scale_modifier, rotation, features_dc, features_rest, opacity, cams, width,
                                         height, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb,
@@ -2074,9 +2136,10 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_dyn(
     for (int t = 0; t < 6; t++) al |= (uintptr_t)ad.m[t] | (uintptr_t)ad.v[t];
     if (al & 15) return GSR_EINVAL;  // 16-byte accesses on the moments and the _features_rest block
     const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
+    const int aa = gsr_antialiasing_mode();
     if (B == 1 && tanfov0) {  // one camera: the leaner kernel without accumulators
-        GSR_DISPATCH_DEG(sh_degree,
-                         hipLaunchKernelGGL(preprocess_backward_adam_kernel<DEG>, grid, block, 0,
+        GSR_DISPATCH_DEG_AA(sh_degree, aa,
+                         hipLaunchKernelGGL((preprocess_backward_adam_kernel<DEG, AA>), grid, block, 0,
                                             reinterpret_cast<hipStream_t>(stream), P, xyz, scaling, scale_modifier,
                                             rotation, features_dc, features_rest, opacity, cams, cams + 16, cams + 32,
                                             width, height, tanfov0[0], tanfov0[1], radii, cov3D, clamped, dL_dmeans2D,
@@ -2084,8 +2147,8 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_dyn(
         GSR_LAUNCH_CHECK();
         return 0;
     }
-    GSR_DISPATCH_DEG(sh_degree,
-                     hipLaunchKernelGGL(preprocess_backward_adam_batched_kernel<DEG>, grid, block, 0,
+    GSR_DISPATCH_DEG_AA(sh_degree, aa,
+                     hipLaunchKernelGGL((preprocess_backward_adam_batched_kernel<DEG, AA>), grid, block, 0,
                                         reinterpret_cast<hipStream_t>(stream), P, B, xyz, scaling, scale_modifier,
                                         rotation, features_dc, features_rest, opacity, cams, width, height, radii,
                                         cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride, ad));
@@ -2129,8 +2192,8 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_sparse(
                        dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride, skip_flag_dev, ws, list, active_out);
     GSR_LAUNCH_CHECK();
     const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
-    GSR_DISPATCH_DEG(sh_degree,
-                     hipLaunchKernelGGL(sparse_adam_update_kernel<DEG>, grid, block, 0, st, P, B, xyz, scaling,
+    GSR_DISPATCH_DEG_AA(sh_degree, gsr_antialiasing_mode(),
+                     hipLaunchKernelGGL((sparse_adam_update_kernel<DEG, AA>), grid, block, 0, st, P, B, xyz, scaling,
                                         scale_modifier, rotation, features_dc, features_rest, opacity, cams, width,
                                         height, radii, cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb,
                                         grad_row_stride, ad, ws, list, num_active_dev));
@@ -2162,6 +2225,8 @@ extern "C" int gsr_preprocess_backward_cams(int P, int B, int sh_degree, int sh_
         GSR_LAUNCH_CHECK();
         return 0;
     }
+    if (gsr_antialiasing_mode() != 0)
+        return GSR_EINVAL;  // the factor of the opacity depends on the pose too, and this entry point has no opacity
     if (!means3D || !sh_dc || (!sh_rest && sh_coeffs > 1) || !cams || !radii || !cov3D || !clamped || !dL_dmeans2D ||
         !dL_dconic_opacity || !dL_drgb || !workspace || ((uintptr_t)workspace & 7))
         return GSR_EINVAL;

@@ -269,6 +269,49 @@ def _grad_triple(g_means2D, g_rgb, g_conic_opacity, P, dev):
     return z(g_means2D, 2), z(g_rgb, 3), z(g_conic_opacity, 4), 0
 
 
+# ---- anti-aliased splatting (include/gsraster.h: gsr_set_antialiasing) ------------------------------------------------
+# The library's switch is process-wide and read per launch; a backward has to run under the mode of ITS forward, whatever
+# the setting is by then.  So every forward notes the mode it ran under (ctx.aa, or the last entry of the batched path's
+# `meta`), and every K1 / K11 launch of this module goes through _lib_antialiasing(mode) first, which calls into the
+# library only when the mode differs from the last one it set.
+_ANTIALIASING = [os.environ.get("GSR_ANTIALIASING", "0").strip().lower() not in ("", "0", "false", "off", "no")]
+_ANTIALIASING_LIB = [0]  # what the library was last set to (its initial mode is 0)
+
+
+def set_antialiasing(on):
+    """opacity compensation for the 0.3 px^2 dilation of every splat (the 2D Mip filter; include/gsraster.h:
+    gsr_set_antialiasing has the definition).  Off by default (the reference's behaviour); the initial value comes from
+    GSR_ANTIALIASING.  Takes effect for the forwards that follow; a backward or a fused optimizer step runs under the
+    mode of its own forward.  Camera-pose gradients are not implemented under it (NotImplementedError)."""
+    _ANTIALIASING[0] = bool(on)
+
+
+def get_antialiasing():
+    """the mode that the next forward will run under"""
+    return _ANTIALIASING[0]
+
+
+def _lib_antialiasing(mode):
+    mode = 1 if mode else 0
+    if _ANTIALIASING_LIB[0] != mode:
+        if lib.gsr_set_antialiasing(mode) < 0:
+            raise RuntimeError("gsr_set_antialiasing failed")
+        _ANTIALIASING_LIB[0] = mode
+
+
+def _refuse_camera_grad_under_antialiasing(what):
+    if _ANTIALIASING[0]:
+        raise NotImplementedError(
+            f"{what}: camera tensors (viewmatrix / projmatrix / campos / cams) that require grad together with "
+            "set_antialiasing(True) -- the opacity's compensation factor depends on the pose as well, and its camera "
+            "gradient is not implemented; detach the camera tensors or switch anti-aliasing off")
+
+
+def _meta_aa(meta):
+    """the anti-aliasing mode at the end of a batched forward's meta (a five-entry meta predates it: off)"""
+    return bool(meta[5]) if len(meta) > 5 else False
+
+
 class _PreprocessGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, scales, rotations, shs, opacities, raster_settings, cuda_args):
@@ -293,6 +336,8 @@ class _PreprocessGaussians(torch.autograd.Function):
         rgb = torch.empty((P, 3), dtype=torch.float32, device=dev)
         clamped = torch.empty((P, 3), dtype=torch.uint8, device=dev)
         ctx.cuda_args = cuda_args
+        ctx.aa = _ANTIALIASING[0]
+        _lib_antialiasing(ctx.aa)
         with _on(dev), kernel_timer.range("preprocess_forward", N=P, B=1, M=M), \
                 zhx_range(cuda_args, "10 preprocess time"):
             check(lib.gsr_preprocess_forward(
@@ -303,6 +348,7 @@ class _PreprocessGaussians(torch.autograd.Function):
         ctx.raster_settings = rs
         ctx.M = M
         ctx.save_for_backward(means3D, scales, rotations, shs, view, proj, campos, radii, cov3D, clamped)
+        ctx.opacities = opacities if ctx.aa else None  # (an input: only K11's anti-aliased form reads it again)
         ctx.mark_non_differentiable(radii, depths)
         return means2D, rgb, conic_opacity, radii, depths
 
@@ -319,14 +365,19 @@ class _PreprocessGaussians(torch.autograd.Function):
         d_rot = torch.empty((P, 4), dtype=torch.float32, device=dev)
         d_shs = torch.empty((P, M, 3), dtype=torch.float32, device=dev)
         d_opac = torch.empty((P, 1), dtype=torch.float32, device=dev)
+        _lib_antialiasing(ctx.aa)
         with _on(dev), kernel_timer.range("preprocess_backward", N=P, B=1, M=M), \
                 zhx_range(ctx.cuda_args, "b20 preprocess time"):
-            check(lib.gsr_preprocess_backward(
-                P, int(rs.sh_degree), M, _ptr(means3D), _ptr(scales), float(rs.scale_modifier), _ptr(rotations),
-                _ptr(shs), _ptr(view), _ptr(proj), _ptr(campos), int(rs.image_width), int(rs.image_height),
-                float(rs.tanfovx), float(rs.tanfovy), _ptr(radii), _ptr(cov3D), _ptr(clamped), _ptr(g_means2D),
-                _ptr(g_conic_opacity), _ptr(g_rgb), gstride, _ptr(d_means3D), _ptr(d_scales), _ptr(d_rot),
-                _ptr(d_shs), _ptr(d_opac), _stream()), "gsr_preprocess_backward")
+            tail = (_ptr(view), _ptr(proj), _ptr(campos), int(rs.image_width), int(rs.image_height),
+                    float(rs.tanfovx), float(rs.tanfovy), _ptr(radii), _ptr(cov3D), _ptr(clamped), _ptr(g_means2D),
+                    _ptr(g_conic_opacity), _ptr(g_rgb), gstride, _ptr(d_means3D), _ptr(d_scales), _ptr(d_rot),
+                    _ptr(d_shs), _ptr(d_opac), _stream())
+            head = (P, int(rs.sh_degree), M, _ptr(means3D), _ptr(scales), float(rs.scale_modifier), _ptr(rotations),
+                    _ptr(shs))
+            if ctx.aa:
+                check(lib.gsr_preprocess_backward_aa(*head, _ptr(ctx.opacities), *tail), "gsr_preprocess_backward_aa")
+            else:
+                check(lib.gsr_preprocess_backward(*head, *tail), "gsr_preprocess_backward")
         return d_means3D, d_scales, d_rot, d_shs, d_opac, None, None
 
 
@@ -356,6 +407,8 @@ class _PreprocessGaussiansRaw(torch.autograd.Function):
         rgb = torch.empty((P, 3), dtype=torch.float32, device=dev)
         clamped = torch.empty((P, 3), dtype=torch.uint8, device=dev)
         ctx.cuda_args = cuda_args
+        ctx.aa = _ANTIALIASING[0]
+        _lib_antialiasing(ctx.aa)
         with _on(dev), kernel_timer.range("preprocess_forward", N=P, B=1, M=M), \
                 zhx_range(cuda_args, "10 preprocess time"):
             check(lib.gsr_preprocess_forward_raw(
@@ -384,6 +437,7 @@ class _PreprocessGaussiansRaw(torch.autograd.Function):
         d_dc = torch.empty((P, 1, 3), dtype=torch.float32, device=dev)
         d_rest = torch.empty((P, M - 1, 3), dtype=torch.float32, device=dev)
         d_opac = torch.empty((P, 1), dtype=torch.float32, device=dev)
+        _lib_antialiasing(ctx.aa)
         with _on(dev), kernel_timer.range("preprocess_backward", N=P, B=1, M=M), \
                 zhx_range(ctx.cuda_args, "b20 preprocess time"):
             check(lib.gsr_preprocess_backward_raw(
@@ -481,6 +535,7 @@ class _PreprocessGaussiansCam(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, scales, rotations, shs, opacities, viewmatrix, projmatrix, campos, raster_settings,
                 cuda_args):
+        _refuse_camera_grad_under_antialiasing("preprocess_gaussians")
         ctx.cam_slot = 5
         ctx.cam_like = [(t.dtype, t.shape) for t in (viewmatrix, projmatrix, campos)]
         rs = raster_settings._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
@@ -503,6 +558,7 @@ class _PreprocessGaussiansRawCam(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, scaling, rotation, features_dc, features_rest, opacity, viewmatrix, projmatrix, campos,
                 raster_settings, cuda_args):
+        _refuse_camera_grad_under_antialiasing("preprocess_gaussians_raw")
         ctx.cam_slot = 6
         ctx.cam_like = [(t.dtype, t.shape) for t in (viewmatrix, projmatrix, campos)]
         rs = raster_settings._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
@@ -596,7 +652,7 @@ class PendingProjectionBackward:
         P changes, so a captured iteration allocates nothing new on replay."""
         self.join_stream()
         xyz, scaling, rotation, f_dc, f_rest, opacity = self.params
-        deg, smod, W, H, M = self.meta
+        deg, smod, W, H, M = self.meta[:5]
         P, B = xyz.shape[0], self.cams.shape[0]
         VP, D, I64 = ctypes.c_void_p * 6, ctypes.c_double * 6, ctypes.c_int64 * 6
         key = (tuple(t.data_ptr() for t in exp_avgs), tuple(t.data_ptr() for t in exp_avg_sqs), tuple(beta1s),
@@ -635,6 +691,7 @@ class PendingProjectionBackward:
         else:
             name, timed = "gsr_preprocess_backward_adam_raw_batched", "preprocess_backward_adam"
             args += [tf]
+        _lib_antialiasing(_meta_aa(self.meta))  # the forward's mode, whatever the setting is by now
         with _on(xyz.device), (kernel_timer.range(timed, N=P, B=B, M=M) if cap_ctx is None else _NULL_RANGE):
             check(getattr(lib, name)(*args, _stream()), name)
 
@@ -642,7 +699,8 @@ class PendingProjectionBackward:
 def _launch_k11(params, cams, radii, cov3D, clamped, g_means2D, g_conic_opacity, g_rgb, gstride, meta, tanfov0,
                 cuda_args_list):
     xyz, scaling, rotation, f_dc, f_rest, opacity = params
-    deg, smod, W, H, M = meta
+    deg, smod, W, H, M = meta[:5]
+    _lib_antialiasing(_meta_aa(meta))  # the forward's mode, whatever the setting is by now
     P, B = xyz.shape[0], cams.shape[0]
     dev = xyz.device
     d_xyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
@@ -688,6 +746,10 @@ class _PreprocessGaussiansRawBatched(torch.autograd.Function):
             raise ValueError("cams must be [B, 40]")
         M = 1 + features_rest.shape[1]
         dev = xyz.device
+        aa = _ANTIALIASING[0]
+        if aa and ctx.needs_input_grad[6]:
+            _refuse_camera_grad_under_antialiasing("preprocess_gaussians_raw_batched")
+        _lib_antialiasing(aa)
         means2D = torch.empty((B, P, 2), dtype=torch.float32, device=dev)
         depths = torch.empty((B, P), dtype=torch.float32, device=dev)
         radii = torch.empty((B, P), dtype=torch.int32, device=dev)
@@ -702,7 +764,7 @@ class _PreprocessGaussiansRawBatched(torch.autograd.Function):
                 _ptr(features_dc), _ptr(features_rest), _ptr(opacity), _ptr(cams), int(width), int(height),
                 _ptr(means2D), _ptr(depths), _ptr(radii), _ptr(cov3D), _ptr(conic_opacity), _ptr(rgb), _ptr(clamped),
                 _stream()), "gsr_preprocess_forward_raw_batched")
-        ctx.meta = (int(sh_degree), float(scale_modifier), int(width), int(height), M)
+        ctx.meta = (int(sh_degree), float(scale_modifier), int(width), int(height), M, aa)
         ctx.save_for_backward(xyz, scaling, rotation, features_dc, features_rest, opacity, cams, radii, cov3D, clamped)
         # per-camera outputs are separate autograd outputs (dense views of the camera-major buffers): a caller
         # that uses camera k alone gets its gradient straight back, without the zeros + copy of a select-backward
@@ -715,7 +777,7 @@ class _PreprocessGaussiansRawBatched(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         xyz, scaling, rotation, f_dc, f_rest, opacity, cams, radii, cov3D, clamped = ctx.saved_tensors
-        deg, smod, W, H, M = ctx.meta
+        deg, smod, W, H, M = ctx.meta[:5]
         P, B = xyz.shape[0], cams.shape[0]
         dev = xyz.device
 

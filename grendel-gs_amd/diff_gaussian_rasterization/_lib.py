@@ -29,6 +29,10 @@ SIGNATURES = {
     "gsr_preprocess_backward": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float] +
                                 [c_void_p] * 6 + [c_int] + [c_void_p] * 6),
+    "gsr_set_antialiasing": (c_int, [c_int]),
+    "gsr_preprocess_backward_aa": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float] +
+                                   [c_void_p] * 6 + [c_int] + [c_void_p] * 6),
     "gsr_get_local2j_ids_bool": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
     "gsr_bin_prepare_bytes": (c_size_t, [c_int, c_int, c_int]),

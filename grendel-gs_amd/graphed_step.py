@@ -59,7 +59,8 @@ def _dbg(*a):
 
 
 class _Entry:
-    __slots__ = ("graph", "proxies", "out", "ctx", "caps_key", "pair_cap", "sproxies", "tasks", "band_cap", "masks")
+    __slots__ = ("graph", "proxies", "out", "ctx", "caps_key", "pair_cap", "sproxies", "tasks", "band_cap", "masks",
+                 "antialiasing")
 
 
 class _BandProxy:
@@ -369,6 +370,9 @@ class GraphedIteration:
             e.ctx.slab_caps_dev = torch.tensor(e.caps_key.reshape(-1), dtype=torch.int32).to(dev)
         torch.cuda.synchronize(dev)
         e.graph = torch.cuda.CUDAGraph()
+        # the K1 / K11 kernels of a captured iteration are those of the anti-aliasing mode in force now (the library picks
+        # the instantiation at launch): a replay under the other setting would silently run the wrong ones
+        e.antialiasing = _dgr.get_antialiasing()
         _dbg("capture begins")
         _dgr._CAPTURE[0] = e.ctx
         saved_caps = None
@@ -596,6 +600,10 @@ class GraphedIteration:
                     self.enabled = False
                     self.stats["disabled"] = err or "the capture failed on another rank"
             return out
+        if _dgr.get_antialiasing() != entry.antialiasing:
+            raise RuntimeError(f"GraphedIteration: this iteration was captured with set_antialiasing({entry.antialiasing}) "
+                               f"and would be replayed under set_antialiasing({_dgr.get_antialiasing()}); the captured "
+                               "kernels keep the mode of the capture -- restore the setting, or reset() to capture anew")
         # replay: inputs + hyper-parameters (one host-to-device copy, one band copy per camera), then ONE launch
         seq = self._stage(entry, cameras, strategies)
         _dbg("replay", seq)

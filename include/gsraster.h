@@ -81,8 +81,44 @@ int gsr_preprocess_backward(int P, int sh_degree, int sh_coeffs, const float *me
                             int grad_row_stride, float *dL_dmeans3D, float *dL_dscales, float *dL_drotations,
                             float *dL_dshs, float *dL_dopacities, gsr_stream_t stream);
 
+/* Anti-aliased splatting: opacity compensation in K1 / K11 (the 2D Mip filter of Mip-Splatting, the `antialiasing`
+ * switch of later 3DGS rasterizers).  No reference call site: the reference dilates every projected covariance by
+ * 0.3 px^2 and leaves the opacity alone, so a Gaussian far smaller than a pixel is drawn as a 0.55 px blob at its full
+ * opacity.  Process-wide switch, read ONCE per call, on the host, by every K1 / K11 entry point of this header (the
+ * activated, raw, camera-batched, fused K11 + Adam, _dyn and sparse forms): a launch already enqueued or captured keeps
+ * the mode it was launched with.  mode 0 (default): the reference's behaviour, bit for bit.  mode 1, for a visible row
+ * (radii > 0) and one camera, with a0, b, c0 = T Sigma T^T BEFORE the dilation:
+ *   det0 = a0 c0 - b^2;  a = a0 + 0.3, c = c0 + 0.3, det = a c - b^2 (the value the conic is made of);  q = det0 / det;
+ *   rho = sqrt(max(0.000025, q)), so 0.005 <= rho < 1.
+ * Forward: conic_opacity.w = opacity * rho (opacity: activated, uncompensated); every other output keeps its bits --
+ *   radii, conic, depths, rgb, clamped, cov3D -- and culled rows stay all zero.
+ * Backward, g = dL/dconic_opacity.w: dL/dopacity = g rho (the raw forms then multiply by the sigmoid's derivative, as
+ *   before); if q > 0.000025, w = g opacity / (2 rho) times dq/d(a, b, c) is added to the conic's dL/d(a, b, c) before
+ *   these go on to Sigma, T and t, so scales, rotation and mean all receive it; if q <= 0.000025 nothing is added.  With
+ *   h = det - det0 = 0.3 (a0 + c0) + 0.09:
+ *     dq/da = (0.3 (c0^2 + b^2) + 0.09 c0) / det^2,  dq/dc = (0.3 (a0^2 + b^2) + 0.09 a0) / det^2,
+ *     dq/db = -2 b h / det^2   (b: the one scalar in both off-diagonal places, as dL/db already is)
+ *   in these closed forms (the quotient rule cancels for large splats) and with the true 1 / det^2; the conic part keeps
+ *   its 1 / (det^2 + 1e-7).
+ * Nothing else changes: binning, composite, exchange and loss see the compensated opacity where they saw the opacity.
+ * -> the previous mode, or GSR_EINVAL for a mode other than 0 and 1 (the mode is then unchanged).
+ * Under mode 1 gsr_preprocess_backward and gsr_preprocess_backward_cams return GSR_EINVAL (for P > 0, before any device
+ * work) rather than an incomplete gradient: the activated K11 needs the opacity (gsr_preprocess_backward_aa below), and
+ * camera-pose gradients under anti-aliasing -- rho depends on the pose as well, and the _cams entry point has no opacity
+ * input -- are not implemented. */
+int gsr_set_antialiasing(int mode);
+/* gsr_preprocess_backward with `opacities` [P] (activated, the forward's input) behind `shs`.  Mode 1: K11 as defined
+ * above.  Mode 0: `opacities` is not read (may be NULL) and the results are gsr_preprocess_backward's bits. */
+int gsr_preprocess_backward_aa(int P, int sh_degree, int sh_coeffs, const float *means3D, const float *scales,
+                               float scale_modifier, const float *rotations, const float *shs, const float *opacities,
+                               const float *viewmatrix, const float *projmatrix, const float *campos, int width,
+                               int height, float tanfovx, float tanfovy, const int32_t *radii, const float *cov3D,
+                               const uint8_t *clamped, const float *dL_dmeans2D, const float *dL_dconic_opacity,
+                               const float *dL_drgb, int grad_row_stride, float *dL_dmeans3D, float *dL_dscales,
+                               float *dL_drotations, float *dL_dshs, float *dL_dopacities, gsr_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
- * K2  `_C.get_local2j_ids_bool` -- gaussian_renderer/workload_division.py:721-744.
+ * K2 `_C.get_local2j_ids_bool` -- gaussian_renderer/workload_division.py:721-744.
  * dist_global_strategy int32 [world_size+1]: band j owns flattened tile ids [d[j], d[j+1]).
  * out uint8 (bool) [P, world_size]: Gaussian i must be sent to band j. */
 int gsr_get_local2j_ids_bool(int P, int width, int height, int world_size, const float *means2D,

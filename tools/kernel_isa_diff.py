@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Compare the kernels of two AMDGPU assembly files (hipcc -save-temps: *-hip-amdgcn-amd-amdhsa-gfx950.s).
 
-    python tools/kernel_isa_diff.py BEFORE.s AFTER.s
+    python tools/kernel_isa_diff.py BEFORE.s AFTER.s [--rename REGEX REPL]
 
 Per kernel symbol: the instruction lines with labels normalised, and the four resource figures of its kernel
 descriptor (.amdhsa_next_free_vgpr / _sgpr, .amdhsa_private_segment_fixed_size = scratch bytes,
 .amdhsa_group_segment_fixed_size = LDS bytes).  One SAME / DIFF line per kernel, `before -> after` where a figure
 changed; exit status 1 when a kernel differs or exists on one side only and is not matched by --allow REGEX.
+--rename REGEX REPL (repeatable): a kernel of AFTER whose demangled name, with REGEX replaced by REPL, is a kernel of
+BEFORE that AFTER no longer has is compared with that one -- for a change that adds template arguments, e.g.
+--rename ', false>$' '>' pairs k<3, true, false> with the earlier k<3, true>.
 Reads text only: nothing is compiled or run.
 """
 import argparse
@@ -58,8 +61,19 @@ def main():
     ap.add_argument("before")
     ap.add_argument("after")
     ap.add_argument("--allow", default=None, help="regex on the demangled name: these kernels may differ (exit status)")
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPL"),
+                    help="pair a kernel of AFTER with the kernel of BEFORE that its demangled name becomes under re.sub")
     a = ap.parse_args()
     old, new = parse(a.before), parse(a.after)
+    if a.rename:
+        pretty = demangle(sorted(set(old) | set(new)))
+        by_name = {pretty[n]: n for n in old if n not in new}
+        for n in [n for n in new if n not in old]:
+            was = pretty[n]
+            for rx, repl in a.rename:
+                was = re.sub(rx, repl, was)
+            if was != pretty[n] and was in by_name:
+                new[by_name.pop(was)] = new.pop(n)  # (listed under BEFORE's name)
     names = sorted(set(old) | set(new))
     pretty = demangle(names)
     bad = 0
