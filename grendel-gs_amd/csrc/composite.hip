@@ -174,7 +174,7 @@ __device__ __forceinline__ RawEntry load_raw(bool have, uint32_t id, const float
 // world size 8) that IS the kernel time (measured: K8 / K10 of a 1/8 band take 1/2.8 of the full image's time, and
 // neither a software prefetch nor another block -> tile map changes it, profiles/r04_ab_*).  The backward can be cut
 // exactly: K10 needs, per pixel, the transmittance T and the colour accumulated IN FRONT of a list position, both of
-// which the forward knows when it passes that position.  So K8 leaves a CHECKPOINT (T, C.rgb per pixel) every SEG_LEN
+// which the forward knows when it passes that position.  So K8 leaves a CHECKPOINT (T, colour sums per pixel) every SEG_LEN
 // entries it really walks and queues the segment that starts there; K10 runs segment 0 of every tile in its usual
 // workgroups and hands the queued segments to persistent worker workgroups (atomic ticket).  Work is only ever created
 // for entries the forward walked: early termination is untouched, nothing is recomputed.
@@ -189,15 +189,18 @@ constexpr int SEG_MAXJ = GSR_SEG_MAXJ;  // boundaries per tile that can carry a 
 static_assert(SEG_LEN % 64 == 0 && (SEG_LEN & (SEG_LEN - 1)) == 0 && SEG_MAXJ <= 31,
               "segment geometry: K8 finds boundaries with c & (SEG_LEN - 1), so SEG_LEN is a power of two");
 constexpr int SEG_WORKERS = 1024;
+constexpr int SEG_SLOT_FLOATS = 7 * 256;  // floats per checkpoint slot: T, P.rgb, B.rgb of 256 pixels
 struct SegWs {
     uint32_t *hdr;      // [0] segments queued by K8 (may exceed cap: only the first cap exist), [1] K10's ticket
     uint32_t *queue;    // [cap]: tile * 32 + segment index (>= 1)
     int32_t *seg_slot;  // [tiles][SEG_MAXJ]: checkpoint slot of the boundary at entry (j + 1) * SEG_LEN, -1: none
-    float *ckpt;        // [cap][4][256]: T, C.r, C.g, C.b of the tile's 256 pixels (quadrant-major: wave * 64 + lane)
+    float *ckpt;        // [cap][7][256], per pixel of the tile (quadrant-major: wave * 64 + lane): T in front of the boundary;
+                        // P.rgb, the colour blended between the wave's previous checkpoint and this one; B.rgb, the colour
+                        // blended BEHIND the boundary (K8 writes it when its walk ends, from the P of the later boundaries)
     uint32_t cap;
 };
 __host__ __device__ inline size_t seg_ws_bytes(int tiles, uint32_t cap) {
-    return 64 + sizeof(uint32_t) * (size_t)cap + sizeof(int32_t) * (size_t)tiles * SEG_MAXJ + sizeof(float) * 1024 * (size_t)cap;
+    return 64 + sizeof(uint32_t) * (size_t)cap + sizeof(int32_t) * (size_t)tiles * SEG_MAXJ + sizeof(float) * SEG_SLOT_FLOATS * (size_t)cap;
 }
 inline SegWs seg_ws_of(void *ws, int tiles, uint32_t cap) {
     SegWs w{};
@@ -213,9 +216,10 @@ inline SegWs seg_ws_of(void *ws, int tiles, uint32_t cap) {
 constexpr uint32_t SEG_CAP = 8192;
 
 // A segment boundary the calling wave really crosses (every SEG_LEN walked entries): the first wave of the tile to get here claims a checkpoint slot and queues the
-// segment for the backward; every wave that gets here leaves its pixels' state (T, colour in front of the boundary).
-__device__ __forceinline__ void k8_checkpoint(const SegWs &seg, int *s_slot, int tile, int c, int lane,
-                                                        int wave, float T, float c0, float c1, float c2) {
+// segment for the backward; every wave that gets here leaves its pixels' state: T, and the colour blended since the
+// wave's previous checkpoint (c0..c2).  -> the slot (wave-uniform), negative: none.
+__device__ __forceinline__ int k8_checkpoint(const SegWs &seg, int *s_slot, int tile, int c, int lane,
+                                                       int wave, float T, float c0, float c1, float c2) {
     const int j = c / SEG_LEN - 1;
     int slot = 0;
     if (lane == 0) {
@@ -235,12 +239,13 @@ __device__ __forceinline__ void k8_checkpoint(const SegWs &seg, int *s_slot, int
     }
     slot = __builtin_amdgcn_readfirstlane(slot);
     if (slot >= 0) {
-        float *ck = seg.ckpt + (size_t)slot * 1024 + wave * 64 + lane;
+        float *ck = seg.ckpt + (size_t)slot * SEG_SLOT_FLOATS + wave * 64 + lane;
         ck[0] = T;
         ck[256] = c0;
         ck[512] = c1;
         ck[768] = c2;
     }
+    return slot;
 }
 
 // ------------------------------------------------------------------------------------------- K8
@@ -339,6 +344,12 @@ composite_forward_kernel(int W, int H, int gx, const int2 *__restrict__ ranges,
     }
     __syncthreads();  // the only workgroup barrier of the kernel: all four waves are at their first instructions
     v2f A0 = {0.f, 0.f}, A1 = {0.f, 0.f}, A2 = {0.f, 0.f};  // colour sums of the even / odd pair slots (added at the end)
+    // SEG: the same sums once more, restarted at every checkpoint.  The backward needs the colour blended BEHIND a boundary;
+    // as (final colour - colour in front of the boundary) that is the difference of two sums of the image's magnitude, and
+    // its rounding, divided by the boundary's T, was the error of every row behind a deep boundary (EXPERIMENTS.md,
+    // 'Composite pixels and rows against float64').  Sums that start at the boundary carry the rounding of their own size.
+    v2f B0 = {0.f, 0.f}, B1 = {0.f, 0.f}, B2 = {0.f, 0.f};
+    int nstored = 0;  // boundaries this wave left a checkpoint at (wave-uniform; they are a prefix of the boundaries)
     float *wslab = slab[wave];
     int walked = 0;
 
@@ -347,8 +358,12 @@ composite_forward_kernel(int W, int H, int gx, const int2 *__restrict__ ranges,
     // thin band is bound by the imbalance of ONE round of resident workgroups, not by memory latency)
     for (int c = 0; c < n; c += 64) {
         if (__all(done)) break;
-        if (SEG && seg.seg_slot && c > 0 && (c & (SEG_LEN - 1)) == 0 && c <= SEG_LEN * SEG_MAXJ)
-            k8_checkpoint(seg, s_slot, tile, c, lane, wave, T, A0.x + A0.y, A1.x + A1.y, A2.x + A2.y);
+        if (SEG && seg.seg_slot && c > 0 && (c & (SEG_LEN - 1)) == 0 && c <= SEG_LEN * SEG_MAXJ) {
+            if (k8_checkpoint(seg, s_slot, tile, c, lane, wave, T, B0.x + B0.y, B1.x + B1.y, B2.x + B2.y) >= 0) {
+                B0 = B1 = B2 = v2f{0.f, 0.f};
+                nstored = c / SEG_LEN;
+            }
+        }
         walked = c + 64;
         const bool have = c + lane < n;
         const uint32_t id = have ? point_list[range.x + c + lane] : 0u;
@@ -417,6 +432,11 @@ composite_forward_kernel(int W, int H, int gx, const int2 *__restrict__ ranges,
                 A0 = __builtin_elementwise_fma(cr[h], w2, A0);
                 A1 = __builtin_elementwise_fma(cg[h], w2, A1);
                 A2 = __builtin_elementwise_fma(cb[h], w2, A2);
+                if (SEG) {
+                    B0 = __builtin_elementwise_fma(cr[h], w2, B0);
+                    B1 = __builtin_elementwise_fma(cg[h], w2, B1);
+                    B2 = __builtin_elementwise_fma(cb[h], w2, B2);
+                }
             }
             if (__all(done)) break;
         }
@@ -428,6 +448,20 @@ composite_forward_kernel(int W, int H, int gx, const int2 *__restrict__ ranges,
     C0 = A0.x + A0.y;
     C1 = A1.x + A1.y;
     C2 = A2.x + A2.y;
+    if (SEG && nstored > 0) {
+        // the colour behind each boundary this wave checkpointed, back to front: what was blended behind the last one, then
+        // plus the P of each boundary passed (this lane's own stores above)
+        float r0 = B0.x + B0.y, r1 = B1.x + B1.y, r2 = B2.x + B2.y;
+        for (int j = nstored - 1; j >= 0; j--) {  // wave-uniform
+            float *ck = seg.ckpt + (size_t)s_slot[j] * SEG_SLOT_FLOATS + wave * 64 + lane;
+            ck[1024] = r0;
+            ck[1280] = r1;
+            ck[1536] = r2;
+            r0 += ck[256];
+            r1 += ck[512];
+            r2 += ck[768];
+        }
+    }
     if (inside) {
         out_color[pid] = C0 + T * bg[0];
         out_color[HW + pid] = C1 + T * bg[1];
@@ -483,7 +517,7 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
                            const uint8_t *__restrict__ compute_locally, const float *__restrict__ bg,
                            const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
                            const float *__restrict__ dL_dpixels, double *__restrict__ dL_record,
-                           const float *__restrict__ out_color, const SegWs &seg, uint8_t *__restrict__ touched) {
+                           const SegWs &seg, uint8_t *__restrict__ touched) {
     if (!compute_locally[tile]) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tx = tile % gx, ty = tile / gx;
@@ -586,14 +620,11 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
     float rho = 0.f;  // (colour accumulated BEHIND the current position) . g
     if (end_slot >= 0 && last > c_hi) {
         // this pixel blends entries beyond the segment: start from the forward's state at the boundary.  T = the
-        // transmittance in front of entry c_hi; the colour behind it is what the pixel ended with (without the
-        // background's share) minus what it had accumulated in front of the boundary, normalised by T
-        const float *ck = seg.ckpt + (size_t)end_slot * 1024 + wave * 64 + lane;
+        // transmittance in front of entry c_hi; the colour blended behind it is the forward's own sum over those entries
+        // (not the image minus the colour in front: see K8), normalised by T
+        const float *ck = seg.ckpt + (size_t)end_slot * SEG_SLOT_FLOATS + wave * 64 + lane;
         T = ck[0];
-        const float r0 = out_color[pid] - T_final * bg[0] - ck[256];
-        const float r1 = out_color[HW + pid] - T_final * bg[1] - ck[512];
-        const float r2 = out_color[2 * HW + pid] - T_final * bg[2] - ck[768];
-        rho = (r0 * g0 + r1 * g1 + r2 * g2) * __builtin_amdgcn_rcpf(T);
+        rho = (ck[1024] * g0 + ck[1280] * g1 + ck[1536] * g2) * __builtin_amdgcn_rcpf(T);
     }
 
     // software prefetch: the list entries of a chunk are loaded one chunk ahead, their indices two chunks ahead (three
@@ -792,8 +823,7 @@ composite_backward_kernel(int W, int H, int gx, int tiles, const int2 *__restric
                           const uint8_t *__restrict__ compute_locally, const float *__restrict__ bg,
                           const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
                           const float *__restrict__ dL_dpixels, double *__restrict__ dL_record,
-                          const float *__restrict__ out_color, const SegWs seg, int band_first, int band_tiles,
-                          uint8_t *__restrict__ touched) {
+                          const SegWs seg, int band_first, int band_tiles, uint8_t *__restrict__ touched) {
     // workgroups [0, nstatic): segment 0 of every tile (of the band, when the caller named it: see K8), XCD-contiguous
     // spans.  The others are persistent workers: they take the segments K8 queued (their number is only known on the
     // device) by atomic ticket.
@@ -825,7 +855,7 @@ composite_backward_kernel(int W, int H, int gx, int tiles, const int2 *__restric
                                   : composite_tile_of_block(ranges, gx, tiles);
         }
         composite_backward_segment(tile, sidx, W, H, gx, ranges, point_list, means2D, conic_opacity, rgb,
-                                   compute_locally, bg, final_T, n_contrib, dL_dpixels, dL_record, out_color, seg, touched);
+                                   compute_locally, bg, final_T, n_contrib, dL_dpixels, dL_record, seg, touched);
         if (!worker) return;
     }
 }
@@ -949,7 +979,7 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
     hipLaunchKernelGGL(composite_backward_kernel, grid, dim3(256), 0, stream, W, H, gx, gx * gy,
                        reinterpret_cast<const int2 *>(ranges), point_list, reinterpret_cast<const float2 *>(means2D),
                        reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
-                       dL_dpixels, acc64, out_color, seg, b.band_first, b.band_tiles, touched);
+                       dL_dpixels, acc64, seg, b.band_first, b.band_tiles, touched);
     GSR_LAUNCH_CHECK();
     if (touched)
         hipLaunchKernelGGL(record_from_f64_touched_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream,

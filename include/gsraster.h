@@ -307,12 +307,16 @@ int gsr_bin_sort_bounded(int P, int width, int height, const uint8_t *compute_lo
  *   workgroups at world size 8).  The backward can be cut exactly: per pixel it needs the transmittance and the colour
  *   accumulated IN FRONT of a list position, which the forward knows when it passes that position.  With a workspace of
  *   gsr_render_seg_bytes(width, height) bytes (caller-allocated, alive and untouched until the backward has run) the
- *   forward leaves a checkpoint (T, C.rgb per pixel) every 256 list entries it really walks and queues the segment that
- *   starts there; the backward, given the same workspace, runs segment 0 of every tile in its usual workgroups and hands
- *   the queued segments to persistent worker workgroups.  It then needs out_color = the forward's image (the colour
- *   BEHIND a boundary is the final colour minus the checkpointed one).  Early termination is untouched (segments exist
- *   only for entries the forward walked); gradients equal the one-segment kernel's up to fp32 rounding (the checkpointed
- *   T replaces a chain of divisions).  A second backward over one forward walks the same segments again.
+ *   forward leaves a checkpoint every 256 list entries it really walks -- per pixel T, the colour blended since the
+ *   previous checkpoint and, filled in when the walk ends, the colour blended behind this one: 7 KiB per tile and
+ *   boundary -- and queues the segment that starts there; the backward, given the same workspace, runs segment 0 of every tile in its usual workgroups and hands
+ *   the queued segments to persistent worker workgroups.  The colour BEHIND a boundary is the forward's own sum over the
+ *   entries behind it (the checkpoints carry per-segment colour sums; the image minus the colour in front of the
+ *   boundary would carry the image's rounding divided by the boundary's T).  out_color = the forward's image is still
+ *   required with a workspace, for callers of earlier versions; the kernel no longer reads it.  Early termination is
+ *   untouched (segments exist only for entries the forward walked); gradients equal the one-segment kernel's up to fp32
+ *   rounding (the checkpointed T replaces a chain of divisions).  A second backward over one forward walks the same
+ *   segments again.
  *   seg_ws == NULL: no segments; seg_bytes is ignored and out_color may be NULL in the backward.
  *   A workspace that is too small: GSR_ENOSPACE (forward), GSR_EINVAL (backward; also for out_color == NULL).
  *
