@@ -109,7 +109,8 @@ __device__ __forceinline__ Entry load_entry(bool have, uint32_t id, const float2
 // terms) is done for TWO entries per instruction.  For that the RELEVANT entries of a chunk are compacted (in walk
 // order) into pair records in the wave's LDS slab, the two entries' values of each field next to each other, so
 // that one broadcast read returns register PAIRS: rec = {xa xb ya yb | a2a a2b b2a b2b | c2a c2b oa ob | ra rb ga gb |
-// ba bb - -}.  Slots behind the last entry are zeroed (K8) or never evaluated (K10).
+// ba bb la lb}.  la, lb are K8's alone (pair_store_last).  Slots behind the last entry are inert records (K8) or never
+// evaluated (K10).
 typedef float v2f __attribute__((ext_vector_type(2)));
 constexpr int PREC = 20;  // floats per pair record (80 bytes: 16-byte aligned reads)
 struct PairRec {
@@ -120,6 +121,33 @@ __device__ __forceinline__ void pair_store(float *__restrict__ slab, int pos, co
     rec[0] = e.x;  rec[2] = e.y;  rec[4] = e.a2;  rec[6] = e.b2;  rec[8] = e.c2;
     rec[10] = e.o; rec[12] = r;   rec[14] = g;    rec[16] = b;
 }
+// K8 only: the value n_contrib takes if the entry in slot `pos` is the pixel's last blended one (list position + 1),
+// as bits in one of the record's two spare floats -- the walk reads it back with the record instead of deriving the
+// slot's list position from the ballot mask (a serial scalar chain per slot).  K10 neither writes nor reads it.
+__device__ __forceinline__ void pair_store_last(float *__restrict__ slab, int pos, int last) {
+    slab[(pos >> 1) * PREC + 18 + (pos & 1)] = __int_as_float(last);
+}
+// K8's read of a pair record (wave-uniform address): the fifth quad carries b and the two `last` values, one 16-byte read
+__device__ __forceinline__ PairRec pair_load_last(const float *__restrict__ slab, int pair, int &la, int &lb) {
+    const float4 *q = reinterpret_cast<const float4 *>(slab + pair * PREC);
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
+    PairRec p;
+    p.x = v2f{q0.x, q0.y};  p.y = v2f{q0.z, q0.w};  p.a2 = v2f{q1.x, q1.y};  p.b2 = v2f{q1.z, q1.w};
+    p.c2 = v2f{q2.x, q2.y}; p.o = v2f{q2.z, q2.w};  p.r = v2f{q3.x, q3.y};   p.g = v2f{q3.z, q3.w};
+    p.b = v2f{q4.x, q4.y};
+    la = __float_as_int(q4.z);
+    lb = __float_as_int(q4.w);
+    // (opaque to the compiler: a select whose operand IS a load gets turned into a branch around a 4-byte read, which
+    // splits this quad's read in three and puts an exec-masked block into the walk's inner loop)
+    asm("" : "+v"(la), "+v"(lb));
+    return p;
+}
+// opacity term of an INERT slot: the exponent becomes -inf, exp2 gives +0, and the alpha >= 1/255 test fails by itself
+#ifdef GSR_LOG2O
+#define GSR_PAD_O (-__builtin_inff())
+#else
+#define GSR_PAD_O 0.f
+#endif
 __device__ __forceinline__ PairRec pair_load(const float *__restrict__ slab, int pair) {  // wave-uniform address
     const float4 *q = reinterpret_cast<const float4 *>(slab + pair * PREC);
     const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
@@ -251,7 +279,7 @@ __device__ __forceinline__ int k8_checkpoint(const SegWs &seg, int *s_slot, int 
 // ------------------------------------------------------------------------------------------- K8
 template <bool SEG, bool BAND>  // SEG: leave checkpoints for the backward's list segments; BAND: the grid covers the
                                 // band's tiles only (each costs registers: the whole-image launch keeps its 64)
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, SEG ? 6 : (BAND ? 7 : 8))  // waves per SIMD: <= 80 / 72 / 64 VGPRs
 composite_forward_kernel(int W, int H, int gx, const int2 *__restrict__ ranges,
                          const uint32_t *__restrict__ point_list, const float2 *__restrict__ means2D,
                          const float4 *__restrict__ conic_opacity, const float *__restrict__ rgb,
@@ -382,31 +410,53 @@ composite_forward_kernel(int W, int H, int gx, const int2 *__restrict__ ranges,
         // WITHOUT spending VALU issue slots, and the VALU is what bounds this kernel.  No barrier: the slab is private to
         // the wave and LDS operations of one wave execute in order.
         const int nrel = __popcll(m);
+#ifdef GSR_ABL_K8_MASKWALK  // ablation: slot positions from the ballot mask, zeroed padding masked by `live`
         if (e.relevant) pair_store(wslab, __popcll(m & ((1ull << lane) - 1ull)), e, r, g, b);
         {   // the walk below takes four slots at a time: zero the <= 3 slots behind the last entry (a stale colour times
             // a zero weight would still be a NaN if the stale bits are one)
             const int pad = (-nrel) & 3, slot = nrel + lane / 9;
             if (lane < 9 * pad) wslab[(slot >> 1) * PREC + 2 * (lane % 9) + (slot & 1)] = 0.f;
         }
+#else
+        if (e.relevant) {
+            const int pos = __popcll(m & ((1ull << lane) - 1ull));
+            pair_store(wslab, pos, e, r, g, b);
+            pair_store_last(wslab, pos, c + lane + 1);
+        }
+        {   // the walk below takes four slots at a time: the <= 3 slots behind the last entry are made INERT -- all ten
+            // fields written (nothing stale is ever read: a stale colour times a zero weight would still be a NaN if the
+            // stale bits are one), zeros except the opacity term, with which the slot fails the alpha test by itself
+            const int pad = (-nrel) & 3, slot = nrel + lane / 10, f = lane % 10;
+            if (lane < 10 * pad) wslab[(slot >> 1) * PREC + 2 * f + (slot & 1)] = f == 5 ? GSR_PAD_O : 0.f;
+        }
+#endif
         // Entries are taken four (two pairs) at a time: their alphas are independent (ILP across the LDS and v_exp
         // latency), only the short T chain is sequential, and the wave tests "everybody done?" once per group.
         for (int p0 = 0; p0 < nrel; p0 += 4) {  // wave-uniform
             float al[4];
             bool ok[4];
-            int kk[4];
+            int kk[4];  // list position + 1 of the slot's entry: n_contrib if it is the pixel's last blended one
             v2f cr[2], cg[2], cb[2];
 #pragma unroll
             for (int h = 0; h < 2; h++) {
+#ifdef GSR_ABL_K8_MASKWALK
                 const PairRec pr = pair_load(wslab, (p0 >> 1) + h);
+#else
+                const PairRec pr = pair_load_last(wslab, (p0 >> 1) + h, kk[2 * h], kk[2 * h + 1]);
+#endif
                 const v2f pe = pair_exponent(pr, pxf, pyf);
                 cr[h] = pr.r;
                 cg[h] = pr.g;
                 cb[h] = pr.b;
 #pragma unroll
                 for (int u = 0; u < 2; u++) {
+#ifdef GSR_ABL_K8_MASKWALK
                     const bool live = m != 0;  // wave-uniform: entry p0 + 2 h + u exists
-                    kk[2 * h + u] = live ? __builtin_ctzll(m) : 0;
+                    kk[2 * h + u] = c + (live ? __builtin_ctzll(m) : 0) + 1;
                     m &= m - 1;  // 0 & ~0 stays 0
+#else
+                    const bool live = true;    // (an inert slot fails the alpha test)
+#endif
                     const float pe1 = u ? pe.y : pe.x, lo = u ? pr.o.y : pr.o.x;
                     al[2 * h + u] = fminf(0.99f, __builtin_amdgcn_exp2f(pe1));
                     ok[2 * h + u] = live && pe1 <= lo && al[2 * h + u] >= ALPHA_MIN;  // power <= 0  <=>  exponent <= log2 o
@@ -415,16 +465,16 @@ composite_forward_kernel(int W, int H, int gx, const int2 *__restrict__ ranges,
             float wv[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                const bool take = !done && ok[u];
                 const float w0 = al[u] * T;
                 const float test_T = T - w0;  // T (1 - alpha) >= 0: compared as an integer so that `!stop` below is the
                 // complement of ONE compare (a float `<` and its negation are two instructions: NaN semantics)
+                const bool take = !done && ok[u];
                 const bool stop = take && __float_as_int(test_T) < __float_as_int(T_STOP);
                 done = done || stop;
                 const bool blend = take && !stop;
                 wv[u] = blend ? w0 : 0.f;
                 T = blend ? test_T : T;
-                last = blend ? c + kk[u] + 1 : last;
+                last = blend ? kk[u] : last;
             }
 #pragma unroll
             for (int h = 0; h < 2; h++) {

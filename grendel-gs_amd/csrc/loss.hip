@@ -105,6 +105,9 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
     __shared__ v2f hCD[HH][HSTR];       // ... of (x^2, y^2)
     __shared__ float hE[HH][HSTR];      // ... of x y
     __shared__ float red[LT / 64];
+#ifndef GSR_ABL_LOSS_TWO_REDUCTIONS
+    __shared__ float red2[LT / 64];
+#endif
     int c, ox, oy, nwg;
     long long row_off;
     const int rows_cap = rows;
@@ -176,6 +179,11 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
             xy[i] = sXY[r][cx0 + i];
             sq[i] = xy[i] * xy[i];
             pr[i] = xy[i].x * xy[i].y;
+#ifndef GSR_ABL_LOSS_FWD_OUTPUT_PAIRS
+            // (opaque: left alone, the compiler forms x y for two elements per v_pk_mul_f32 and pairs adjacent outputs of
+            // this map, whose windows start at odd registers -- four moves per multiply saved, and more for the pairs)
+            asm("" : "+v"(pr[i]));
+#endif
         }
 #pragma unroll
         for (int o = 0; o < 4; o++) {
@@ -205,6 +213,9 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
             p[i] = hAB[ty0 + i][tx];
             q[i] = hCD[ty0 + i][tx];
             t[i] = hE[ty0 + i][tx];
+#ifndef GSR_ABL_LOSS_FWD_OUTPUT_PAIRS
+            asm("" : "+v"(t[i]));
+#endif
         }
 #pragma unroll
         for (int o = 0; o < VO; o++) {
@@ -248,8 +259,25 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
             }
         }
     }
+#ifdef GSR_ABL_LOSS_TWO_REDUCTIONS  // ablation: one block_sum (two barriers) per sum
     const float sl1 = block_sum(l1, red);
     const float sss = block_sum(ssim_sum, red);
+#else
+    // both sums through ONE pair of barriers; each keeps its own butterfly and its own order over the waves
+    float sl1 = l1, sss = ssim_sum;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sl1 += __shfl_xor(sl1, d, 64);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sss += __shfl_xor(sss, d, 64);
+    if ((tid & 63) == 0) {
+        red[tid >> 6] = sl1;
+        red2[tid >> 6] = sss;
+    }
+    __syncthreads();
+    sl1 = sss = 0.f;
+    for (int w = 0; w < LT / 64; w++) sl1 += red[w];
+    for (int w = 0; w < LT / 64; w++) sss += red2[w];
+#endif
     if (tid == 0) {  // indexed by tile, not by workgroup: the finalize adds them in the same fixed order either way
         partials[2 * (size_t)tile_id] = sl1;
         partials[2 * (size_t)tile_id + 1] = sss;
