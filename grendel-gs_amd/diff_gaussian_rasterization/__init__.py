@@ -2076,6 +2076,125 @@ def densify_move(cls, ranks, counts, srcs, dsts, roles, alts=None, rotation=None
     return n_new
 
 
+# ------------------------------------------------------------------------------------------ 3DGS-MCMC
+MCMC_ROLE_COPY, MCMC_ROLE_MOMENT, MCMC_ROLE_OPACITY, MCMC_ROLE_SCALING = 0, 1, 2, 3
+MCMC_N_MAX = 51
+
+
+def _mcmc_dense(t, name, dtype=torch.float32):
+    if not t.is_cuda:
+        raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must live on the gfx950 device (no CPU fallback)")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{name}: a dense {dtype} tensor expected")
+    return t
+
+
+def mcmc_relocate_plan(opacity_act, n_add, min_opacity, seed, event, src=None, count=None, workspace=None):
+    """the plan of a relocation event (include/gsraster.h: gsr_mcmc_relocate_plan): opacity_act fp32 [P] (activated) ->
+    (src int32 [P+n_add], count int32 [P], totals int64 [2] = {n_dead, n_alive}), all on the device; nothing is read back.
+    src / count / workspace: buffers to reuse (at least P+n_add / P elements / gsr_mcmc_relocate_bytes(P) bytes)."""
+    op = _mcmc_dense(opacity_act, "opacity_act").reshape(-1)
+    P, n_add, dev = op.shape[0], int(n_add), op.device
+    if n_add < 0:
+        raise ValueError("n_add must not be negative")
+    if src is None or src.numel() < P + n_add:
+        src = torch.empty(max(P + n_add, 1), dtype=torch.int32, device=dev)
+    if count is None or count.numel() < P:
+        count = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    _mcmc_dense(src, "src", torch.int32)
+    _mcmc_dense(count, "count", torch.int32)
+    nbytes = lib.gsr_mcmc_relocate_bytes(P)
+    if workspace is None or workspace.numel() * workspace.element_size() < nbytes:
+        workspace = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    if P == 0:  # no row to draw from (the entry point writes nothing): no destination has a source
+        src.view(-1)[:n_add].fill_(-1)
+        return src.view(-1)[:n_add], count.view(-1)[:0], totals.zero_()
+    with _on(dev):
+        check(lib.gsr_mcmc_relocate_plan(P, n_add, _ptr(op), float(min_opacity), int(seed) & (2 ** 64 - 1),
+                                         int(event) & 0xffffffff, _ptr(src), _ptr(count), _ptr(totals), _ptr(workspace),
+                                         workspace.numel() * workspace.element_size(), _stream()),
+              "gsr_mcmc_relocate_plan")
+    return src.view(-1)[:P + n_add], count.view(-1)[:P], totals
+
+
+def mcmc_relocate_apply(src, count, opacity_act, min_opacity, tensors, roles, n_max=MCMC_N_MAX):
+    """apply a relocation plan IN PLACE to every tensor in two launches (include/gsraster.h: gsr_mcmc_relocate_apply).
+    src [P+n_add] / count [P]: the plan's; tensors[k]: [>= P+n_add, ...] dense, 4-byte elements; roles[k] one of
+    MCMC_ROLE_*."""
+    op = _mcmc_dense(opacity_act, "opacity_act").reshape(-1)
+    _mcmc_dense(src, "src", torch.int32)
+    _mcmc_dense(count, "count", torch.int32)
+    P, rows, K = op.shape[0], src.shape[0], len(tensors)
+    if count.shape[0] != P or rows < P:
+        raise ValueError("mcmc_relocate_apply: src [P+n_add] and count [P] of the plan expected")
+    if K > 32:
+        raise ValueError("mcmc_relocate_apply: at most 32 tensors per call")
+    if not 1 <= int(n_max) <= MCMC_N_MAX:
+        raise ValueError(f"n_max must lie in [1, {MCMC_N_MAX}]")
+    widths = []
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("diff_gaussian_rasterization: every tensor must live on the gfx950 device (no CPU "
+                               "fallback)")
+        if t.element_size() != 4 or not t.is_contiguous() or t.shape[0] < rows:
+            raise ValueError("mcmc_relocate_apply: dense tensors of 4-byte elements with at least P + n_add rows expected")
+        w = 1
+        for d in t.shape[1:]:
+            w *= d
+        widths.append(w)
+    if K == 0 or P == 0:
+        return
+    VP = ctypes.c_void_p * K
+    with _on(op.device):
+        check(lib.gsr_mcmc_relocate_apply(P, rows - P, _ptr(src), _ptr(count), _ptr(op), float(min_opacity), int(n_max), K,
+                                          VP(*[t.data_ptr() for t in tensors]), (ctypes.c_int32 * K)(*widths),
+                                          (ctypes.c_int64 * K)(*widths), (ctypes.c_int32 * K)(*[int(r) for r in roles]),
+                                          _stream()), "gsr_mcmc_relocate_apply")
+
+
+def mcmc_normals(n, seed, step, device=None, out=None):
+    """the xi [n,3] that mcmc_noise(xi=None) draws for rows 0..n-1 at (seed, step) (gsr_mcmc_normals)"""
+    if out is None:
+        out = torch.empty((int(n), 3), dtype=torch.float32, device=device if device is not None else "cuda")
+    _mcmc_dense(out, "out")
+    if out.numel() < 3 * int(n):
+        raise ValueError("out: room for [n,3] expected")
+    with _on(out.device):
+        check(lib.gsr_mcmc_normals(int(n), int(seed) & (2 ** 64 - 1), int(step) & 0xffffffff, _ptr(out), _stream()),
+              "gsr_mcmc_normals")
+    return out
+
+
+def mcmc_noise(xyz, scaling_raw, rotation_raw, opacity_raw, scaler, xi=None, seed=0, step=0):
+    """xyz += scaler * g(1 - sigmoid(opacity_raw)) * Sigma * xi, in place, one launch (gsr_mcmc_noise).  xi None: drawn in
+    the kernel from (seed, step) -- the values of mcmc_normals; otherwise a dense fp32 [P,3]."""
+    P = xyz.shape[0]
+    for t, name, shape in ((xyz, "xyz", (P, 3)), (scaling_raw, "scaling_raw", (P, 3)),
+                           (rotation_raw, "rotation_raw", (P, 4)), (xi, "xi", (P, 3))):
+        if t is not None and tuple(_mcmc_dense(t, name).shape) != shape:
+            raise ValueError(f"{name}: shape {shape} expected")
+    if _mcmc_dense(opacity_raw, "opacity_raw").numel() != P:
+        raise ValueError("opacity_raw: P elements expected")
+    with _on(xyz.device):
+        check(lib.gsr_mcmc_noise(P, _ptr(xyz), _ptr(scaling_raw), _ptr(rotation_raw), _ptr(opacity_raw), float(scaler),
+                                 _ptr(xi), int(seed) & (2 ** 64 - 1), int(step) & 0xffffffff, _stream()),
+              "gsr_mcmc_noise")
+    return xyz
+
+
+def mcmc_reg_grad(opacity_raw, scaling_raw, c_opacity, c_scale, grad_opacity, grad_scaling):
+    """grad_opacity += c_opacity * o (1 - o), grad_scaling += c_scale * exp(s), in place, one launch (gsr_mcmc_reg_grad)"""
+    P = scaling_raw.shape[0]
+    for t, name, numel in ((opacity_raw, "opacity_raw", P), (scaling_raw, "scaling_raw", 3 * P),
+                           (grad_opacity, "grad_opacity", P), (grad_scaling, "grad_scaling", 3 * P)):
+        if _mcmc_dense(t, name).numel() != numel:
+            raise ValueError(f"{name}: {numel} elements expected")
+    with _on(scaling_raw.device):
+        check(lib.gsr_mcmc_reg_grad(P, _ptr(opacity_raw), _ptr(scaling_raw), float(c_opacity), float(c_scale),
+                                    _ptr(grad_opacity), _ptr(grad_scaling), _stream()), "gsr_mcmc_reg_grad")
+
+
 # ------------------------------------------------------------------------------------------ _C
 class _CNamespace:
     """stand-in for the reference extension's pybind module `diff_gaussian_rasterization._C`."""

@@ -92,6 +92,15 @@ SIGNATURES = {
     "gsr_densify_plan": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gsr_densify_move": (c_int, [c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int] +
                          [c_void_p] * 7 + [c_int64, c_void_p, c_void_p, c_void_p]),
+    "gsr_mcmc_relocate_bytes": (c_size_t, [c_int64]),
+    "gsr_mcmc_relocate_plan": (c_int, [c_int64, c_int64, c_void_p, c_float, ctypes.c_uint64, ctypes.c_uint32, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gsr_mcmc_relocate_apply": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int] +
+                                [c_void_p] * 5),
+    "gsr_mcmc_noise": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, ctypes.c_uint64,
+                               ctypes.c_uint32, c_void_p]),
+    "gsr_mcmc_normals": (c_int, [c_int64, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p]),
+    "gsr_mcmc_reg_grad": (c_int, [c_int64, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, ctypes.c_double, c_int64, c_float, c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int] + [c_void_p] * 10 + [c_float, c_void_p]),

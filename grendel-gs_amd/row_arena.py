@@ -73,6 +73,21 @@ class RowArena:
             h = halves[i] = torch.empty((self.capacity,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
         return h
 
+    def extend(self, key, t, rows):
+        """the first `rows` rows of the half that `t` lives in, `t` being its first t.shape[0] rows: the longer view of the
+        SAME storage, nothing moves (the rows beyond t are undefined until the caller writes them).  A tensor that does
+        not live in the arena yet -- or whose half is too short, after a growth -- is copied once into a reserved half.
+        For in-place row growth (mcmc.MCMCStrategy.relocate_and_grow)."""
+        self.reserve(rows)
+        halves = self._halves.setdefault(key, [None, None])
+        cur = self.half_of(key, t)
+        if cur is not None and halves[cur].shape[0] >= rows and t.data_ptr() == halves[cur].data_ptr():
+            return halves[cur][:rows]
+        h = torch.empty((self.capacity,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
+        h[:t.shape[0]].copy_(t)
+        halves[cur if cur is not None else 0] = h  # (a half that was too short goes when its last view does)
+        return h[:rows]
+
     def release_other(self, key, live):
         """drop the half of `key` that `live` is not a view of when it is smaller than the capacity (after a growth: the
         next event would have to replace it anyway, so its memory goes back now rather than then)"""

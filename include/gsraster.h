@@ -651,6 +651,65 @@ int gsr_densify_move(int64_t P, const uint8_t *cls, const int32_t *ranks, int64_
                      const float *samples, gsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N4  fixed-budget densification: 3DGS-MCMC (new symbols, ABI unchanged; csrc/mcmc.hip).  Neither the reference nor its
+ * rasterizer has it; the formulas are those of "3D Gaussian Splatting as Markov Chain Monte Carlo".  Dead rows are
+ * teleported IN PLACE onto live rows drawn in proportion to opacity, the population grows by a host-known n_add rows,
+ * and a state-dependent noise term moves the positions after every optimizer step.  No call reads anything back.
+ * Determinism: every draw is Philox4x32-10 keyed by `seed` (low word first) with counter (row low, row high, event or
+ * step, domain) -- domain 1 for the relocation draws, 2 for the noise -- so the same seed, event / step and inputs give
+ * the same bits on any grid.  All arguments are validated before any launch (GSR_EINVAL); P == 0 returns 0 without one.
+ * P + n_add <= 2^31 - 1.
+ *
+ * gsr_mcmc_relocate_bytes(rows) answers: how large a workspace does a plan over `rows` rows need (8-byte aligned)?
+ * gsr_mcmc_relocate_plan answers: which row does every destination take its values from, and how often is each row
+ *   drawn?  opacity_act: the ACTIVATED opacity, dense fp32 [P].  A row is dead iff opacity <= min_opacity (or NaN).
+ *   Destinations: the dead rows and the new rows P .. P+n_add-1.  Weights w_i = dead ? 0 : (uint32)(opacity_i * 2^24),
+ *   exclusive prefix sums in uint64 (three plain launches: tile sums, scan of the tile sums, draw).  Destination d draws
+ *   r = mulhi64(x0 | x1 << 32, total) and takes the unique i with prefix[i] <= r < prefix[i] + w_i.
+ *   src int32 [P+n_add]: the source row, -1 for a row that is no destination; count int32 [P]: draws per row; totals
+ *   int64 [2] on the device: {n_dead, n_alive}.  total == 0 (no live row): every src is -1.  P == 0 writes nothing.
+ *   A workspace smaller than gsr_mcmc_relocate_bytes(P), or not 8-byte aligned: GSR_EINVAL.
+ * gsr_mcmc_relocate_apply answers: what do the rows hold after the event?  In place on num_tensors <= 32 tensors of
+ *   4-byte words with at least P + n_add rows (HOST tables; strides in words).  With n = min(count_i + 1, n_max),
+ *   1 <= n_max <= GSR_MCMC_N_MAX, evaluated in fp64 from opacity_act (o):
+ *       o' = -expm1(log1p(-o) / n),   D = sum_{k=0}^{n-1} C(n,k+1) (-1)^k o'^(k+1) / sqrt(k+1),   f = o / D,
+ *   o' then clamped to [min_opacity, 1 - 2^-23].  Roles:
+ *     COPY     a destination copies its source's row bit for bit; sources keep theirs;
+ *     OPACITY  width 1; source and destination become log(o' / (1 - o'));
+ *     SCALING  width 3; source and destination become the source's OLD raw scale + log(f);
+ *     MOMENT   zero on every source and every destination row, untouched elsewhere.
+ *   Two launches: destinations first (they only read source rows), then the sources.  A destination is re-derived from
+ *   opacity_act (row >= P or dead); src[] is clamped into [0, P) and must name a live row, else the row is left alone.
+ * gsr_mcmc_noise answers: where are the positions after this iteration's noise?  In place, one launch:
+ *       xyz += scaler * g(1 - sigmoid(opacity_raw)) * Sigma * xi,    g(x) = 1 / (1 + exp(-100 (x - 0.995))),
+ *       Sigma = R diag(exp(scaling_raw))^2 R^T,  R = R(q / |q|) of rotation_raw (16-byte aligned, dense [P,4]).
+ *   xi != NULL: dense [P,3] supplied by the caller; xi == NULL: drawn in the kernel, Box-Muller on
+ *   u = ((x >> 8) + 0.5) * 2^-24 of the Philox words of (row, step): finite, |xi| <= 5.89.
+ * gsr_mcmc_normals answers: which xi would gsr_mcmc_noise draw for rows 0 .. n-1 at (seed, step)?  out: dense [n,3].
+ * gsr_mcmc_reg_grad answers: what are the gradients once the regulariser c_opacity * sum(sigmoid(opacity_raw)) +
+ *   c_scale * sum(exp(scaling_raw)) is added?  In place: grad_opacity [P] += c_opacity * o (1 - o), grad_scaling [P,3]
+ *   += c_scale * exp(s).  The caller folds lambda / count into the constants. */
+#define GSR_MCMC_ROLE_COPY 0
+#define GSR_MCMC_ROLE_MOMENT 1
+#define GSR_MCMC_ROLE_OPACITY 2
+#define GSR_MCMC_ROLE_SCALING 3
+#define GSR_MCMC_N_MAX 51
+size_t gsr_mcmc_relocate_bytes(int64_t rows);
+int gsr_mcmc_relocate_plan(int64_t P, int64_t n_add, const float *opacity_act, float min_opacity, uint64_t seed,
+                           uint32_t event, int32_t *src, int32_t *count, int64_t *totals, void *workspace,
+                           size_t workspace_bytes, gsr_stream_t stream);
+int gsr_mcmc_relocate_apply(int64_t P, int64_t n_add, const int32_t *src, const int32_t *count,
+                            const float *opacity_act, float min_opacity, int n_max, int num_tensors,
+                            void *const *tensors, const int32_t *widths, const int64_t *strides, const int32_t *roles,
+                            gsr_stream_t stream);
+int gsr_mcmc_noise(int64_t P, float *xyz, const float *scaling_raw, const float *rotation_raw,
+                   const float *opacity_raw, float scaler, const float *xi, uint64_t seed, uint32_t step,
+                   gsr_stream_t stream);
+int gsr_mcmc_normals(int64_t n, uint64_t seed, uint32_t step, float *out, gsr_stream_t stream);
+int gsr_mcmc_reg_grad(int64_t P, const float *opacity_raw, const float *scaling_raw, float c_opacity, float c_scale,
+                      float *grad_opacity, float *grad_scaling, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1 / K11 on the RAW parameters of GaussianModel (scene/gaussian_model.py:219-242): `scaling` log-scales
  * [P,3], `rotation` un-normalised quaternions [P,4], `opacity` logits [P,1], `features_dc` [P,1,3],
  * `features_rest` [P,sh_coeffs-1,3].  The getters' activations (scene/gaussian_model.py:109-129: exp,
