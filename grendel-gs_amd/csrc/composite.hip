@@ -109,8 +109,8 @@ __device__ __forceinline__ Entry load_entry(bool have, uint32_t id, const float2
 // terms) is done for TWO entries per instruction.  For that the RELEVANT entries of a chunk are compacted (in walk
 // order) into pair records in the wave's LDS slab, the two entries' values of each field next to each other, so
 // that one broadcast read returns register PAIRS: rec = {xa xb ya yb | a2a a2b b2a b2b | c2a c2b oa ob | ra rb ga gb |
-// ba bb la lb}.  la, lb are K8's alone (pair_store_last).  Slots behind the last entry are inert records (K8) or never
-// evaluated (K10).
+// ba bb la lb}.  la, lb are the entries' list positions + 1 (pair_store_last).  Slots behind the last entry that a walk
+// still evaluates (K8: up to three, K10: one) are inert records.
 typedef float v2f __attribute__((ext_vector_type(2)));
 constexpr int PREC = 20;  // floats per pair record (80 bytes: 16-byte aligned reads)
 struct PairRec {
@@ -121,13 +121,15 @@ __device__ __forceinline__ void pair_store(float *__restrict__ slab, int pos, co
     rec[0] = e.x;  rec[2] = e.y;  rec[4] = e.a2;  rec[6] = e.b2;  rec[8] = e.c2;
     rec[10] = e.o; rec[12] = r;   rec[14] = g;    rec[16] = b;
 }
-// K8 only: the value n_contrib takes if the entry in slot `pos` is the pixel's last blended one (list position + 1),
-// as bits in one of the record's two spare floats -- the walk reads it back with the record instead of deriving the
-// slot's list position from the ballot mask (a serial scalar chain per slot).  K10 neither writes nor reads it.
+// The list position + 1 of the entry in slot `pos`, as bits in one of the record's two spare floats -- the walk reads it
+// back with the record instead of deriving the slot's list position from the ballot mask (a serial scalar chain per
+// slot).  K8: the value n_contrib takes if the entry is the pixel's last blended one.  K10: compared with n_contrib
+// (`position + 1 <= last`: the pixel blended the entry), and minus c + 1 the entry's chunk index, which is its row in
+// the wave's result table.  An inert slot of K10 carries K10_NO_POS, which no n_contrib reaches.
 __device__ __forceinline__ void pair_store_last(float *__restrict__ slab, int pos, int last) {
     slab[(pos >> 1) * PREC + 18 + (pos & 1)] = __int_as_float(last);
 }
-// K8's read of a pair record (wave-uniform address): the fifth quad carries b and the two `last` values, one 16-byte read
+// read of a pair record (wave-uniform address): the fifth quad carries b and the two `last` values, one 16-byte read
 __device__ __forceinline__ PairRec pair_load_last(const float *__restrict__ slab, int pair, int &la, int &lb) {
     const float4 *q = reinterpret_cast<const float4 *>(slab + pair * PREC);
     const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
@@ -537,7 +539,9 @@ composite_forward_kernel(int W, int H, int gx, const int2 *__restrict__ ranges,
 //   phase A (lane = pixel): walk the pair records back to front; recompute alpha, carry T and rho = R.g (R = colour
 //       behind the entry: ONE scalar recurrence instead of three), and store (q, w) of the entry into a wave-private
 //       LDS matrix [slot][pixel] -- ~20 VALU instructions per (wave, entry) where the transposed butterfly reduction
-//       this replaces needed ~80 (SQ_INSTS_VALU 277 M -> 98 M per launch on the bench views);
+//       this replaces needed ~80 (SQ_INSTS_VALU 277 M -> 98 M per launch on the bench views); a pair per trip on a
+//       trip count: an entry's list position is read with its record (pair_store_last), an odd count is filled with
+//       one inert record, and the scalar unit carries a loop counter and four predicate ANDs per pair, nothing else;
 //   phase B (every 8 entries): 16 K-steps of 4 pixels.  Lane (k = lane >> 4, i = lane & 15) reads component i >> 3 of
 //       slot i & 7, pixel 4 t + k -- the A operand: rows 0-7 are the q-rows of the eight slots, rows 8-15 their w-rows;
 //       conflict-free with the row stride of 66 -- and issues ONE v_mfma_f32_16x16x4_f32 against a per-lane constant
@@ -558,6 +562,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MB = 8;      // entries per MFMA batch: rows 0-7 of the 16 x 16 result are their q-rows, rows 8-15 their w-rows
 constexpr int MSTR = 66;   // row stride of the (q, w) matrix in 8-byte elements: phase A writes and phase B reads conflict-free
+[[maybe_unused]] constexpr int K10_NO_POS = 0x7fffffff;  // position word of an inert slot: fails `position + 1 <= n_contrib`
 
 // segment `sidx` of tile `tile`: the list entries [sidx * SEG_LEN, next boundary with a checkpoint or the end)
 __device__ __forceinline__ void
@@ -706,7 +711,21 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
             GSR_STAT(6, 1);
             // wave-private LDS slab + broadcast reads (see K8): the relevant entries, compacted in WALK order (back to
             // front: rank = relevant lanes above), as pair records -- slot 0 of a pair is walked first
+#ifdef GSR_ABL_K10_MASKWALK  // ablation: slot positions and chunk indices from the ballot mask (see the walk below)
             if (e.relevant) pair_store(wslab, __popcll((m >> lane) >> 1), e, raw.r, raw.g, raw.b);
+#else
+            // The list position + 1 of every relevant entry goes into its record, and if their number is odd the slot behind
+            // the last one becomes an INERT record (all ten fields written: nothing stale is ever read): the walk below
+            // runs on a trip count of whole pairs and knows neither the ballot mask nor a "second entry?" predicate.
+            const int nrel = __popcll(m);
+            if (e.relevant) {
+                const int pos = __popcll((m >> lane) >> 1);
+                pair_store(wslab, pos, e, raw.r, raw.g, raw.b);
+                pair_store_last(wslab, pos, c + lane + 1);
+            }
+            if ((nrel & 1) && lane < 10)  // (slot nrel is the second of pair nrel >> 1; field 9 is its position word)
+                wslab[(nrel >> 1) * PREC + 2 * lane + 1] = lane == 5 ? GSR_PAD_O : lane == 9 ? __int_as_float(K10_NO_POS) : 0.f;
+#endif
             // the flush below reads positions / conics / ids by chunk index from the wave that walks the longest list
             // (it holds every entry of every chunk)
             if (wave == wbest) {
@@ -715,6 +734,7 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
                 fe[5] = __uint_as_float(id_cur);
                 fe[6] = raw.co.w;
             }
+#ifdef GSR_ABL_K10_MASKWALK
             // chunk index of the entry in each slot: 8 bytes in a scalar register pair (wave-uniform, SALU only)
             unsigned long long sk = 0ull;
             // phase B: [rows x pixels] . [pixels x columns] on the matrix pipe.  Result element r of a lane: row
@@ -796,6 +816,110 @@ composite_backward_segment(const int tile, const int sidx, int W, int H, int gx,
                 }
             }
             if (s > 0) contract_batch(s);
+#else
+            // phase B: [rows x pixels] . [pixels x columns] on the matrix pipe, batch `b` of the (wave, chunk): the slots
+            // 8 b ... 8 b + 7, of which `filled` (>= 8: all) hold entries.  Result element r of a lane: row 4 kq + r,
+            // column j.  Rows of unfilled slots hold whatever the matrix held before (an inert slot's: zeros): rows are
+            // independent, they are simply not added.  The row of the result table an entry's values go to is its
+            // chunk index: the position word of its record minus c + 1, read here by the lanes that store (two 8-byte
+            // reads: the lane's four slots are two pairs) -- no scalar register is spent on it during the walk.
+            auto contract_batch = [&](int b, int filled) {
+                __builtin_amdgcn_wave_barrier();  // the wave's own LDS stores above precede its loads below
+                const float *pw = wslab + (4 * b + 2 * (kq & 1)) * PREC + 18;
+                float2 w01 = *reinterpret_cast<const float2 *>(pw), w23 = *reinterpret_cast<const float2 *>(pw + PREC);
+                asm("" : "+v"(w01.x), "+v"(w01.y), "+v"(w23.x), "+v"(w23.y));  // (see pair_load_last: no branches around these reads)
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};  // two chains: back-to-back issue
+#pragma unroll
+                for (int t = 0; t < 16; t += 2) {
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[8 * t], Bop[t], acc, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[8 * t + 8], Bop[t + 1], acc1, 0, 0, 0);
+                }
+                acc += acc1;
+                const int row[4] = {__float_as_int(w01.x) - (c + 1), __float_as_int(w01.y) - (c + 1),
+                                    __float_as_int(w23.x) - (c + 1), __float_as_int(w23.y) - (c + 1)};
+#pragma unroll
+                for (int r4 = 0; r4 < 4; r4++) {
+                    const int slot = 4 * (kq & 1) + r4;
+                    // an entry is in exactly one batch of this wave: a plain store into the wave's own table
+                    if (slot < filled && my_cols) acc_tab[row[r4] * 9 + j] = acc[r4];
+                }
+                GSR_STAT(5, 1);
+                __builtin_amdgcn_wave_barrier();  // the next batch overwrites the matrix only after these reads
+            };
+            // Entries are taken two at a time: their LDS reads and alphas are independent (one wait for both), only
+            // the short T / rho chain is sequential.  MB is even, so a pair never straddles a batch.  Whether the pixel
+            // blended an entry (`position + 1 <= last`) is read from the record; an inert slot fails that test and the
+            // alpha test, takes nothing (q = w = 0, inv = 1: T and rho keep their values) and leaves a zero matrix row.
+            // (pair `rp` of the records at `recs`, which is pair `pi` of the chunk -- only GSR_STATS wants to know;
+            // mrow: the (q, w) row of its first slot, the second one is the next row)
+            auto walk_pair = [&](const float *recs, int rp, int pi, float2 *mrow) {
+                int la, lb;
+                const PairRec pr = pair_load_last(recs, rp, la, lb);  // wave-uniform address: LDS broadcasts
+                const v2f pe = pair_exponent(pr, pxf, pyf);
+                const float aar = __builtin_amdgcn_exp2f(pe.x), bar = __builtin_amdgcn_exp2f(pe.y);  // o exp(power), unclamped
+                const float aal = fminf(0.99f, aar), bal = fminf(0.99f, bar);
+                const bool atake = la <= last && pe.x <= pr.o.x && aal >= ALPHA_MIN;  // power <= 0 <=> exponent <= log2 o
+                const bool btake = lb <= last && pe.y <= pr.o.y && bal >= ALPHA_MIN;
+                const v2f cg = __builtin_elementwise_fma(pr.b, v2f{g2, g2}, __builtin_elementwise_fma(pr.g, v2f{g1, g1}, pr.r * g0));
+                GSR_STAT(2, min(2, nrel - 2 * pi));
+                GSR_STAT(3, (__builtin_amdgcn_ballot_w64(atake) != 0ull) + (__builtin_amdgcn_ballot_w64(btake) != 0ull));
+                GSR_STAT(4, __popcll(__builtin_amdgcn_ballot_w64(atake)) + __popcll(__builtin_amdgcn_ballot_w64(btake)));
+                // No "does any lane take it?" branch: the quadrant test above is exact, 97.5-99.7 % of the evaluated
+                // entries are taken by at least one pixel (profiles/r02_kstats_bwd.txt), and the wave-wide test costs
+                // two VALU instructions per entry.  A lane that does not take an entry runs the same arithmetic with
+                // alpha = 0: T / (1 - 0) and rho + 0 * (...) leave its state untouched and it stores (0, 0) (the
+                // factors are SELECTED, never multiplied by an inf / NaN).
+                const v2f qa = {atake ? aar : 0.f, atake ? aal : 0.f};   // (o G, alpha) of the first entry, or (0, 0)
+                const v2f qb = {btake ? bar : 0.f, btake ? bal : 0.f};
+                const v2f inv = {__builtin_amdgcn_rcpf(1.f - qa.y), __builtin_amdgcn_rcpf(1.f - qb.y)};  // 1 ulp, inside the 1e-4 budget
+                const v2f tbi = inv * tb;
+                {
+                    const float Tn = T * inv.x;                     // transmittance in front of the entry
+                    const float dot = cg.x - rho;                   // (c - R) . g
+                    const float da = fmaf(dot, Tn, -tbi.x);         // dL/dalpha
+                    const v2f qw = qa * v2f{da, Tn};                // (q = o G dL/dalpha, w = alpha T)
+                    mrow[0] = make_float2(qw.x, qw.y);
+                    rho = fmaf(qa.y, dot, rho);
+                    T = Tn;
+                }
+                {
+                    const float Tn = T * inv.y;
+                    const float dot = cg.y - rho;
+                    const float da = fmaf(dot, Tn, -tbi.y);
+                    const v2f qw = qb * v2f{da, Tn};
+                    mrow[MSTR] = make_float2(qw.x, qw.y);
+                    rho = fmaf(qb.y, dot, rho);
+                    T = Tn;
+                }
+            };
+#ifdef GSR_ABL_K10_SLOTCOUNT  // ablation: one flat loop, the matrix row and the batch test from a count of filled slots
+            int s = 0;
+            for (int pi = 0; pi < (nrel + 1) >> 1; pi++) {
+                walk_pair(wslab, pi, pi, &smat[wave][s * MSTR + lane]);
+                s += 2;
+                if (s == MB) {
+                    contract_batch(pi >> 2, nrel - 8 * (pi >> 2));
+                    s = 0;
+                }
+            }
+            if (s > 0) contract_batch(nrel >> 3, nrel & 7);
+#else
+            // batch by batch: up to four pairs, then their contraction; no slot counter is kept or tested per pair
+            for (int b = 0; 8 * b < nrel; b++) {
+                const int filled = nrel - 8 * b;  // (>= 8: all)
+                const int np = min(MB / 2, (filled + 1) >> 1);
+                // (unrolled with an early exit: record and row offsets are constants of the instructions)
+                float2 *const mrow = &smat[wave][lane];
+                const float *const brec = wslab + 4 * b * PREC;
+#pragma unroll
+                for (int k = 0; k < MB / 2; k++) {
+                    if (k >= np) break;
+                    walk_pair(brec, k, 4 * b + k, mrow + 2 * k * MSTR);
+                }
+                contract_batch(b, filled);
+            }
+#endif
+#endif
         }
         __syncthreads();
         // Flush.  The four quadrant waves' raw pixel moments (about the TILE origin) add up; then
