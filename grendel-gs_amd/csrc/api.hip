@@ -180,4 +180,28 @@ int gsr_render_backward(int P, int width, int height, const int32_t *ranges, con
                                          reinterpret_cast<hipStream_t>(stream));
 }
 
+int gsr_render_contrib(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                       const float *means2D, const float *conic_opacity, const uint8_t *compute_locally,
+                       const int32_t *n_contrib, int row_lo, int row_hi, int64_t *hits, float *wmax, double *wsum,
+                       gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    // (point_list may be NULL: every list can be empty)
+    if (!ranges || !means2D || !conic_opacity || !compute_locally || !n_contrib || !hits || !wmax || !wsum)
+        return GSR_EINVAL;
+    return gsr_launch_composite_contrib(P, width, height, ranges, point_list, means2D, conic_opacity, compute_locally,
+                                        n_contrib, row_lo, row_hi, hits, wmax, wsum,
+                                        reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_contrib_merge_rows(int64_t n, const int32_t *idx, const int64_t *src_hits, const float *src_wmax,
+                           const double *src_wsum, int64_t *dst_hits, float *dst_wmax, double *dst_wsum,
+                           gsr_stream_t stream) {
+    if (n < 0) return GSR_EINVAL;
+    if (n == 0) return 0;
+    if (!idx || !src_hits || !src_wmax || !src_wsum || !dst_hits || !dst_wmax || !dst_wsum) return GSR_EINVAL;
+    return gsr_launch_contrib_merge_rows(n, idx, src_hits, src_wmax, src_wsum, dst_hits, dst_wmax, dst_wsum,
+                                         reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

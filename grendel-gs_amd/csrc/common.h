@@ -160,3 +160,10 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
                                   const int32_t *n_contrib, const float *dL_dpixels, float *dL_record,
                                   const float *out_color, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
                                   int record_is_zero, double *acc64, uint8_t *touched, hipStream_t stream);
+int gsr_launch_composite_contrib(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
+                                 const float *means2D, const float *conic_opacity, const uint8_t *compute_locally,
+                                 const int32_t *n_contrib, int row_lo, int row_hi, int64_t *hits, float *wmax,
+                                 double *wsum, hipStream_t stream);
+int gsr_launch_contrib_merge_rows(int64_t n, const int32_t *idx, const int64_t *src_hits, const float *src_wmax,
+                                  const double *src_wsum, int64_t *dst_hits, float *dst_wmax, double *dst_wsum,
+                                  hipStream_t stream);

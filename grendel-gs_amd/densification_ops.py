@@ -471,9 +471,27 @@ def reset_opacity(self):
     self._opacity = replace_tensor_to_optimizer(self, new, "opacity")["opacity"]
 
 
+def prune_by_contribution(self, scores, min_wmax=None, min_hits=1):
+    """Prune the rows no training view made use of (no counterpart in the reference): `scores` is the
+    diff_gaussian_rasterization.ContributionStats that gaussian_renderer.score_contributions accumulated over the views,
+    one row per local Gaussian.  A row goes when fewer than `min_hits` pixels blended it or, with `min_wmax`, when its
+    largest blend weight on any pixel stayed below that (RadSplat's rule).  The thresholds are absolute, so the ranks
+    need no agreement.  -> the number of rows pruned"""
+    if not isinstance(scores, dgr.ContributionStats) or scores.P != self._xyz.shape[0]:
+        raise ValueError("prune_by_contribution: `scores` must be a ContributionStats with one row per local Gaussian")
+    mask = scores.hits < int(min_hits)
+    if min_wmax is not None:
+        mask = torch.logical_or(mask, scores.wmax < float(min_wmax))
+    n = int(mask.sum())
+    _log("Number of gaussians pruned by contribution: {}\n".format(n))
+    if n:
+        prune_points(self, mask)
+    return n
+
+
 def install(cls):
     """graft level B3: make these functions the methods of the reference's GaussianModel class"""
-    for fn in (prune_points, cat_tensors_to_optimizer, densification_postfix, densify_and_clone, densify_and_split,
+    for fn in (prune_points, prune_by_contribution, cat_tensors_to_optimizer, densification_postfix, densify_and_clone, densify_and_split,
                densify_and_prune, densify_and_prune_fused, need_redistribute_gaussians, redistribute_gaussians,
                add_densification_stats, update_densification_stats,
                replace_tensor_to_optimizer, reset_opacity):

@@ -1189,6 +1189,17 @@ class _RenderGaussians(torch.autograd.Function):
         if _CAPTURE[0] is not None:
             timing = "off"  # events recorded inside a capture cannot be read
         stats = cuda_args.get("stats_collector") if isinstance(cuda_args, dict) else None
+        # opt-in: a ContributionStats the view's per-Gaussian statistics are accumulated into, by a kernel of its own
+        # behind K8 (contribution_stats).  The pair count is then NOT deferred: the lists K8 drew from are final before
+        # the statistics walk them, and K8 is never redrawn underneath them
+        contrib = cuda_args.get("contributions") if isinstance(cuda_args, dict) else None
+        if contrib is not None:
+            if _CAPTURE[0] is not None:
+                raise RuntimeError("diff_gaussian_rasterization: cuda_args['contributions'] is not available under graph "
+                                   "capture (the statistics need the view's final lists)")
+            if not isinstance(contrib, ContributionStats) or contrib.P != P or \
+                    contrib.hits.get_device() != means2D.get_device():
+                raise ValueError(f"cuda_args['contributions'] must be a ContributionStats of {P} rows on {dev}")
         with _on(dev):
             if timing != "off":
                 ev0 = torch.cuda.Event(enable_timing=True)
@@ -1200,7 +1211,7 @@ class _RenderGaussians(torch.autograd.Function):
                 # (round 6) the pair count is looked at AFTER K8 has been launched -- by the caller, after ALL its cameras
                 # have been launched, when it hands a list through cuda_args["_gsr_pending"] (gaussian_renderer.render_final)
                 point_list, ranges, D = bin_gaussians(means2D, depths, radii, conic_opacity, mask, W, H, cuda_args,
-                                                      defer=True)
+                                                      defer=contrib is None)
             pend = D if isinstance(D, PendingPairs) else None
             kt.meta["D"] = D = (0 if pend is not None else D)
             if kernel_timer.enabled:
@@ -1261,6 +1272,9 @@ class _RenderGaussians(torch.autograd.Function):
                 return k8t
 
             k8t = launch_k8(D)
+            if contrib is not None:  # the same lists, mask and band, behind K8 on the same stream
+                contribution_stats(ranges, lists[0], means2D, conic_opacity, n_contrib, mask, W, H, contrib,
+                                   band=(row_lo, row_hi))
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("fwd1", id(stats))
             ctx.seg = (seg_ws, seg_bytes, row_lo, row_hi)
@@ -1885,6 +1899,99 @@ def scatter_add_rows(idx, src, n_rows, dst=None):
     with _on(src.device):
         check(lib.gsr_scatter_add_rows(src.shape[0], _ptr(idx), _ptr(src), _ptr(dst), _stream()), "gsr_scatter_add_rows")
     return dst
+
+
+class ContributionStats:
+    """Per-Gaussian contribution statistics of rendered views (include/gsraster.h: gsr_render_contrib), accumulated over
+    every view that is rendered into them: hits int64 [P] (pixels that blended the row), wmax fp32 [P] (the largest blend
+    weight alpha T on any pixel), wsum fp64 [P] (the sum of the weights).  A row nobody blended stays all zero."""
+
+    def __init__(self, P, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("diff_gaussian_rasterization: ContributionStats must live on the gfx950 device "
+                               "(no CPU fallback)")
+        self.P = int(P)
+        self.hits = torch.zeros((self.P,), dtype=torch.int64, device=device)
+        self.wmax = torch.zeros((self.P,), dtype=torch.float32, device=device)
+        self.wsum = torch.zeros((self.P,), dtype=torch.float64, device=device)
+
+    @classmethod
+    def of(cls, hits, wmax, wsum):
+        """a record around existing dense device tensors (int64 / float32 / float64, one length), e.g. rows that came
+        back from another rank"""
+        if not (hits.is_cuda and wmax.is_cuda and wsum.is_cuda):
+            raise RuntimeError("diff_gaussian_rasterization: ContributionStats must live on the gfx950 device "
+                               "(no CPU fallback)")
+        if (hits.dtype, wmax.dtype, wsum.dtype) != (torch.int64, torch.float32, torch.float64) or \
+                not (hits.shape == wmax.shape == wsum.shape and hits.dim() == 1) or \
+                not (hits.is_contiguous() and wmax.is_contiguous() and wsum.is_contiguous()):
+            raise ValueError("ContributionStats.of: dense int64 hits, float32 wmax and float64 wsum of one length expected")
+        self = cls.__new__(cls)
+        self.P, self.hits, self.wmax, self.wsum = hits.shape[0], hits, wmax, wsum
+        return self
+
+    def zero_(self):
+        self.hits.zero_()
+        self.wmax.zero_()
+        self.wsum.zero_()
+        return self
+
+    def merge_rows(self, idx, other):
+        """self[idx[r]]: hits += other.hits[r], wmax = max(., other.wmax[r]), wsum += other.wsum[r]; rows with
+        idx[r] < 0 are skipped, duplicate indices accumulate (gsr_contrib_merge_rows).  idx: int32 [other.P]"""
+        if not isinstance(other, ContributionStats):
+            raise TypeError("merge_rows: a ContributionStats expected")
+        if not idx.is_cuda:
+            raise RuntimeError("diff_gaussian_rasterization: `idx` must live on the gfx950 device (no CPU fallback)")
+        if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != other.P:
+            raise ValueError("merge_rows: idx must be contiguous int32 with one entry per row of `other`")
+        with _on(self.hits.device):
+            check(lib.gsr_contrib_merge_rows(other.P, _ptr(idx), _ptr(other.hits), _ptr(other.wmax), _ptr(other.wsum),
+                                             _ptr(self.hits), _ptr(self.wmax), _ptr(self.wsum), _stream()),
+                  "gsr_contrib_merge_rows")
+        return self
+
+    def importance(self, kind="max"):
+        """the per-row score a pruning rule thresholds: "max" (RadSplat), "sum" (LightGaussian), "hits" -> float32 [P]"""
+        if kind == "max":
+            return self.wmax
+        if kind == "sum":
+            return self.wsum.to(torch.float32)
+        if kind == "hits":
+            return self.hits.to(torch.float32)
+        raise ValueError(f"importance: kind must be 'max', 'sum' or 'hits', not {kind!r}")
+
+
+def contribution_stats(ranges, point_list, means2D, conic_opacity, n_contrib, compute_locally, width, height, out,
+                       band=None):
+    """accumulate one rendered view's statistics into `out` (a ContributionStats of means2D.shape[0] rows): a forward-only
+    walk over the lists K8 drew from, with K8's n_contrib -- blended pairs are exactly those of the image.  ranges int32
+    [tiles, 2] (the mask's row hull in the row behind it) and point_list as bin_gaussians returns them, compute_locally
+    uint8 / bool [tiles],
+    band = (row_lo, row_hi) as gsr_render_forward takes it (None: the whole grid)"""
+    means2D, conic_opacity = _f32c(means2D, "means2D"), _f32c(conic_opacity, "conic_opacity")
+    P = means2D.shape[0]
+    if not isinstance(out, ContributionStats) or out.P != P:
+        raise ValueError(f"contribution_stats: `out` must be a ContributionStats of {P} rows")
+    for t, n in ((ranges, "ranges"), (point_list, "point_list"), (n_contrib, "n_contrib"),
+                 (compute_locally, "compute_locally")):
+        if not t.is_cuda:
+            raise RuntimeError(f"diff_gaussian_rasterization: `{n}` must live on the gfx950 device (no CPU fallback)")
+    gx, gy = (int(width) + BLOCK_X - 1) // BLOCK_X, (int(height) + BLOCK_Y - 1) // BLOCK_Y
+    mask = compute_locally.contiguous().view(-1)
+    mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
+    if ranges.dtype != torch.int32 or not ranges.is_contiguous() or ranges.numel() < 2 * gx * gy or \
+            point_list.dtype != torch.int32 or not point_list.is_contiguous() or mask.numel() != gx * gy or \
+            n_contrib.dtype != torch.int32 or not n_contrib.is_contiguous() or n_contrib.numel() != width * height:
+        raise ValueError("contribution_stats: int32 ranges [tiles, 2], point_list and n_contrib [H, W], and a mask of "
+                         "one entry per tile expected")
+    row_lo, row_hi = (int(band[0]), int(band[1])) if band else (0, 0)
+    with _on(means2D.device):
+        check(lib.gsr_render_contrib(P, int(width), int(height), _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                                     _ptr(conic_opacity), _ptr(mask), _ptr(n_contrib), row_lo, row_hi, _ptr(out.hits),
+                                     _ptr(out.wmax), _ptr(out.wsum), _stream()), "gsr_render_contrib")
+    return out
 
 
 def densify_stats(radii, grad, max_radii2D, accum, denom):

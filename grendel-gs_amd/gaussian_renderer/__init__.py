@@ -367,6 +367,9 @@ def _planner(group, W, B):
     return p
 
 
+_LAST_ROUTE = [None]  # the latest exchange's (send_idx, send_splits, recv_splits, group), kept BEHIND its collective
+
+
 class _ExchangeGroup(torch.autograd.Function):
     """the exchange of the cameras [k0, k0 + nb) of a batch: pack (gsr_exchange_pack / gsr_exchange_pack_slab: 11-float
     records in (destination, camera, local index) order, straight into the send buffer), ONE all-to-all-v, unpack.  Runs
@@ -396,6 +399,7 @@ class _ExchangeGroup(torch.autograd.Function):
                                                count_first=0)
         recv = torch.empty((n_recv, N_DIFF + N_AUX), dtype=msg.dtype, device=dev)
         dist.all_to_all_single(recv, msg, output_split_sizes=recv_splits, input_split_sizes=send_splits, group=group)
+        _LAST_ROUTE[0] = (send_idx, send_splits, recv_splits, group)  # (score_contributions sends statistics back along it)
         if perm is None:  # one exchange per camera (always, with capacity slabs): the message is camera-major already
             outs = list(_dgr.exchange_unpack(recv))
         else:             # several cameras in one exact exchange: (source, camera)-major -> camera-major
@@ -980,6 +984,50 @@ def render_final(batched_screenspace_pkg, batched_strategies, tile_size=16, late
         images, masks, late = _render_cameras(pkg, batched_strategies)
         _settle(late)
     return images, masks
+
+
+def score_contributions(batched_cameras, gaussians, pipe_args, background, batched_strategies, scores):
+    """Per-Gaussian contribution statistics of the given views, accumulated into `scores` (a
+    diff_gaussian_rasterization.ContributionStats of this rank's P_local rows) -- the reference has no counterpart.
+    Forward only (no_grad), one camera at a time: projection + exchange in the EXACT layout on the current stream (what
+    the legacy wrapper takes), render_final with a per-render ContributionStats, and the rows go back to their owners:
+      * world size 1: the render's rows are the owner's rows, the render accumulates into `scores` itself;
+      * world size > 1: the mirror of _ExchangeGroup.backward without autograd -- every rank sends the statistics of
+        the rows it received back with ONE all-to-all-v per camera (the exchange's split sizes, swapped; 16 bytes per
+        row: hits as int32 -- a view has fewer pixels than that --, wmax, wsum) and the owner merges them through the
+        exchange's send_idx (gsr_contrib_merge_rows: a Gaussian needed by two bands arrives twice).
+    EVERY rank takes part in every camera's return trip, also one that renders no part of the camera or took the
+    < 10-Gaussian stand-in: it sends zeros.  -> scores"""
+    if not isinstance(scores, _dgr.ContributionStats) or scores.P != gaussians._xyz.shape[0]:
+        raise ValueError("score_contributions: `scores` must be a ContributionStats of the model's local row count")
+    exchanged = not (utils.DEFAULT_GROUP.size() == 1 and not (_EXCHANGE_OPTIONS["forced"] and dist.is_initialized()))
+    with torch.no_grad():
+        for camera, strategy in zip(batched_cameras, batched_strategies):
+            _LAST_ROUTE[0] = None
+            pkg = distributed_preprocess3dgs_and_all2all_final([camera], gaussians, pipe_args, background,
+                                                               batched_strategies=[strategy], mode="test", _legacy=True)
+            n_rows = pkg["batched_means2D_redistributed"][0].shape[0]
+            stats = None
+            if utils.GLOBAL_RANK in strategy.gpu_ids and n_rows >= 10:  # (render_final's stand-in rule: nothing is drawn)
+                stats = _dgr.ContributionStats(n_rows, scores.hits.device) if exchanged else scores
+                pkg["batched_cuda_args"][0]["contributions"] = stats
+                render_final(pkg, [strategy])
+            if not exchanged:
+                continue
+            send_idx, send_splits, recv_splits, group = _LAST_ROUTE[0]
+            n_recv, n_send = sum(recv_splits), sum(send_splits)
+            dev = send_idx.device
+            msg = torch.zeros((n_recv, 4), dtype=torch.int32, device=dev)  # [hits | wmax bits | wsum bits (2 words)]
+            if stats is not None:
+                msg[:, 0] = stats.hits
+                msg[:, 1] = stats.wmax.view(torch.int32)
+                msg[:, 2:4] = stats.wsum.view(torch.int32).view(n_recv, 2)
+            back = torch.empty((n_send, 4), dtype=torch.int32, device=dev)
+            dist.all_to_all_single(back, msg, output_split_sizes=send_splits, input_split_sizes=recv_splits, group=group)
+            scores.merge_rows(send_idx, _dgr.ContributionStats.of(
+                back[:, 0].to(torch.int64), back[:, 1].contiguous().view(torch.float32),
+                back[:, 2:4].contiguous().view(torch.float64).view(n_send)))
+    return scores
 
 
 def _no_gsplat(*a, **k):

@@ -367,6 +367,36 @@ int gsr_render_backward(int P, int width, int height, const int32_t *ranges, con
  * Synchronous (a device-to-host copy of two words); reset != 0 zeroes the counters afterwards. */
 int gsr_composite_walked(unsigned long long *out2, int reset);
 
+/* Per-Gaussian CONTRIBUTION statistics of a rendered view (the reference has no counterpart: its only per-Gaussian
+ * signals are radii > 0, the screen-space gradient norm and the opacity, none of which says whether a Gaussian was ever
+ * blended into a pixel).  A forward-only walk over the lists gsr_render_forward drew from, with that call's n_contrib:
+ * the entry at list position k (0-based) of a local tile is BLENDED on a pixel iff k + 1 <= n_contrib[pixel],
+ * power <= 0 and alpha = min(0.99, o exp(power)) >= 1/255 -- gsr_render_backward's rule, in the composite kernels' own
+ * arithmetic, so the statistics describe exactly the image that was drawn; the stop is the forward's, nothing is
+ * re-decided.  Per pixel T starts at 1; a blended pair has the weight w = alpha T, then T <- T (1 - alpha).  Takes no
+ * rgb, bg or final_T.  ranges, point_list, means2D, conic_opacity, compute_locally, row_lo / row_hi: as
+ * gsr_render_forward (whole grid, host band, -1 = device hull behind the range table).
+ * The three arrays are the CALLER's, zeroed by the caller, and are ACCUMULATED into, never overwritten -- several views
+ * (or bands) add up in one record:
+ *   hits int64 [P] += the number of pixels that blended the row;
+ *   wmax fp32  [P]  = max(old, largest w over those pixels) -- an unsigned 32-bit atomic max on the bits (values are
+ *                     non-negative), exact and independent of the order;
+ *   wsum fp64  [P] += the sum of w over those pixels: per 8x8 quadrant in fp32 in a fixed order, then one fp64 atomic add
+ *                     (at most 4 x local tiles additions per row and launch).
+ * Rows that are blended nowhere in the launch receive no write.  P < 0, a non-positive frame, or a missing pointer with
+ * P > 0: GSR_EINVAL before any device work; P == 0 returns 0 and touches nothing.
+ * gsr_contrib_merge_rows: dst[idx[r]] gets hits += src_hits[r], wmax = max(., src_wmax[r]), wsum += src_wsum[r] for the
+ * n rows of a record that came back from another rank -- the counterpart of gsr_scatter_add_rows for this record: rows
+ * with idx[r] < 0 are skipped, duplicate indices are allowed (a Gaussian needed by two bands arrives twice; atomics).
+ * n < 0 or a missing pointer with n > 0: GSR_EINVAL; n == 0 returns 0 and touches nothing. */
+int gsr_render_contrib(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                       const float *means2D, const float *conic_opacity, const uint8_t *compute_locally,
+                       const int32_t *n_contrib, int row_lo, int row_hi, int64_t *hits, float *wmax, double *wsum,
+                       gsr_stream_t stream);
+int gsr_contrib_merge_rows(int64_t n, const int32_t *idx, const int64_t *src_hits, const float *src_wmax,
+                           const double *src_wsum, int64_t *dst_hits, float *dst_wmax, double *dst_wsum,
+                           gsr_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * N1  fused band-local L1 + SSIM loss -- the arithmetic of final_system_loss_computation,
  * gaussian_renderer/loss_distribution.py:2536-2585 (pixelwise_l1_with_mask / pixelwise_ssim_with_mask,
