@@ -218,11 +218,10 @@ touch_count_kernel(int P, int gx, int gy, const float2 *__restrict__ means2D, co
                 if (gsr_alpha_extent(co, ex, ey)) {
                     int minx, miny, maxx, maxy;
                     gsr_get_rect(xy.x, xy.y, rad, gx, gy, minx, miny, maxx, maxy);
-                    // tile t covers pixel centres [16t, 16t+15]
-                    minx = max(minx, (int)ceilf((xy.x - ex - (GSR_BLOCK_X - 1)) * (1.0f / GSR_BLOCK_X)));
-                    maxx = min(maxx, (int)floorf((xy.x + ex) * (1.0f / GSR_BLOCK_X)) + 1);
-                    miny = max(max(miny, hull0), (int)ceilf((xy.y - ey - (GSR_BLOCK_Y - 1)) * (1.0f / GSR_BLOCK_Y)));
-                    maxy = min(min(maxy, hull1), (int)floorf((xy.y + ey) * (1.0f / GSR_BLOCK_Y)) + 1);
+                    miny = max(miny, hull0);
+                    maxy = min(maxy, hull1);
+                    gsr_narrow_span(xy.x, ex, minx, maxx);
+                    gsr_narrow_span(xy.y, ey, miny, maxy);
                     // (the tile count, the exact tile mask when culling is on, the tile sort's digit histograms)
                     if (maxx > minx && maxy > miny)
                         n = gsr_rect_tiles(xy, co, minx, miny, maxx, maxy, cull != 0, tile_hist ? dxy : nullptr, rect);
@@ -737,6 +736,9 @@ int bin_sort_impl(int P, int width, int height, const uint8_t *compute_locally, 
     const BinFrame f = bin_frame(width, height);
     if (D == 0 || P == 0 || !f.yx)  // (the (row, column) forms clear the table inside their first kernel)
         GSR_HIP(hipMemsetAsync(ranges, 0, sizeof(int32_t) * 2 * ((size_t)f.gx * f.gy + 1), stream));  // + the hull row: (0, 0)
+    if (D == 0 && P > 0 && prep)  // a view without pairs still has its band: K3 left the hull, as the bounded sort copies it
+        GSR_HIP(hipMemcpyAsync(ranges + 2 * (size_t)f.gx * f.gy, views(prep_layout(P), const_cast<void *>(prep)).hull,
+                               2 * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
     if (D == 0 || P == 0) return 0;
     if (!compute_locally || !prep || !scratch || !point_list) return GSR_EINVAL;
     const BinHooks h = read_hooks();

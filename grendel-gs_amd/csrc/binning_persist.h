@@ -311,8 +311,12 @@ __device__ __forceinline__ unsigned long long gsr_tile_mask(const float2 xy, con
             dxR += 0.02f + 1e-4f * fabsf(dxR);
             dxL -= 0.02f + 1e-4f * fabsf(dxL);
             // tile x covers pixel centres [16 x, 16 x + 15]: kept when that interval meets [cx + dxL, cx + dxR]
-            xa = max(0, (int)ceilf((xy.x + dxL - (float)(GSR_BLOCK_X - 1)) * (1.0f / GSR_BLOCK_X)) - minx);
-            xb = min(w, (int)floorf((xy.x + dxR) * (1.0f / GSR_BLOCK_X)) + 1 - minx);
+            // (gsr_clamp_span clamps as floats: a span of billions of pixels cannot wrap the integers)
+            xa = minx;
+            xb = maxx;
+            gsr_clamp_span(xy.x + dxL, xy.x + dxR, xa, xb);
+            xa -= minx;
+            xb -= minx;
             if (xb <= xa) continue;
         }
         mask |= gsr_full_mask(xb - xa) << (r * w + xa);
@@ -852,10 +856,10 @@ bin_prepare_persist_kernel(const PrepPersistArgs a) {
                     if (gsr_alpha_extent(co[q4], exx, eyy)) {
                         int minx, miny, maxx, maxy;
                         gsr_get_rect(xy[q4].x, xy[q4].y, rad[q4], a.gx, a.gy, minx, miny, maxx, maxy);
-                        minx = max(minx, (int)ceilf((xy[q4].x - exx - (GSR_BLOCK_X - 1)) * (1.0f / GSR_BLOCK_X)));
-                        maxx = min(maxx, (int)floorf((xy[q4].x + exx) * (1.0f / GSR_BLOCK_X)) + 1);
-                        miny = max(max(miny, hull0), (int)ceilf((xy[q4].y - eyy - (GSR_BLOCK_Y - 1)) * (1.0f / GSR_BLOCK_Y)));
-                        maxy = min(min(maxy, hull1), (int)floorf((xy[q4].y + eyy) * (1.0f / GSR_BLOCK_Y)) + 1);
+                        miny = max(miny, hull0);
+                        maxy = min(maxy, hull1);
+                        gsr_narrow_span(xy[q4].x, exx, minx, maxx);
+                        gsr_narrow_span(xy[q4].y, eyy, miny, maxy);
                         if (maxx > minx && maxy > miny)
                             n = gsr_rect_tiles(xy[q4], co[q4], minx, miny, maxx, maxy, a.cull != 0,
                                                a.tile_hist ? ex.dxy : nullptr, rect);

@@ -55,7 +55,11 @@ __device__ __forceinline__ int gsr_xcd_span_of_block_band(int b, int nwg, int fi
 }
 
 // tile rect [min,max) of (pixel centre, radius): C truncation, clamped to the grid
-// (restates SURVEY.md A.2 step 7; identical in preprocess, K2 and K3 so that the three agree).
+// (restates SURVEY.md A.2 step 7; identical in preprocess, K2 and K3 so that the three agree).  The upper edge is
+// (p + r) + 15, two roundings.  oracle/gsraster_ref.c spells it p + r + BLOCK_X - 1, i.e. ((p + r) + 16) - 1 with three:
+// an ulp apart when the sums cross a power of two, which is a whole tile when the edge lies on a multiple of 16
+// (tests/binning_refs.py, family `borders`, pins where the two part).  Kept as it is: changing it changes lists of
+// proper inputs.
 __device__ __forceinline__ void gsr_get_rect(float px, float py, int radius, int gx, int gy, int &minx, int &miny,
                                              int &maxx, int &maxy) {
     const float r = (float)radius;
@@ -83,6 +87,26 @@ __device__ __forceinline__ bool gsr_alpha_extent(const float4 co, float &ex, flo
         ey = sqrtf(s * co.x) * 1.01f + 0.5f;
     }
     return true;
+}
+
+// Intersect the tile span [lo, hi) (0 <= lo, hi <= grid size) with the tiles whose pixel centres [16 t, 16 t + 15] meet
+// the pixel interval [left, right].  The bounds are clamped to [lo, hi] as FLOATS before the conversion:
+// v_cvt_i32_f32 saturates, and the INT_MAX + 1 of `(int)floorf(..) + 1` wrapped to INT_MIN, which emptied the span of a
+// Gaussian whose extent is huge.  Same spans as the integer min / max wherever those did not wrap; an empty span comes
+// out as hi <= lo.  A NaN bound narrows nothing.
+__device__ __forceinline__ void gsr_clamp_span(float left, float right, int &lo, int &hi) {
+    if (left != left || right != right) return;
+    const float flo = (float)lo, fhi = (float)hi;
+    const float a = ceilf((left - (float)(GSR_BLOCK_X - 1)) * (1.0f / GSR_BLOCK_X));
+    const float b = floorf(right * (1.0f / GSR_BLOCK_X)) + 1.0f;
+    lo = (int)fminf(fmaxf(a, flo), fhi);
+    hi = (int)fminf(fmaxf(b, flo), fhi);
+}
+static_assert(GSR_BLOCK_X == GSR_BLOCK_Y, "gsr_clamp_span serves both axes");
+// One axis of K3's narrowing: the span against [c - e, c + e], e = a half extent of gsr_alpha_extent.  An unbounded
+// (1e30) or non-finite extent narrows nothing: the 3-sigma span stands.
+__device__ __forceinline__ void gsr_narrow_span(float c, float e, int &lo, int &hi) {
+    if (e < 1e30f) gsr_clamp_span(c - e, c + e, lo, hi);
 }
 
 // Exact (up to a conservative tolerance) test "can this Gaussian reach alpha >= 1/255 on some pixel

@@ -142,7 +142,8 @@ int gsr_get_local2j_ids_bool(int P, int width, int height, int world_size, const
  *   point_list uint32 [D] (Gaussian index per pair, grouped by tile, front-to-back inside a
  *   tile, ties by Gaussian index) and ranges int32 [tiles + 1, 2]: rows 0 .. tiles-1 = [start,end) per tile, row `tiles`
  *   = [lo, hi) the tile ROWS that contain locally computed tiles (the band this rank renders; (0,0) when there is
- *   none) -- gsr_render_forward / _backward read it to spread the band, not the whole grid, over the eight XCDs.
+ *   none or P is 0; also written when D is 0) -- gsr_render_forward / _backward read it to spread the band, not the
+ *   whole grid, over the eight XCDs.
  *   The caller allocates tiles + 1 rows (ABI 7).
  *   `scratch` is a device workspace of gsr_bin_sort_bytes(P, D, width, height) bytes. */
 size_t gsr_bin_prepare_bytes(int P, int width, int height);
