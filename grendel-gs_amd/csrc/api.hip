@@ -204,4 +204,41 @@ int gsr_contrib_merge_rows(int64_t n, const int32_t *idx, const int64_t *src_hit
                                          reinterpret_cast<hipStream_t>(stream));
 }
 
+int gsr_render_invdepth(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                        const float *means2D, const float *conic_opacity, const float *depths,
+                        const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi,
+                        float *invdepth, gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0 || !invdepth) return GSR_EINVAL;
+    // (point_list may be NULL: every list can be empty)
+    if (P > 0 && (!ranges || !means2D || !conic_opacity || !depths || !compute_locally || !n_contrib)) return GSR_EINVAL;
+    return gsr_launch_composite_invdepth(P, width, height, ranges, point_list, means2D, conic_opacity, depths,
+                                         compute_locally, n_contrib, row_lo, row_hi, invdepth,
+                                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_render_invdepth_backward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                                 const float *means2D, const float *conic_opacity, const float *depths,
+                                 const uint8_t *compute_locally, const int32_t *n_contrib, const float *final_T,
+                                 const float *invdepth, const float *dL_dinvdepth, int row_lo, int row_hi,
+                                 float *dL_record, double *acc64, gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!ranges || !means2D || !conic_opacity || !depths || !compute_locally || !n_contrib || !final_T || !invdepth ||
+        !dL_dinvdepth || !dL_record || !acc64)
+        return GSR_EINVAL;
+    // (the walk goes back to front from final_T, as K10's does: the forward's map is part of the interface, not read)
+    return gsr_launch_composite_invdepth_backward(P, width, height, ranges, point_list, means2D, conic_opacity, depths,
+                                                  compute_locally, n_contrib, final_T, dL_dinvdepth, row_lo, row_hi,
+                                                  dL_record, acc64, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_depth_backward_means3d(int P, const int32_t *radii, const float *viewmatrix, const float *dL_ddepth,
+                               int row_stride, float *dL_dmeans3D, int overwrite, gsr_stream_t stream) {
+    if (P < 0 || row_stride < 1) return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!radii || !viewmatrix || !dL_ddepth || !dL_dmeans3D) return GSR_EINVAL;
+    return gsr_launch_depth_to_means3D(P, radii, viewmatrix, dL_ddepth, row_stride, dL_dmeans3D, overwrite ? 1 : 0,
+                                       reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

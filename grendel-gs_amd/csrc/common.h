@@ -191,3 +191,14 @@ int gsr_launch_composite_contrib(int P, int W, int H, const int32_t *ranges, con
 int gsr_launch_contrib_merge_rows(int64_t n, const int32_t *idx, const int64_t *src_hits, const float *src_wmax,
                                   const double *src_wsum, int64_t *dst_hits, float *dst_wmax, double *dst_wsum,
                                   hipStream_t stream);
+int gsr_launch_composite_invdepth(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
+                                  const float *means2D, const float *conic_opacity, const float *depths,
+                                  const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi,
+                                  float *invdepth, hipStream_t stream);
+int gsr_launch_composite_invdepth_backward(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
+                                           const float *means2D, const float *conic_opacity, const float *depths,
+                                           const uint8_t *compute_locally, const int32_t *n_contrib,
+                                           const float *final_T, const float *dL_dinvdepth, int row_lo, int row_hi,
+                                           float *dL_record, double *acc64, hipStream_t stream);
+int gsr_launch_depth_to_means3D(int P, const int32_t *radii, const float *viewmatrix, const float *dL_ddepth,
+                                int row_stride, float *dL_dmeans3D, int overwrite, hipStream_t stream);

@@ -1200,6 +1200,12 @@ class _RenderGaussians(torch.autograd.Function):
             if not isinstance(contrib, ContributionStats) or contrib.P != P or \
                     contrib.hits.get_device() != means2D.get_device():
                 raise ValueError(f"cuda_args['contributions'] must be a ContributionStats of {P} rows on {dev}")
+        # opt-in: the view's lists, mask, band, final_T and n_contrib are left in cuda_args for render_invdepth (the
+        # inverse-depth map, a kernel of its own behind K8).  The pair count is then NOT deferred either
+        invd = bool(cuda_args.get("invdepth")) if isinstance(cuda_args, dict) else False
+        if invd and _CAPTURE[0] is not None:
+            raise RuntimeError("diff_gaussian_rasterization: cuda_args['invdepth'] is not available under graph capture "
+                               "(the map needs the view's final lists)")
         with _on(dev):
             if timing != "off":
                 ev0 = torch.cuda.Event(enable_timing=True)
@@ -1211,7 +1217,7 @@ class _RenderGaussians(torch.autograd.Function):
                 # (round 6) the pair count is looked at AFTER K8 has been launched -- by the caller, after ALL its cameras
                 # have been launched, when it hands a list through cuda_args["_gsr_pending"] (gaussian_renderer.render_final)
                 point_list, ranges, D = bin_gaussians(means2D, depths, radii, conic_opacity, mask, W, H, cuda_args,
-                                                      defer=contrib is None)
+                                                      defer=contrib is None and not invd)
             pend = D if isinstance(D, PendingPairs) else None
             kt.meta["D"] = D = (0 if pend is not None else D)
             if kernel_timer.enabled:
@@ -1275,6 +1281,8 @@ class _RenderGaussians(torch.autograd.Function):
             if contrib is not None:  # the same lists, mask and band, behind K8 on the same stream
                 contribution_stats(ranges, lists[0], means2D, conic_opacity, n_contrib, mask, W, H, contrib,
                                    band=(row_lo, row_hi))
+            if invd:
+                cuda_args[_INVDEPTH_KEY] = (ranges, lists[0], mask, (row_lo, row_hi), final_T, n_contrib, W, H)
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("fwd1", id(stats))
             ctx.seg = (seg_ws, seg_bytes, row_lo, row_hi)
@@ -1387,6 +1395,86 @@ class _RenderGaussians(torch.autograd.Function):
         return d_means2D, d_conic_opacity, d_rgb, None, None, None, None, None, None
 
 
+_INVDEPTH_KEY = "_gsr_invdepth"  # what _RenderGaussians leaves in cuda_args when cuda_args["invdepth"] is set
+
+
+class _RenderInvDepth(torch.autograd.Function):
+    """the inverse-depth map of a view K8 has drawn (include/gsraster.h: gsr_render_invdepth), from the colour render's
+    own lists, mask, band, final_T and n_contrib; backward: the three column groups of the [P,7] record"""
+
+    @staticmethod
+    def forward(ctx, means2D, conic_opacity, depths, view):
+        if _CAPTURE[0] is not None:
+            raise RuntimeError("diff_gaussian_rasterization: the inverse-depth map is not available under graph capture "
+                               "(it needs the view's final lists)")
+        ranges, point_list, mask, band, final_T, n_contrib, W, H = view
+        means2D, conic_opacity = _f32c(means2D, "means2D"), _f32c(conic_opacity, "conic_opacity")
+        depths = _f32c(depths, "depths")
+        P = means2D.shape[0]
+        if conic_opacity.shape[0] != P or depths.numel() != P:
+            raise ValueError(f"render_invdepth: means2D, conic_opacity and depths must have the {P} rows of the view")
+        dev = means2D.device
+        out = torch.empty((H, W), dtype=torch.float32, device=dev)
+        with _on(dev), kernel_timer.range("composite_invdepth", P=P):
+            check(lib.gsr_render_invdepth(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D), _ptr(conic_opacity),
+                                          _ptr(depths), _ptr(mask), _ptr(n_contrib), band[0], band[1], _ptr(out),
+                                          _stream()), "gsr_render_invdepth")
+        ctx.view = view
+        ctx.save_for_backward(means2D, conic_opacity, depths, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        means2D, conic_opacity, depths, out = ctx.saved_tensors
+        ranges, point_list, mask, band, final_T, n_contrib, W, H = ctx.view
+        P = means2D.shape[0]
+        dev = means2D.device
+        g = g.float().contiguous()
+        record = torch.empty((P, 7), dtype=torch.float32, device=dev)
+        acc64 = torch.empty((P, 7), dtype=torch.float64, device=dev)
+        with _on(dev), kernel_timer.range("composite_invdepth_backward", P=P):
+            check(lib.gsr_render_invdepth_backward(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                                                   _ptr(conic_opacity), _ptr(depths), _ptr(mask), _ptr(n_contrib),
+                                                   _ptr(final_T), _ptr(out), _ptr(g), band[0], band[1], _ptr(record),
+                                                   _ptr(acc64), _stream()), "gsr_render_invdepth_backward")
+        return record[:, 0:2], record[:, 2:6], record[:, 6], None
+
+
+class _ViewDepths(torch.autograd.Function):
+    """K1's `depths` (the same values) with a grad_fn: depth = ([p,1] viewmatrix)[2], so dL/dmeans3D = dL/ddepth times
+    the third column of the view matrix (gsr_depth_backward_means3d).  The projection ops themselves keep `depths`
+    non-differentiable; this node is only built by a caller that supervises depth."""
+
+    @staticmethod
+    def forward(ctx, means3D, viewmatrix, depths, radii):
+        if ctx.needs_input_grad[0]:
+            sink = deferred_backward_sink()
+            if sink is not None and getattr(sink, "fuse_backward", False):
+                raise ValueError("the inverse-depth map's gradient needs an optimizer with fuse_backward=False: the "
+                                 "fused K11 + Adam step never writes the xyz gradient the depth path is added to")
+        if not (means3D.is_cuda and depths.is_cuda and radii.is_cuda):
+            raise RuntimeError("diff_gaussian_rasterization: tensors must live on the gfx950 device (no CPU fallback)")
+        ctx.save_for_backward(viewmatrix, radii)
+        ctx.P = means3D.shape[0]
+        return depths.view_as(depths)
+
+    @staticmethod
+    def backward(ctx, g):
+        viewmatrix, radii = ctx.saved_tensors
+        P = ctx.P
+        dev = g.device
+        if g.dtype != torch.float32 or g.dim() != 1 or (P > 1 and g.stride(0) < 1):
+            g = g.float().contiguous().view(-1)
+        stride = int(g.stride(0)) if P > 1 else 1
+        view = viewmatrix.detach().to(device=dev, dtype=torch.float32).contiguous()
+        radii = radii.to(torch.int32).contiguous()
+        out = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        with _on(dev):
+            check(lib.gsr_depth_backward_means3d(P, _ptr(radii), _ptr(view), _ptr(g), stride, _ptr(out), 1, _stream()),
+                  "gsr_depth_backward_means3d")
+        return out, None, None, None
+
+
 class GaussianRasterizer(nn.Module):
     """one instance per camera per iteration (gaussian_renderer/__init__.py:945)."""
 
@@ -1433,6 +1521,23 @@ class GaussianRasterizer(nn.Module):
         image, n_contrib = fn.apply(means2D, conic_opacity, rgb, depths, radii, compute_locally,
                                     self.raster_settings, cuda_args, token)
         return image, getattr(fn, "last_num_rendered", None), None, n_contrib
+
+    def render_invdepth(self, means2D, conic_opacity, depths, cuda_args, means3D=None, radii=None):
+        """-> the view's inverse-depth map [H,W] (extension of this build; include/gsraster.h: gsr_render_invdepth): per
+        pixel the sum of alpha T / depth over what render_gaussians blended, no background term, exactly 0 outside the
+        locally computed tiles.  Call it after render_gaussians of the SAME view and rows with cuda_args["invdepth"]
+        set: the colour render leaves its lists, mask, band, final_T and n_contrib in `cuda_args`.  Differentiable in
+        means2D and conic_opacity (added to K10's gradients by autograd) and, when `means3D` and `radii` (the rows K1
+        projected, the same P) are given, in means3D through the depth (depths = ([p,1] viewmatrix)[2])."""
+        view = cuda_args.get(_INVDEPTH_KEY) if isinstance(cuda_args, dict) else None
+        if view is None:
+            raise RuntimeError("render_invdepth: call render_gaussians of the same view with cuda_args['invdepth'] set "
+                               "first (it leaves the view's lists and n_contrib in cuda_args)")
+        if means3D is not None:
+            if radii is None:
+                raise ValueError("render_invdepth: `means3D` needs the `radii` of the same rows")
+            depths = _ViewDepths.apply(means3D, self.raster_settings.viewmatrix, depths, radii)
+        return _RenderInvDepth.apply(means2D, conic_opacity, depths, view)
 
 
 # ------------------------------------------------------------------------------- N1: fused loss

@@ -142,6 +142,9 @@ SIGNATURES = {
     "gsr_composite_walked": (c_int, [ctypes.POINTER(ctypes.c_ulonglong), c_int]),
     "gsr_render_contrib": (c_int, [c_int, c_int, c_int] + [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 4),
     "gsr_contrib_merge_rows": (c_int, [c_int64] + [c_void_p] * 8),
+    "gsr_render_invdepth": (c_int, [c_int, c_int, c_int] + [c_void_p] * 7 + [c_int, c_int, c_void_p, c_void_p]),
+    "gsr_render_invdepth_backward": (c_int, [c_int, c_int, c_int] + [c_void_p] * 10 + [c_int, c_int] + [c_void_p] * 3),
+    "gsr_depth_backward_means3d": (c_int, [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_int, c_void_p]),
     "gsr_publish_flag": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p]),
     "gsr_exchange_check": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_uint64, c_int, c_void_p,
                                    ctypes.c_uint32, ctypes.c_uint32, c_void_p, c_void_p]),

@@ -19,7 +19,8 @@ import torch.distributed as dist
 
 import utils.general_utils as utils
 from diff_gaussian_rasterization import image_metrics, metrics_from_sums
-from gaussian_renderer import distributed_preprocess3dgs_and_all2all_final, render_final
+from gaussian_renderer import (distributed_preprocess3dgs_and_all2all_final, get_invdepth, render_final,
+                               set_invdepth)
 from gaussian_renderer.loss_distribution import get_coverage_y_min_max, load_camera_from_cpu_to_all_gpu_for_eval
 from gaussian_renderer.workload_division import DivisionStrategyHistoryFinal, start_strategy_final
 
@@ -143,13 +144,17 @@ def _say(text):
 
 
 @torch.no_grad()
-def training_report(iteration, testing_iterations, scene, pipe_args, background, *, ssim=False, quantize=False):
+def training_report(iteration, testing_iterations, scene, pipe_args, background, *, ssim=False, quantize=False,
+                    invdepth=False):
     """Mirror of train_internal.py:355-493.  When the batch [iteration, iteration + bsz) reaches testing_iterations[0]
     (popped; passed entries are dropped first): render the test cameras and a subset of the train cameras in batches of
     bsz and write, per set, `[ITER n] Evaluating <name>: L1 <l1> PSNR <psnr>` -- rank 0 prints it, every rank writes it to
     utils.get_log_file().  The means over the cameras are accumulated in fp64 on the device; one host read per set.
     -> {name: {"l1", "psnr", "ssim" (None unless asked for), "num_cameras", "cameras" (uids, in the order scored)}}, empty
-    when nothing was due (the reference returns nothing; a caller here wants the numbers)."""
+    when nothing was due (the reference returns nothing; a caller here wants the numbers).
+    `invdepth` (extension of this build): also render every scored camera's inverse-depth map (gaussian_renderer
+    .set_invdepth, switched on for the duration of the call), assembled across the bands by a SUM all-reduce like the
+    image, and return them as report[name]["invdepth"]: one [H,W] device tensor per entry of "cameras", 4 H W bytes each."""
     args = utils.get_args()
     log_file = utils.get_log_file()
     while len(testing_iterations) > 0 and iteration > testing_iterations[0]:
@@ -173,7 +178,7 @@ def training_report(iteration, testing_iterations, scene, pipe_args, background,
         dataset = EvalDataset(cameras)
         history = DivisionStrategyHistoryFinal(dataset, group.size(), group.rank())
         acc = torch.zeros(3, dtype=torch.float64, device=dev)  # sums over the cameras of (l1, psnr, ssim)
-        uids = []
+        uids, maps = [], []
         for idx in range(1, num_cameras + 1, args.bsz):
             to_load = min(args.bsz, num_cameras - idx + 1)
             if args.local_sampling:
@@ -186,9 +191,14 @@ def training_report(iteration, testing_iterations, scene, pipe_args, background,
                 batched_cameras = dataset.get_batched_cameras(to_load)
             strategies, gpuid2tasks = start_strategy_final(batched_cameras, history)
             load_camera_from_cpu_to_all_gpu_for_eval(batched_cameras, strategies, gpuid2tasks)
-            pkg = distributed_preprocess3dgs_and_all2all_final(batched_cameras, scene.gaussians, pipe_args, background,
-                                                               batched_strategies=strategies, mode="test")
-            batched_image, _ = render_final(pkg, strategies)
+            was = get_invdepth()
+            set_invdepth(was or invdepth)
+            try:
+                pkg = distributed_preprocess3dgs_and_all2all_final(batched_cameras, scene.gaussians, pipe_args,
+                                                                   background, batched_strategies=strategies, mode="test")
+                batched_image, _ = render_final(pkg, strategies)
+            finally:
+                set_invdepth(was)
             sums = evaluate_batch(batched_image, batched_cameras, strategies, ssim=ssim, quantize=quantize)
             l1, psnr, ss = metrics_from_sums(sums, utils.IMG_H, utils.IMG_W)
             keep = [k for k in range(len(batched_cameras)) if idx + k < num_cameras + 1]
@@ -196,6 +206,12 @@ def training_report(iteration, testing_iterations, scene, pipe_args, background,
             for k, camera in enumerate(batched_cameras):
                 if k in keep:
                     uids.append(camera.uid)
+                    if invdepth:
+                        inv = pkg["batched_invdepth"][k]
+                        inv = torch.zeros((utils.IMG_H, utils.IMG_W), device=dev) if inv is None else inv[0].clone()
+                        if group.size() > 1:
+                            dist.all_reduce(inv, op=dist.ReduceOp.SUM, group=group)
+                        maps.append(inv)
                 camera.original_image = None
         if num_cameras == 0:
             continue
@@ -206,5 +222,7 @@ def training_report(iteration, testing_iterations, scene, pipe_args, background,
             log_file.write(line + "\n")
         report[name] = {"l1": l1_mean, "psnr": psnr_mean, "ssim": ssim_mean if ssim else None,
                         "num_cameras": num_cameras, "cameras": uids}
+        if invdepth:
+            report[name]["invdepth"] = maps
     torch.cuda.empty_cache()
     return report

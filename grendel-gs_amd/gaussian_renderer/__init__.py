@@ -72,7 +72,7 @@ def get_cuda_args_final(strategy, mode="train"):
         iteration = -1
     else:
         raise ValueError("mode should be train or test.")
-    return {
+    ca = {
         "mode": mode,
         "world_size": str(utils.WORLD_SIZE),
         "global_rank": str(utils.GLOBAL_RANK),
@@ -87,6 +87,59 @@ def get_cuda_args_final(strategy, mode="train"):
         "avoid_pixel_all2all": False,
         "stats_collector": {},
     }
+    if _INVDEPTH[0]:  # (opt-in: without it the dictionary is the reference's, key for key)
+        ca["invdepth"] = True
+    return ca
+
+
+# ------------------------------------------------------------------------------ inverse-depth maps (opt-in)
+_INVDEPTH = [os.environ.get("GSR_INVDEPTH", "0") not in ("", "0")]
+
+
+def set_invdepth(on):
+    """True (default False; GSR_INVDEPTH=1 in the environment: True): render_final leaves pkg["batched_invdepth"] -- per
+    camera the inverse-depth map [1,H,W] of the official 3DGS rasterizer (sum of alpha T / depth, no background term),
+    zero outside this rank's band, or None where the camera is not rendered here or took the fewer-than-10-Gaussians
+    stand-in -- for depth supervision (loss_distribution.invdepth_l1).  Extension of this build: the reference renders
+    no depth.  render_final's return value is unchanged, and with the switch off nothing changes at all.
+    World size 1: the map carries gradients into xyz, opacity, scaling and rotation (not with
+    FusedAdam(fuse_backward=True): the xyz gradient of the depth path has to reach memory).  World size > 1: the map is
+    rendered (the bands SUM to the one-rank map), asking it for gradients raises NotImplementedError."""
+    _INVDEPTH[0] = bool(on)
+
+
+def get_invdepth():
+    return _INVDEPTH[0]
+
+
+class _InvDepthNoGrad(torch.autograd.Function):
+    """the map at world size > 1: tied into the graph so that a loss on it cannot silently train on nothing -- its
+    backward runs before the exchange's (it consumes the exchange's output) and raises before any collective"""
+
+    @staticmethod
+    def forward(ctx, inv, means2D):
+        return inv.view_as(inv)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise NotImplementedError("gradients of the inverse-depth map are not available at world size > 1: the depth "
+                                  "column of the received rows needs its own return trip through the exchange")
+
+
+def _invdepth_map(pkg, k, cuda_args, means2D, conic_opacity):
+    """-> [1,H,W], behind camera k's colour render on the same stream"""
+    rast = pkg["batched_rasterizers"][k]
+    depths = pkg["batched_depths_redistributed"][k]
+    wants_grad = torch.is_grad_enabled() and (means2D.requires_grad or conic_opacity.requires_grad)
+    xyz = pkg.get("_invdepth_xyz")
+    if xyz is not None:  # no exchange: the rendered rows are the model's rows, in order
+        if wants_grad and xyz.requires_grad:
+            return rast.render_invdepth(means2D, conic_opacity, depths, cuda_args, means3D=xyz,
+                                        radii=pkg["batched_radii_redistributed"][k])[None]
+        return rast.render_invdepth(means2D, conic_opacity, depths, cuda_args)[None]
+    with torch.no_grad():
+        inv = rast.render_invdepth(means2D, conic_opacity, depths, cuda_args)[None]
+    return _InvDepthNoGrad.apply(inv, means2D) if wants_grad else inv
 
 
 # ------------------------------------------------------------------------------ the exchange
@@ -826,6 +879,8 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
         redistributed = tuple([p[c] for p in params] for c in range(5))
         sizes = [[[p[0].shape[0] for p in params]]]
         _fill(pkg, redistributed, sizes)
+        if _INVDEPTH[0]:
+            pkg["_invdepth_xyz"] = raw[0]  # (the depth path of the inverse-depth map: dL/ddepth -> dL/dxyz)
         return pkg
     if W * len(params) > 512:
         raise ValueError(f"world size x batch size = {W * len(params)} exceeds the 512 (destination, camera) segments "
@@ -892,6 +947,7 @@ def _render_cameras(pkg, batched_strategies):
     reads num_rendered back at the same place)."""
     timers = utils.get_timers()
     images, masks, late = [], [], []
+    invdepth = [None] * len(batched_strategies)  # (left in the package only when a camera's cuda_args ask for the map)
     mine = [k for k, st in enumerate(batched_strategies) if utils.GLOBAL_RANK in st.gpu_ids]
     dev0 = pkg["batched_means2D_redistributed"][mine[0]].device if mine else None
     two = (_EXCHANGE_OPTIONS["camera_streams"] > 1 and len(mine) > 1 and dev0 is not None and dev0.type == "cuda"
@@ -937,6 +993,10 @@ def _render_cameras(pkg, batched_strategies):
                         compute_locally=compute_locally, extended_compute_locally=extended, cuda_args=cuda_args)
                 finally:
                     cuda_args.pop("_gsr_pending", None)
+                if cuda_args.get("invdepth"):
+                    invdepth[k] = _invdepth_map(pkg, k, cuda_args, means2D, conic_opacity)
+                    if two:
+                        invdepth[k].record_stream(main)
             if two:
                 image.record_stream(main)  # (allocated on the side stream, consumed by the loss on the caller's)
             if timers is not None:
@@ -946,6 +1006,8 @@ def _render_cameras(pkg, batched_strategies):
     if two:
         for s_ in sides:
             main.wait_stream(s_)
+    if any(ca.get("invdepth") for ca in pkg["batched_cuda_args"]):
+        pkg["batched_invdepth"] = invdepth
     return images, masks, late
 
 

@@ -12,6 +12,8 @@ Each rank evaluates L1 and SSIM on ITS row band only, zero-padded at the band ed
 normalised by the FULL image's pixel count, so that the per-rank partial losses of a camera add up to
 the full-image loss up to the band-border SSIM term.
 """
+import math
+
 import torch
 import torch.distributed as dist
 
@@ -241,3 +243,32 @@ def batched_loss_computation(batched_image, batched_cameras, batched_compute_loc
     if timers is not None:
         timers.stop("loss_computation")
     return (total if args.lr_scale_loss == 1.0 else total * args.lr_scale_loss), parts
+
+
+# ------------------------------------------------------------------------------ depth supervision (opt-in)
+def invdepth_l1(invdepth, target, mask=None, y0=0, y1=None):
+    """mean(|invdepth - target| * mask) over the rows [y0, y1) of this rank's band -- the official 3DGS depth
+    regulariser's L1 on the inverse-depth map render_final leaves in pkg["batched_invdepth"] (gaussian_renderer
+    .set_invdepth); `target` the prior's inverse depth, `mask` its validity (None: everywhere), all [1,H,W] or [H,W].
+    Four element-wise operations on one channel, in plain torch (extension of this build: the reference has no depth
+    loss); the caller multiplies by invdepth_weight(iteration, ...)."""
+    if not invdepth.is_cuda:
+        raise RuntimeError("invdepth_l1: the map must live on the gfx950 device (there is no CPU path)")
+    H = invdepth.shape[-2]
+    y1 = H if y1 is None else min(int(y1), H)
+    rows = slice(int(y0), y1)
+    diff = (invdepth[..., rows, :] - target[..., rows, :].to(invdepth.dtype)).abs()
+    if mask is not None:
+        diff = diff * mask[..., rows, :].to(invdepth.dtype)
+    return diff.mean()
+
+
+def invdepth_weight(iteration, init=1.0, final=0.01, max_steps=30_000):
+    """the official exponential schedule of the depth regulariser's weight (log-linear from `init` at iteration 0 to
+    `final` at `max_steps`, constant afterwards; 0 when both ends are 0 or the iteration is negative)"""
+    if iteration < 0 or (init == 0.0 and final == 0.0):
+        return 0.0
+    if init <= 0.0 or final <= 0.0:
+        raise ValueError("invdepth_weight: `init` and `final` must both be positive (or both 0)")
+    t = min(max(iteration / float(max_steps), 0.0), 1.0)
+    return math.exp(math.log(init) * (1.0 - t) + math.log(final) * t)

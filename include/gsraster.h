@@ -398,6 +398,56 @@ int gsr_contrib_merge_rows(int64_t n, const int32_t *idx, const int64_t *src_hit
                            const double *src_wsum, int64_t *dst_hits, float *dst_wmax, double *dst_wsum,
                            gsr_stream_t stream);
 
+/* INVERSE-DEPTH map of a rendered view, with gradients (depth supervision).  The reference's rasterizer renders no depth
+ * of any kind, so there is NO reference call site for these three entry points: the quantity is the inverse-depth output
+ * of the official 3DGS rasterizer, and oracle/torch_oracle.py's `render` with rgb = (v, 0, 0), bg = 0 -- differentiated
+ * by autograd in float64 -- is the arbiter.  New symbols only: gsr_abi_version does not move.
+ * A walk over the lists gsr_render_forward drew from, with that call's n_contrib (and, backward, final_T): the entry at
+ * list position k (0-based) of a local tile is BLENDED on a pixel iff k + 1 <= n_contrib[pixel], power <= 0 and
+ * alpha = min(0.99, o exp(power)) >= 1/255 -- gsr_render_contrib's rule, in the composite kernels' own arithmetic;
+ * nothing is re-decided.  Per pixel T starts at 1; a blended entry i has the weight w_i = alpha_i T_i, then T <- T - w_i.
+ * v_i = 1.0f / depths[id_i], depths = K1's view-space z.  CALLER'S CONDITION: every listed row has depth > 0 (K1 lists
+ * rows with radii > 0 only, whose depth exceeds 0.2); rows in no list may carry any depth, 0 included.
+ * ranges, point_list, means2D, conic_opacity, compute_locally, row_lo / row_hi: as gsr_render_contrib (whole grid, host
+ * band, -1 = device hull behind the range table).
+ *
+ * gsr_render_invdepth: invdepth fp32 [H,W], FULLY overwritten:
+ *   invdepth[p] = sum over the blended entries of w_i v_i -- no background term, no division by 1 - T_final; pixels of
+ *   tiles that are not ours (and of tiles outside the band of a band launch) are exactly 0: the map is assembled across
+ *   bands by a SUM, as the image is.  P == 0 writes the all-zero map and touches nothing else.
+ *
+ * gsr_render_invdepth_backward: with g = dL_dinvdepth[p] ([H,W]; read on the local tiles only),
+ *   dL/dv_i     = sum_p g w_i, hence dL/ddepth_i = -(sum_p g w_i) / depth_i^2;
+ *   dL/dalpha_i = g (T_i v_i - S_i / (1 - alpha_i)), S_i = the sum of w_j v_j over the blended j behind i;
+ *   from dL/dalpha on, gsr_render_backward's chain to opacity, conic (A, B, C) and means2D, including its treatment of
+ *   the 0.99 clamp (the identity in the backward); means2D gradients in its units: pixel gradient x (W/2, H/2).
+ *   dL_record fp32 [P,7], FULLY overwritten: [0:2] dL_dmeans2D, [2:6] dL_dconic_opacity, [6] dL_ddepth; rows that are
+ *   blended nowhere are 0.0f.  acc64: [P,7] doubles, device scratch of the caller, cleared by the call: the per-quadrant
+ *   sums (fp32, a fixed order over the 64 pixels) are added into it in fp64 and each sum is rounded once into the record
+ *   (gsr_render_backward's reason: the fp32 result does not depend on the order the tiles finish, but for the rare sum
+ *   within fp64 rounding of an fp32 rounding boundary).  final_T and invdepth are the forward calls' outputs; the walk
+ *   goes back to front from final_T, and `invdepth` is not read by this implementation (a front-to-back walk would take
+ *   S_i from it).  P == 0 returns 0 and touches nothing.
+ *
+ * gsr_depth_backward_means3d: depth = ([p,1] viewmatrix)[2] in the row-vector convention (viewmatrix: 16 floats on the
+ *   device, row-major), so dL_dmeans3D[i] (+)= dL_ddepth[i * row_stride] * (view[0][2], view[1][2], view[2][2]);
+ *   row_stride in floats (1 dense, 7 = column 6 of the record above).  Rows with radii <= 0 are skipped.  overwrite == 0:
+ *   += into the caller's (zeroed) [P,3]; overwrite != 0: every row is written, skipped rows as zeros.
+ *
+ * All three: a negative size, a non-positive frame (row_stride < 1), or a missing pointer with P > 0: GSR_EINVAL before
+ * any device work (the forward needs `invdepth` for P == 0 too). */
+int gsr_render_invdepth(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                        const float *means2D, const float *conic_opacity, const float *depths,
+                        const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi,
+                        float *invdepth, gsr_stream_t stream);
+int gsr_render_invdepth_backward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                                 const float *means2D, const float *conic_opacity, const float *depths,
+                                 const uint8_t *compute_locally, const int32_t *n_contrib, const float *final_T,
+                                 const float *invdepth, const float *dL_dinvdepth, int row_lo, int row_hi,
+                                 float *dL_record, double *acc64, gsr_stream_t stream);
+int gsr_depth_backward_means3d(int P, const int32_t *radii, const float *viewmatrix, const float *dL_ddepth,
+                               int row_stride, float *dL_dmeans3D, int overwrite, gsr_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * N1  fused band-local L1 + SSIM loss -- the arithmetic of final_system_loss_computation,
  * gaussian_renderer/loss_distribution.py:2536-2585 (pixelwise_l1_with_mask / pixelwise_ssim_with_mask,
