@@ -176,7 +176,33 @@ int gsr_render_backward(int P, int width, int height, const int32_t *ranges, con
         return GSR_EINVAL;
     return gsr_launch_composite_backward(P, width, height, ranges, point_list, means2D, conic_opacity, rgb,
                                          compute_locally, bg, final_T, n_contrib, dL_dpixels, dL_record, out_color,
-                                         seg_ws, seg_bytes, row_lo, row_hi, record_is_zero ? 1 : 0, acc64, touched,
+                                         seg_ws, seg_bytes, row_lo, row_hi, record_is_zero ? 1 : 0, acc64, touched, 1,
+                                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_render_backward_sums(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                             const float *means2D, const float *conic_opacity, const float *rgb,
+                             const uint8_t *compute_locally, const float *bg, const float *final_T,
+                             const int32_t *n_contrib, const float *dL_dpixels, const float *out_color, void *seg_ws,
+                             size_t seg_bytes, int row_lo, int row_hi, double *acc64, uint8_t *touched,
+                             gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!ranges || !compute_locally || !bg || !final_T || !n_contrib || !dL_dpixels || !means2D || !conic_opacity ||
+        !rgb || !acc64 || !touched)
+        return GSR_EINVAL;
+    return gsr_launch_composite_backward(P, width, height, ranges, point_list, means2D, conic_opacity, rgb,
+                                         compute_locally, bg, final_T, n_contrib, dL_dpixels, nullptr, out_color,
+                                         seg_ws, seg_bytes, row_lo, row_hi, 1, acc64, touched, 0,
+                                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_render_record_materialize(int P, const double *acc64, const uint8_t *touched, float *dL_record,
+                                  int record_is_zero, gsr_stream_t stream) {
+    if (P < 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!acc64 || !touched || !dL_record) return GSR_EINVAL;
+    return gsr_launch_record_materialize(P, acc64, touched, dL_record, record_is_zero ? 1 : 0,
                                          reinterpret_cast<hipStream_t>(stream));
 }
 

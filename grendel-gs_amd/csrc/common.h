@@ -183,7 +183,10 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
                                   const uint8_t *compute_locally, const float *bg, const float *final_T,
                                   const int32_t *n_contrib, const float *dL_dpixels, float *dL_record,
                                   const float *out_color, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
-                                  int record_is_zero, double *acc64, uint8_t *touched, hipStream_t stream);
+                                  int record_is_zero, double *acc64, uint8_t *touched, int round_record,
+                                  hipStream_t stream);
+int gsr_launch_record_materialize(int P, const double *acc64, const uint8_t *touched, float *dL_record,
+                                  int record_is_zero, hipStream_t stream);
 int gsr_launch_composite_contrib(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
                                  const float *means2D, const float *conic_opacity, const uint8_t *compute_locally,
                                  const int32_t *n_contrib, int row_lo, int row_hi, int64_t *hits, float *wmax,

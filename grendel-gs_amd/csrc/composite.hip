@@ -17,6 +17,9 @@
 //
 // Backward: the same walk in reverse order; the per-pixel products are transposed through LDS and contracted
 // over the 64 pixels of the quadrant on the matrix pipe (exact-fp32 MFMA) -- see the comment above K10.
+#include <atomic>
+#include <cstdlib>
+
 #include "common.h"
 #include "composite_math.h"  // the alpha arithmetic, the block -> tile map, the band's launch geometry (shared with contrib.hip)
 
@@ -1040,10 +1043,13 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
                                   const uint8_t *compute_locally, const float *bg, const float *final_T,
                                   const int32_t *n_contrib, const float *dL_dpixels, float *dL_record,
                                   const float *out_color, void *seg_ws, size_t seg_bytes, int row_lo, int row_hi,
-                                  int record_is_zero, double *acc64, uint8_t *touched, hipStream_t stream) {
+                                  int record_is_zero, double *acc64, uint8_t *touched, int round_record,
+                                  hipStream_t stream) {
     // (acc64: [P,9] fp64 sums K10 adds into, rounded once to the record afterwards; record_is_zero: the forward launch
     // cleared them; touched: [P] row flags -- the forward cleared sums, record AND flags, only the rows K10 flags are
-    // rounded)
+    // rounded.  round_record == 0 (gsr_render_backward_sums): the sums and flags ARE the result, dL_record is not
+    // touched; whoever needs the record calls gsr_launch_record_materialize)
+    if (!round_record && (!record_is_zero || !touched)) return GSR_EINVAL;
     if (!record_is_zero) {
         touched = nullptr;
         GSR_HIP(hipMemsetAsync(acc64, 0, sizeof(double) * 9 * (size_t)P, stream));
@@ -1063,6 +1069,7 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
                        reinterpret_cast<const float4 *>(conic_opacity), rgb, compute_locally, bg, final_T, n_contrib,
                        dL_dpixels, acc64, seg, b.band_first, b.band_tiles, touched);
     GSR_LAUNCH_CHECK();
+    if (!round_record) return 0;
     if (touched)
         hipLaunchKernelGGL(record_from_f64_touched_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream,
                            acc64, dL_record, touched, P);
@@ -1071,4 +1078,35 @@ int gsr_launch_composite_backward(int P, int W, int H, const int32_t *ranges, co
                            acc64, dL_record, 9 * (size_t)P);
     GSR_LAUNCH_CHECK();
     return 0;
+}
+
+// the rounding gsr_render_backward_sums left out, on any stream that is ordered behind that launch: the flagged rows
+// as above; record_is_zero == 0: the forward did not clear the record (its 36 P bytes were left out of K8's clear),
+// so the other rows are written too
+int gsr_launch_record_materialize(int P, const double *acc64, const uint8_t *touched, float *dL_record,
+                                  int record_is_zero, hipStream_t stream) {
+    if (P == 0) return 0;
+    if (!record_is_zero) GSR_HIP(hipMemsetAsync(dL_record, 0, sizeof(float) * 9 * (size_t)P, stream));
+    hipLaunchKernelGGL(record_from_f64_touched_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, acc64,
+                       dL_record, touched, P);
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
+// gsr_set_deferred_rounding: process-wide, like the binning switches (binning_host.h).  The library only keeps the
+// word; the caller that owns the record (diff_gaussian_rasterization) asks before it leaves the rounding out.
+static std::atomic<int> g_deferred_rounding{-1};  // -1 = environment
+extern "C" int gsr_set_deferred_rounding(int mode) {
+    if (mode < -1 || mode > 1) return GSR_EINVAL;
+    g_deferred_rounding.store(mode, std::memory_order_relaxed);
+    return 0;
+}
+extern "C" int gsr_deferred_rounding(void) {  // GSR_DEFER_ROUNDING = 0 | 1 (default)
+    const int mode = g_deferred_rounding.load(std::memory_order_relaxed);
+    if (mode >= 0) return mode;
+    static const int env_mode = [] {
+        const char *e = getenv("GSR_DEFER_ROUNDING");
+        return (e && *e == '0') ? 0 : 1;
+    }();
+    return env_mode;
 }

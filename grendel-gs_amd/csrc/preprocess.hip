@@ -867,6 +867,71 @@ __device__ __forceinline__ K11In k11_load(size_t i, const float *__restrict__ me
     return in;
 }
 
+// Where the fused dense kernels (K11 + Adam, one camera and camera-batched) take the incoming gradient from.
+// GradRecord: fp32 gradients, dense or columns of a record (grad_ld2 above) -- what every other K11 kernel reads; the
+// record kernels keep the three pointers and the stride as arguments of their own, the struct only bundles them on the host.
+// GradSums: K10's own [P,9] fp64 sums and [P] row flags of each camera (gsr_render_backward_sums), before anything has
+// rounded them into a record.  A lane converts the nine doubles of a flagged row with one (float) each, in the record's
+// column order (means2D 0:2, rgb 2:5, conic_opacity 5:9): the bits record_from_f64_touched_kernel would have stored.
+// A row whose flag is clear received nothing: its record row would be the forward's zeros, so it takes the kernels'
+// zero-gradient path as a culled row does, and neither its sums nor its cov3D / clamp flags are read.
+struct GradRecord {
+    const float *means2D, *conic_opacity, *rgb;
+    int gstride;
+};
+constexpr int K11_SUMS_CAMS = 8;  // cameras one GradSums launch takes (the tables travel in the kernel arguments)
+struct GradSums {
+    const double *acc[K11_SUMS_CAMS];
+    const uint8_t *flags[K11_SUMS_CAMS];
+};
+#ifndef GSR_K11_SUMS_COV_ALWAYS
+#define GSR_K11_SUMS_COV_ALWAYS 0  // 1 (A/B): cov3D and the clamp flags are loaded for every row, only the sums wait
+#endif
+
+// k11_load with GradSums.  `rad` and `flag` are the lane's radius and row flag, which the caller requested FIRST: they
+// decide the loads at the bottom, and the wait for them leaves every other load of the lane in flight.
+__device__ __forceinline__ K11In k11_load_sums(size_t i, int32_t rad, uint8_t flag, const float *__restrict__ xyz,
+                                               const float *__restrict__ scaling, const float *__restrict__ rotation,
+                                               const float *__restrict__ f_dc, const float *__restrict__ opacity,
+                                               const float *__restrict__ cov3D, const uint8_t *__restrict__ clamped,
+                                               const double *__restrict__ acc) {
+    K11In in;
+#pragma unroll
+    for (int e = 0; e < 3; e++) {
+        in.p[e] = xyz[3 * i + e];
+        in.sc[e] = scaling[3 * i + e];
+        in.dc[e] = f_dc[3 * i + e];
+        in.cl[e] = GSR_K11_SUMS_COV_ALWAYS ? clamped[3 * i + e] : (uint8_t)0;
+        in.grgb[e] = 0.f;
+    }
+    in.op = opacity[i];
+    in.q = *reinterpret_cast<const float4 *>(rotation + 4 * i);
+#pragma unroll
+    for (int e = 0; e < 6; e++) in.cv[e] = GSR_K11_SUMS_COV_ALWAYS ? cov3D[6 * i + e] : 0.f;
+    in.gco = make_float4(0.f, 0.f, 0.f, 0.f);
+    in.g2 = make_float2(0.f, 0.f);
+    __builtin_amdgcn_sched_barrier(0);  // the loads above are issued before the flag is waited for
+    const bool live = flag && rad > 0;
+    in.rad = live ? rad : 0;
+    if (live) {
+        const double *a = acc + 9 * i;
+        double v[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) v[k] = a[k];
+        if (!GSR_K11_SUMS_COV_ALWAYS) {
+#pragma unroll
+            for (int e = 0; e < 6; e++) in.cv[e] = cov3D[6 * i + e];
+#pragma unroll
+            for (int e = 0; e < 3; e++) in.cl[e] = clamped[3 * i + e];
+        }
+        in.g2 = make_float2((float)v[0], (float)v[1]);
+#pragma unroll
+        for (int e = 0; e < 3; e++) in.grgb[e] = (float)v[2 + e];
+        in.gco = make_float4((float)v[5], (float)v[6], (float)v[7], (float)v[8]);
+    }
+    return in;
+}
+
 // dL/dopacity of one row from g = the summed dL/dconic_opacity.w (AA: each camera's times its rho): through the sigmoid
 // for the raw forms, into the fused step's slot 13 or to HBM
 template <bool RAW, bool ADAM>
@@ -1084,24 +1149,37 @@ preprocess_backward_kernel(int P, int M, const float *__restrict__ means3D, cons
 
 // K11 + Adam, one camera, 16-coefficient model (the launcher checks): the same body with the stores replaced by the
 // optimizer update (K11Adam above).  Own kernel name so that traces and counters tell the fused launch apart.
-template <int DEG, bool AA>
-__global__ void __launch_bounds__(K11_BLOCK, K11_WAVES_PER_EU)
-preprocess_backward_adam_kernel(int P, float *__restrict__ xyz, float *__restrict__ scaling, float scale_modifier,
-                                float *__restrict__ rotation, float *__restrict__ f_dc, float *__restrict__ f_rest,
-                                float *__restrict__ opacity, const float *__restrict__ view,
-                                const float *__restrict__ proj, const float *__restrict__ campos, int W, int H,
-                                float tanfovx, float tanfovy, const int32_t *__restrict__ radii,
-                                const float *__restrict__ cov3D, const uint8_t *__restrict__ clamped,
-                                const float *__restrict__ dL_dmeans2D, const float *__restrict__ dL_dconic_opacity,
-                                const float *__restrict__ dL_drgb, int gstride, const K11Adam ad_in) {
+// GRAD: GradNone -- the gradients are the three fp32 pointers and their row stride (preprocess_backward_adam_kernel) --
+// or GradSums (preprocess_backward_adam_sums_kernel: the row's flag and radius are requested first, k11_load_sums).
+struct GradNone {};
+template <int DEG, bool AA, typename GRAD>
+__device__ __forceinline__ void
+preprocess_backward_adam_body(int P, float *__restrict__ xyz, float *__restrict__ scaling, float scale_modifier,
+                              float *__restrict__ rotation, float *__restrict__ f_dc, float *__restrict__ f_rest,
+                              float *__restrict__ opacity, const float *__restrict__ view,
+                              const float *__restrict__ proj, const float *__restrict__ campos, int W, int H,
+                              float tanfovx, float tanfovy, const int32_t *__restrict__ radii,
+                              const float *__restrict__ cov3D, const uint8_t *__restrict__ clamped,
+                              const float *__restrict__ dL_dmeans2D, const float *__restrict__ dL_dconic_opacity,
+                              const float *__restrict__ dL_drgb, int gstride, const GRAD &sums, const K11Adam &ad_in) {
     if (ad_in.skip && *ad_in.skip) return;  // wave-uniform: a capacity overflowed earlier in this replay
     const K11Adam ad = k11_adam_resolve(ad_in);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ float s_rest[K11_BLOCK * REST_W];
     const size_t ic = (size_t)min(i, P - 1);
+    int32_t rad = 0;
+    uint8_t flag = 0;
+    if constexpr (std::is_same<GRAD, GradSums>::value) {
+        rad = radii[ic];
+        flag = sums.flags[0][ic];
+    }
     RestStage st = rest_stage_issue(f_rest, P);
-    const K11In in = k11_load<true>(ic, xyz, scaling, rotation, f_dc, opacity, radii, cov3D, clamped, dL_dmeans2D,
-                                    dL_dconic_opacity, dL_drgb, gstride);
+    K11In in;
+    if constexpr (std::is_same<GRAD, GradSums>::value)
+        in = k11_load_sums(ic, rad, flag, xyz, scaling, rotation, f_dc, opacity, cov3D, clamped, sums.acc[0]);
+    else
+        in = k11_load<true>(ic, xyz, scaling, rotation, f_dc, opacity, radii, cov3D, clamped, dL_dmeans2D,
+                            dL_dconic_opacity, dL_drgb, gstride);
     __builtin_amdgcn_sched_barrier(0);  // every load of the lane is issued before the first result is used
     rest_stage_commit(s_rest, st, f_rest, P);
     __syncthreads();
@@ -1115,6 +1193,33 @@ preprocess_backward_adam_kernel(int P, float *__restrict__ xyz, float *__restric
     rest_adam_out(s_rest, f_rest, ad, P);
     __syncthreads();  // the stage is free: the moments of the small tensors go through it
     k11_adam_small_lds(s_rest, ad, P, i, xyz, scaling, rotation, f_dc, opacity, sp, sg);
+}
+template <int DEG, bool AA>
+__global__ void __launch_bounds__(K11_BLOCK, K11_WAVES_PER_EU)
+preprocess_backward_adam_kernel(int P, float *__restrict__ xyz, float *__restrict__ scaling, float scale_modifier,
+                                float *__restrict__ rotation, float *__restrict__ f_dc, float *__restrict__ f_rest,
+                                float *__restrict__ opacity, const float *__restrict__ view,
+                                const float *__restrict__ proj, const float *__restrict__ campos, int W, int H,
+                                float tanfovx, float tanfovy, const int32_t *__restrict__ radii,
+                                const float *__restrict__ cov3D, const uint8_t *__restrict__ clamped,
+                                const float *__restrict__ dL_dmeans2D, const float *__restrict__ dL_dconic_opacity,
+                                const float *__restrict__ dL_drgb, int gstride, const K11Adam ad_in) {
+    preprocess_backward_adam_body<DEG, AA>(P, xyz, scaling, scale_modifier, rotation, f_dc, f_rest, opacity, view, proj,
+                                           campos, W, H, tanfovx, tanfovy, radii, cov3D, clamped, dL_dmeans2D,
+                                           dL_dconic_opacity, dL_drgb, gstride, GradNone{}, ad_in);
+}
+template <int DEG, bool AA>
+__global__ void __launch_bounds__(K11_BLOCK, K11_WAVES_PER_EU)
+preprocess_backward_adam_sums_kernel(int P, float *__restrict__ xyz, float *__restrict__ scaling, float scale_modifier,
+                                     float *__restrict__ rotation, float *__restrict__ f_dc,
+                                     float *__restrict__ f_rest, float *__restrict__ opacity,
+                                     const float *__restrict__ view, const float *__restrict__ proj,
+                                     const float *__restrict__ campos, int W, int H, float tanfovx, float tanfovy,
+                                     const int32_t *__restrict__ radii, const float *__restrict__ cov3D,
+                                     const uint8_t *__restrict__ clamped, const GradSums sums, const K11Adam ad_in) {
+    preprocess_backward_adam_body<DEG, AA>(P, xyz, scaling, scale_modifier, rotation, f_dc, f_rest, opacity, view, proj,
+                                           campos, W, H, tanfovx, tanfovy, radii, cov3D, clamped, nullptr, nullptr,
+                                           nullptr, 0, sums, ad_in);
 }
 
 // ------------------------------------------------------------------------- K1 / K11, batched over cameras
@@ -1258,6 +1363,38 @@ __device__ __forceinline__ K11CamGeo k11_cam_load_geo(size_t o, const int32_t *_
     c.g2 = grad_ld2(dL_dmeans2D, o, gstride);
     return c;
 }
+// The same two with GradSums: `live` = the camera's flag of the row is set and the row is visible there (the body reads
+// every camera's flag and radius once, at the top); o = camera * P + row as above, a = the camera's sums of the row.
+// A camera that is not live loads nothing and comes back with radius 0: the loops skip it.
+__device__ __forceinline__ K11CamSH k11_cam_load_sh_sums(size_t o, bool live, const uint8_t *__restrict__ clamped,
+                                                         const double *__restrict__ a) {
+    K11CamSH c;
+    c.rad = live ? 1 : 0;
+#pragma unroll
+    for (int e = 0; e < 3; e++) {
+        c.grgb[e] = 0.f;
+        c.cl[e] = 0;
+    }
+    if (live) {
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+            c.grgb[e] = (float)a[2 + e];
+            c.cl[e] = clamped[3 * o + e];
+        }
+    }
+    return c;
+}
+__device__ __forceinline__ K11CamGeo k11_cam_load_geo_sums(bool live, const double *__restrict__ a) {
+    K11CamGeo c;
+    c.rad = live ? 1 : 0;
+    c.gco = make_float4(0.f, 0.f, 0.f, 0.f);
+    c.g2 = make_float2(0.f, 0.f);
+    if (live) {
+        c.g2 = make_float2((float)a[0], (float)a[1]);
+        c.gco = make_float4((float)a[5], (float)a[6], (float)a[7], (float)a[8]);
+    }
+    return c;
+}
 
 // Where the lanes of the camera-batched body find their rows.  DenseRows: lane i of the grid owns row i, a workgroup's
 // rows are contiguous (the LDS stage moves them in 16-byte pieces).  ListRows (the sparse update, ADAM and 16
@@ -1350,7 +1487,7 @@ __device__ __forceinline__ void sa_rest_adam_out(const float *__restrict__ s_res
     }
 }
 
-template <int DEG, bool ADAM, bool AA, typename ROWS = DenseRows>
+template <int DEG, bool ADAM, bool AA, typename ROWS = DenseRows, bool SUMS = false>
 __device__ __forceinline__ void
 preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ xyz,
                                    const float *__restrict__ scaling, float scale_modifier,
@@ -1364,9 +1501,10 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
                                    float *__restrict__ dL_dxyz, float *__restrict__ dL_dscaling,
                                    float4 *__restrict__ dL_drotation, float *__restrict__ dL_ddc,
                                    float *__restrict__ dL_drest, float *__restrict__ dL_dopacity, const K11Adam &ad,
-                                   const ROWS rows = ROWS{}) {
+                                   const ROWS rows = ROWS{}, const GradSums *sums = nullptr) {
     constexpr bool LIST = std::is_same<ROWS, ListRows>::value;
     static_assert(!LIST || ADAM, "ListRows is the sparse K11 + Adam update (and takes M == 16)");
+    static_assert(!SUMS || (ADAM && !LIST), "GradSums (B <= K11_SUMS_CAMS) feeds the fused dense kernel only");
     __shared__ float s_rest[K11_BLOCK * REST_W];
     __shared__ uint32_t s_rows[LIST ? K11_BLOCK : 1];  // ListRows: the workgroup's rows, for the gathers
     const bool staged = M == 16;  // _features_rest in, its gradient out: coalesced through LDS (ADAM: always)
@@ -1376,6 +1514,7 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
     int i, nrows = 0;  // the lane's row;  ListRows: the workgroup's share of the list
     size_t ic;
     RestStage st;
+    uint32_t live = 0;  // GradSums: bit c = camera c added into the row (flag set) and the row is visible there
     if constexpr (LIST) {
         const size_t first = (size_t)blockIdx.x * K11_BLOCK;
         nrows = (int)min((size_t)K11_BLOCK, (size_t)rows.count - first);
@@ -1386,12 +1525,29 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
     } else {
         i = blockIdx.x * blockDim.x + threadIdx.x;
         ic = (size_t)min(i, P - 1);
-        if (staged) st = rest_stage_issue(f_rest, P);
+        if constexpr (SUMS) {  // every camera's flag and radius of the row first: they decide the loads of the queue
+            int32_t rd[K11_SUMS_CAMS];
+            uint8_t fl[K11_SUMS_CAMS];
+#pragma unroll
+            for (int u = 0; u < K11_SUMS_CAMS; u++) {
+                const int c = min(u, B - 1);
+                rd[u] = radii[(size_t)c * P + ic];
+                fl[u] = sums->flags[c][ic];
+            }
+            if (staged) st = rest_stage_issue(f_rest, P);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < K11_SUMS_CAMS; u++) live |= (u < B && fl[u] && rd[u] > 0) ? 1u << u : 0u;
+        } else if (staged) st = rest_stage_issue(f_rest, P);
     }
     const float p[3] = {xyz[3 * ic], xyz[3 * ic + 1], xyz[3 * ic + 2]};
     float cvr[6];
 #pragma unroll
-    for (int e = 0; e < 6; e++) cvr[e] = cov3D[6 * ic + e];
+    for (int e = 0; e < 6; e++) cvr[e] = SUMS ? 0.f : cov3D[6 * ic + e];
+    if (SUMS && live) {
+#pragma unroll
+        for (int e = 0; e < 6; e++) cvr[e] = cov3D[6 * ic + e];
+    }
     const float dc[3] = {f_dc[3 * ic], f_dc[3 * ic + 1], f_dc[3 * ic + 2]};
     const float oraw = opacity[ic];
     const float4 qraw = *reinterpret_cast<const float4 *>(rotation + 4 * ic);
@@ -1404,8 +1560,15 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
 #pragma unroll
         for (int u = 0; u < K11_CAMQ; u++) {
             const size_t o = (size_t)min(u, B - 1) * P + ic;
-            shq[u] = k11_cam_load_sh(o, radii, clamped, dL_drgb, gstride);
-            geoq[u] = k11_cam_load_geo(o, radii, dL_dmeans2D, dL_dconic_opacity, gstride);
+            if constexpr (SUMS) {
+                const int c = min(u, B - 1);
+                const double *a = sums->acc[c] + 9 * ic;
+                shq[u] = k11_cam_load_sh_sums(o, (live >> c) & 1u, clamped, a);
+                geoq[u] = k11_cam_load_geo_sums((live >> c) & 1u, a);
+            } else {
+                shq[u] = k11_cam_load_sh(o, radii, clamped, dL_drgb, gstride);
+                geoq[u] = k11_cam_load_geo(o, radii, dL_dmeans2D, dL_dconic_opacity, gstride);
+            }
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1450,8 +1613,15 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
         if constexpr (!LIST) {
 #pragma unroll
             for (int u = 0; u + 1 < K11_CAMQ; u++) shq[u] = shq[u + 1];
-            if (bc + K11_CAMQ < B)  // (uniform) the camera K11_CAMQ ahead: in flight while this one is differentiated
-                shq[K11_CAMQ - 1] = k11_cam_load_sh((size_t)(bc + K11_CAMQ) * P + i, radii, clamped, dL_drgb, gstride);
+            if (bc + K11_CAMQ < B) {  // (uniform) the camera K11_CAMQ ahead: in flight while this one is differentiated
+                if constexpr (SUMS)
+                    shq[K11_CAMQ - 1] =
+                        k11_cam_load_sh_sums((size_t)(bc + K11_CAMQ) * P + i, (live >> (bc + K11_CAMQ)) & 1u, clamped,
+                                             sums->acc[bc + K11_CAMQ] + 9 * (size_t)i);
+                else
+                    shq[K11_CAMQ - 1] =
+                        k11_cam_load_sh((size_t)(bc + K11_CAMQ) * P + i, radii, clamped, dL_drgb, gstride);
+            }
         }
         if (cin.rad <= 0) continue;
         if (staged) asm volatile("" ::: "memory");  // (keeps the LDS reads of the coefficients inside the loop)
@@ -1489,9 +1659,14 @@ preprocess_backward_batched_body(int P, int B, int M, const float *__restrict__ 
         if constexpr (!LIST) {
 #pragma unroll
             for (int u = 0; u + 1 < K11_CAMQ; u++) geoq[u] = geoq[u + 1];
-            if (bc + K11_CAMQ < B)
-                geoq[K11_CAMQ - 1] = k11_cam_load_geo((size_t)(bc + K11_CAMQ) * P + i, radii, dL_dmeans2D,
-                                                      dL_dconic_opacity, gstride);
+            if (bc + K11_CAMQ < B) {
+                if constexpr (SUMS)
+                    geoq[K11_CAMQ - 1] = k11_cam_load_geo_sums((live >> (bc + K11_CAMQ)) & 1u,
+                                                               sums->acc[bc + K11_CAMQ] + 9 * (size_t)i);
+                else
+                    geoq[K11_CAMQ - 1] = k11_cam_load_geo((size_t)(bc + K11_CAMQ) * P + i, radii, dL_dmeans2D,
+                                                          dL_dconic_opacity, gstride);
+            }
         }
         if (cin.rad <= 0) continue;
         const float *cp = cams + (size_t)bc * CAM_STRIDE;
@@ -1610,6 +1785,22 @@ preprocess_backward_adam_batched_kernel(int P, int B, float *__restrict__ xyz, f
                                                     opacity, cams, W, H, radii, cov3D, clamped, dL_dmeans2D,
                                                     dL_dconic_opacity, dL_drgb, gstride, nullptr, nullptr, nullptr,
                                                     nullptr, nullptr, nullptr, ad);
+}
+// (GradSums: B <= K11_SUMS_CAMS cameras)
+template <int DEG, bool AA>
+__global__ void __launch_bounds__(K11_BLOCK, K11B_WAVES_PER_EU)
+preprocess_backward_adam_batched_sums_kernel(int P, int B, float *__restrict__ xyz, float *__restrict__ scaling,
+                                             float scale_modifier, float *__restrict__ rotation,
+                                             float *__restrict__ f_dc, float *__restrict__ f_rest,
+                                             float *__restrict__ opacity, const float *__restrict__ cams, int W, int H,
+                                             const int32_t *__restrict__ radii, const float *__restrict__ cov3D,
+                                             const uint8_t *__restrict__ clamped, const GradSums sums,
+                                             const K11Adam ad_in) {
+    if (ad_in.skip && *ad_in.skip) return;
+    const K11Adam ad = k11_adam_resolve(ad_in);
+    preprocess_backward_batched_body<DEG, true, AA, DenseRows, true>(
+        P, B, 16, xyz, scaling, scale_modifier, rotation, f_dc, f_rest, opacity, cams, W, H, radii, cov3D, clamped,
+        nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ad, DenseRows{}, &sums);
 }
 
 // ------------------------------------------------------------------- sparse (lazy) K11 + Adam
@@ -2094,6 +2285,54 @@ static bool k11_adam_fill(K11Adam &ad, std::initializer_list<const void *> devic
     return false;
 }
 
+// The dense fused launch once the arguments are checked and `ad` is filled: alignment of what is moved in 16-byte
+// pieces, then the one-camera kernel (B == 1 with the host tangents) or the camera-batched one, for either source.
+template <typename SRC>
+static int k11_adam_launch(int P, int B, int sh_degree, float *xyz, float *scaling, float scale_modifier, float *rotation,
+                           float *features_dc, float *features_rest, float *opacity, const float *cams, int width,
+                           int height, const int32_t *radii, const float *cov3D, const uint8_t *clamped, const SRC &src,
+                           const K11Adam &ad, const float *tanfov0, gsr_stream_t stream) {
+    uintptr_t al = (uintptr_t)features_rest | (uintptr_t)rotation;
+    for (int t = 0; t < 6; t++) al |= (uintptr_t)ad.m[t] | (uintptr_t)ad.v[t];
+    if (al & 15) return GSR_EINVAL;  // 16-byte accesses on the moments and the _features_rest block
+    const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
+    const int aa = gsr_antialiasing_mode();
+    if (B == 1 && tanfov0) {  // one camera: the leaner kernel without accumulators
+        if constexpr (std::is_same<SRC, GradSums>::value) {
+            GSR_DISPATCH_DEG_AA(sh_degree, aa,
+                             hipLaunchKernelGGL((preprocess_backward_adam_sums_kernel<DEG, AA>), grid, block, 0,
+                                                reinterpret_cast<hipStream_t>(stream), P, xyz, scaling, scale_modifier,
+                                                rotation, features_dc, features_rest, opacity, cams, cams + 16,
+                                                cams + 32, width, height, tanfov0[0], tanfov0[1], radii, cov3D, clamped,
+                                                src, ad));
+        } else {
+            GSR_DISPATCH_DEG_AA(sh_degree, aa,
+                             hipLaunchKernelGGL((preprocess_backward_adam_kernel<DEG, AA>), grid, block, 0,
+                                                reinterpret_cast<hipStream_t>(stream), P, xyz, scaling, scale_modifier,
+                                                rotation, features_dc, features_rest, opacity, cams, cams + 16,
+                                                cams + 32, width, height, tanfov0[0], tanfov0[1], radii, cov3D, clamped,
+                                                src.means2D, src.conic_opacity, src.rgb, src.gstride, ad));
+        }
+        GSR_LAUNCH_CHECK();
+        return 0;
+    }
+    if constexpr (std::is_same<SRC, GradSums>::value) {
+        GSR_DISPATCH_DEG_AA(sh_degree, aa,
+                         hipLaunchKernelGGL((preprocess_backward_adam_batched_sums_kernel<DEG, AA>), grid, block, 0,
+                                            reinterpret_cast<hipStream_t>(stream), P, B, xyz, scaling, scale_modifier,
+                                            rotation, features_dc, features_rest, opacity, cams, width, height, radii,
+                                            cov3D, clamped, src, ad));
+    } else {
+        GSR_DISPATCH_DEG_AA(sh_degree, aa,
+                         hipLaunchKernelGGL((preprocess_backward_adam_batched_kernel<DEG, AA>), grid, block, 0,
+                                            reinterpret_cast<hipStream_t>(stream), P, B, xyz, scaling, scale_modifier,
+                                            rotation, features_dc, features_rest, opacity, cams, width, height, radii,
+                                            cov3D, clamped, src.means2D, src.conic_opacity, src.rgb, src.gstride, ad));
+    }
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
 // K11 for a batch of cameras fused with the optimizer step of the six tensors it differentiates (see K11Adam):
 // xyz .. opacity are read AND updated in place, exp_avgs / exp_avg_sqs are the moments in the tensor order
 // xyz, scaling, rotation, features_dc, features_rest, opacity; lrs .. steps as in gsr_adam_step_multi.  tanfov0: HOST
@@ -2132,28 +2371,37 @@ extern "C" int gsr_preprocess_backward_adam_raw_batched_dyn(
                            dL_dmeans2D, dL_dconic_opacity, dL_drgb},
                       exp_avgs, exp_avg_sqs, lrs, beta1s, beta2s, epss, steps, grad_scale, dyn_dev, skip_flag_dev))
         return GSR_EINVAL;
-    uintptr_t al = (uintptr_t)features_rest | (uintptr_t)rotation;
-    for (int t = 0; t < 6; t++) al |= (uintptr_t)ad.m[t] | (uintptr_t)ad.v[t];
-    if (al & 15) return GSR_EINVAL;  // 16-byte accesses on the moments and the _features_rest block
-    const dim3 grid(gsr_div_up(P, K11_BLOCK)), block(K11_BLOCK);
-    const int aa = gsr_antialiasing_mode();
-    if (B == 1 && tanfov0) {  // one camera: the leaner kernel without accumulators
-        GSR_DISPATCH_DEG_AA(sh_degree, aa,
-                         hipLaunchKernelGGL((preprocess_backward_adam_kernel<DEG, AA>), grid, block, 0,
-                                            reinterpret_cast<hipStream_t>(stream), P, xyz, scaling, scale_modifier,
-                                            rotation, features_dc, features_rest, opacity, cams, cams + 16, cams + 32,
-                                            width, height, tanfov0[0], tanfov0[1], radii, cov3D, clamped, dL_dmeans2D,
-                                            dL_dconic_opacity, dL_drgb, grad_row_stride, ad));
-        GSR_LAUNCH_CHECK();
-        return 0;
+    return k11_adam_launch(P, B, sh_degree, xyz, scaling, scale_modifier, rotation, features_dc, features_rest, opacity,
+                           cams, width, height, radii, cov3D, clamped,
+                           GradRecord{dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride}, ad, tanfov0, stream);
+}
+
+// The same launch with K10's fp64 sums and row flags as the gradient source (GradSums above; include/gsraster.h):
+// acc64[c] / touched[c] are camera c's [P,9] sums and [P] flags, HOST tables of B <= 8 device pointers.
+extern "C" int gsr_preprocess_backward_adam_raw_batched_sums(
+    int P, int B, int sh_degree, int sh_coeffs, float *xyz, float *scaling, float scale_modifier, float *rotation,
+    float *features_dc, float *features_rest, float *opacity, const float *cams, int width, int height,
+    const int32_t *radii, const float *cov3D, const uint8_t *clamped, const double *const *acc64,
+    const uint8_t *const *touched, float *const *exp_avgs, float *const *exp_avg_sqs, const double *lrs,
+    const double *beta1s, const double *beta2s, const double *epss, const int64_t *steps, float grad_scale,
+    const float *tanfov0, const float *dyn_dev, const uint32_t *skip_flag_dev, gsr_stream_t stream) {
+    if (P < 0 || B < 1 || B > K11_SUMS_CAMS || sh_degree < 0 || sh_degree > 3 || sh_coeffs != 16 || width <= 0 ||
+        height <= 0)
+        return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!acc64 || !touched) return GSR_EINVAL;
+    GradSums src{};
+    for (int c = 0; c < K11_SUMS_CAMS; c++) {  // (the slots past B repeat the last camera: never read, never NULL)
+        src.acc[c] = acc64[c < B ? c : B - 1];
+        src.flags[c] = touched[c < B ? c : B - 1];
+        if (!src.acc[c] || !src.flags[c] || ((uintptr_t)src.acc[c] & 7)) return GSR_EINVAL;
     }
-    GSR_DISPATCH_DEG_AA(sh_degree, aa,
-                     hipLaunchKernelGGL((preprocess_backward_adam_batched_kernel<DEG, AA>), grid, block, 0,
-                                        reinterpret_cast<hipStream_t>(stream), P, B, xyz, scaling, scale_modifier,
-                                        rotation, features_dc, features_rest, opacity, cams, width, height, radii,
-                                        cov3D, clamped, dL_dmeans2D, dL_dconic_opacity, dL_drgb, grad_row_stride, ad));
-    GSR_LAUNCH_CHECK();
-    return 0;
+    K11Adam ad{};
+    if (k11_adam_fill(ad, {xyz, scaling, rotation, features_dc, features_rest, opacity, cams, radii, cov3D, clamped},
+                      exp_avgs, exp_avg_sqs, lrs, beta1s, beta2s, epss, steps, grad_scale, dyn_dev, skip_flag_dev))
+        return GSR_EINVAL;
+    return k11_adam_launch(P, B, sh_degree, xyz, scaling, scale_modifier, rotation, features_dc, features_rest, opacity,
+                           cams, width, height, radii, cov3D, clamped, src, ad, tanfov0, stream);
 }
 
 // The sparse (lazy) form of the fused launch: see the kernels above and include/gsraster.h.

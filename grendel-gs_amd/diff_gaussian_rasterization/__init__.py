@@ -22,6 +22,7 @@ from typing import NamedTuple
 
 import torch
 import torch.nn as nn
+import torch.utils._pytree
 
 from . import _lib
 from ._lib import check, lib
@@ -595,6 +596,149 @@ def _batched_record(grads, B, P):
     return base.view(B * P, 9)
 
 
+# ---- deferred rounding: K10's fp64 sums and row flags handed to the fused K11 + Adam launch as they are ----------
+# (include/gsraster.h: gsr_render_backward_sums, gsr_render_record_materialize, gsr_set_deferred_rounding)
+# The render op's backward normally ends with a launch that rounds the rows K10 touched into the fp32 record, whose
+# column views are the gradients of means2D / rgb / conic_opacity.  When the only reader of those gradients is the
+# fused K11 + Adam launch of the same step, that launch reads the sums and flags itself and the rounding launch and
+# most of the 67 bytes K11 loads per row and camera are work nobody needs.
+#   armed    by the caller of the render op, per view: cuda_args["_gsr_defer_record"] (the gaussian_renderer mirror sets
+#            it for a training view at world size 1 without pose gradients and without the inverse-depth map, in a
+#            batch of at most DEFER_MAX_CAMERAS views: a larger one ends in the record path anyway), and only
+#            when the switch is on, a FusedAdam(fuse_backward=True) that is not sparse is the sink, nothing is being
+#            captured and the flags exist.  A hipGraph capture is never armed: the captured body keeps today's launches.
+#   record   the views the backward returns are the same tensors as ever, but their memory holds the forward's zeros
+#            until materialize() has run; the _DeferredRecord of the view travels in _DEFERRED under the address of the
+#            render op's means2D input, where the projection op's backward -- the next node -- picks it up.
+#   readers  K11's node checks that each gradient it received IS the record's view (address, shape, strides); then
+#            the sums go to the fused launch.  Anything else first runs materialize(): a missing gradient, a pose
+#            gradient (K11c reads the record), a sink that declines, the sparse update, a materialized pending
+#            backward.  `.grad` of means2D as the mirror keeps it is a lazy_record_view: the first use materializes.
+#            A gradient that is neither None nor the view means autograd has already ADDED something to unrounded
+#            memory: that raises.
+DEFER_MAX_CAMERAS = 8  # cameras one gsr_preprocess_backward_adam_raw_batched_sums launch takes (include/gsraster.h)
+_DEFERRED = {}  # data_ptr of the render op's means2D input -> _DeferredRecord, until the projection backward pops it
+# counts since import: render backwards that left the rounding out, records rounded afterwards after all, fused launches
+# that read sums and flags (camera-launches: a batch of B counts B)
+deferred_rounding_stats = {"deferred": 0, "materialized": 0, "fused_from_sums": 0}
+
+
+def set_deferred_rounding(mode):
+    """"env" (GSR_DEFER_ROUNDING, default on), True / "on", False / "off": whether an armed render backward leaves the
+    rounding of K10's record to the fused K11 + Adam launch (include/gsraster.h: gsr_set_deferred_rounding)"""
+    code = {"env": -1, True: 1, "on": 1, False: 0, "off": 0}.get(mode)
+    if code is None:
+        raise ValueError('set_deferred_rounding: mode must be "env", True / "on" or False / "off"')
+    check(lib.gsr_set_deferred_rounding(code), "gsr_set_deferred_rounding")
+
+
+def deferred_rounding():
+    return bool(lib.gsr_deferred_rounding())
+
+
+def _defer_armed(cuda_args, P, have_flags):
+    """forward of the render op: may this view's backward leave the rounding out?"""
+    if not (isinstance(cuda_args, dict) and cuda_args.get("_gsr_defer_record")) or not have_flags or P < 2:
+        return False
+    if _CAPTURE[0] is not None or not deferred_rounding():
+        return False
+    sink = deferred_backward_sink()
+    return sink is not None and bool(getattr(sink, "fuse_backward", False)) and not getattr(sink, "sparse", False)
+
+
+class _DeferredRecord:
+    """one view's record whose rounding has been left out: (record, fp64 sums, row flags) and the stream K10 ran on"""
+
+    def __init__(self, record, acc64, touched, stream):
+        self.record, self.acc64, self.touched, self.stream = record, acc64, touched, stream
+        self.materialized = False
+        deferred_rounding_stats["deferred"] += 1
+
+    def is_view(self, g, off, cols):
+        """g IS columns off : off + cols of the record (same memory, shape and strides)"""
+        r = self.record
+        return g is not None and g.dtype == torch.float32 and tuple(g.shape) == (r.shape[0], cols) and \
+            g.stride() == (9, 1) and g.data_ptr() == r.data_ptr() + 4 * off
+
+    def materialize(self):
+        """run the rounding that was left out, once, on the current stream behind K10's"""
+        if self.materialized:
+            return
+        self.materialized = True
+        deferred_rounding_stats["materialized"] += 1
+        r = self.record
+        with _on(r.device):
+            if self.stream is not None:
+                cur = current_stream(r.device)
+                if cur != self.stream:
+                    cur.wait_stream(self.stream)
+            check(lib.gsr_render_record_materialize(r.shape[0], _ptr(self.acc64), _ptr(self.touched), _ptr(r), 1,
+                                                    _stream()), "gsr_render_record_materialize")
+
+
+_DEFERRED_MAX = 16  # pending records the table holds: twice the cameras one sums launch takes
+
+
+def _register_deferred(key, entry):
+    """file a record for the projection backward.  The table is bounded; the record that has to leave it (a view whose
+    projection backward never ran, or a batch of more views than the table holds) is rounded on its way out, so a
+    record nobody can find any more is a complete one"""
+    while len(_DEFERRED) >= _DEFERRED_MAX:
+        _DEFERRED.pop(next(iter(_DEFERRED))).materialize()
+    _DEFERRED[key] = entry
+
+
+def _deferred_of(g):
+    """the pending _DeferredRecord whose record tensor g is a column view of, or None"""
+    if g is None or not _DEFERRED:
+        return None
+    p = g.data_ptr()
+    for e in _DEFERRED.values():
+        lo = e.record.data_ptr()
+        if lo <= p < lo + 36 * e.record.shape[0] and not e.materialized:
+            return e
+    return None
+
+
+def _take_deferred(key, g):
+    """the projection backward's lookup: the record filed under the address of its means2D output, else the one whose
+    memory the gradient it received lies in; the entry leaves _DEFERRED"""
+    e = _DEFERRED.pop(key, None)
+    if e is None:
+        e = _deferred_of(g)
+        if e is not None:
+            for k in [k for k, v in _DEFERRED.items() if v is e]:
+                del _DEFERRED[k]
+    return e
+
+
+class _LazyRecordView(torch.Tensor):
+    """a view of a record whose rounding is deferred: whatever is done with it first materializes the record"""
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        for t in torch.utils._pytree.tree_leaves((args, kwargs)):  # positional, keyword (`other=`, `out=`), nested
+            e = getattr(t, "_gsr_deferred", None) if isinstance(t, _LazyRecordView) else None
+            if e is not None:
+                e.materialize()
+        with torch._C.DisableTorchFunctionSubclass():
+            out = func(*args, **(kwargs or {}))
+        return out.as_subclass(torch.Tensor) if isinstance(out, _LazyRecordView) else out
+
+
+def lazy_record_view(g):
+    """g itself, or -- when g is a view of a record whose rounding is deferred -- the same view as a tensor that
+    materializes the record on first use.  For whoever keeps such a gradient to read it later (`means2D.grad`)."""
+    e = _deferred_of(g)
+    return g if e is None else _lazy_view(g, e)
+
+
+def _lazy_view(g, entry):
+    v = torch.Tensor._make_subclass(_LazyRecordView, g)
+    v._gsr_deferred = entry
+    return v
+
+
 # ---- deferred K11: the projection backward handed to an optimizer that fuses it with its step -------------------
 # A sink (fused_optim.FusedAdam(fuse_backward=True)) registers itself here.  When the six raw parameters of a
 # _PreprocessGaussiansRawBatched node are exactly the tensors the sink optimizes, the node's backward does not launch
@@ -620,7 +764,11 @@ def deferred_backward_sink():
 class PendingProjectionBackward:
     """K11's inputs of one backward pass, alive until the optimizer's step"""
 
-    def __init__(self, params, cams, radii, cov3D, clamped, g_means2D, g_conic_opacity, g_rgb, gstride, meta, tanfov0):
+    def __init__(self, params, cams, radii, cov3D, clamped, g_means2D, g_conic_opacity, g_rgb, gstride, meta, tanfov0,
+                 deferred=None):
+        # deferred: the cameras' _DeferredRecord when the three gradients ARE views of records whose rounding was left
+        # out (B == 1: the views themselves; B > 1: g_* are None until materialize() has assembled them)
+        self.deferred = deferred
         self.params = params  # xyz, scaling, rotation, features_dc, features_rest, opacity (the saved inputs)
         self.versions = tuple(t._version for t in params)
         self.cams, self.radii, self.cov3D, self.clamped = cams, radii, cov3D, clamped
@@ -635,9 +783,26 @@ class PendingProjectionBackward:
             if cur != self.stream:
                 cur.wait_stream(self.stream)
 
+    def round_records(self):
+        """the gradients as fp32 tensors: runs the rounding that was left out (deferred) and, for a batch, gathers the
+        cameras' records into the dense [B,P,.] blocks the kernels read"""
+        entries, self.deferred = self.deferred, None
+        if entries is None:
+            return
+        self.join_stream()
+        for e in entries:
+            e.materialize()
+        if len(entries) > 1:
+            recs = [e.record for e in entries]
+            self.g_means2D = torch.stack([r[:, 0:2] for r in recs])
+            self.g_rgb = torch.stack([r[:, 2:5] for r in recs])
+            self.g_conic_opacity = torch.stack([r[:, 5:9] for r in recs])
+            self.gstride = 0
+
     def materialize(self):
         """-> the six gradients, computed by the plain K11 (what the node's backward would have returned)"""
         self.join_stream()
+        self.round_records()
         return _launch_k11(self.params, self.cams, self.radii, self.cov3D, self.clamped, self.g_means2D,
                            self.g_conic_opacity, self.g_rgb, self.gstride, self.meta, self.tanfov0, None)
 
@@ -651,6 +816,9 @@ class PendingProjectionBackward:
         that receives the number of active rows live in `cache` ("sparse_ws", "num_active"), grow-only and re-made when
         P changes, so a captured iteration allocates nothing new on replay."""
         self.join_stream()
+        if self.deferred is not None and (sparse or not deferred_rounding()):
+            self.round_records()  # (the sparse launch classifies the rows from the record; the switch went off)
+        sums = self.deferred
         xyz, scaling, rotation, f_dc, f_rest, opacity = self.params
         deg, smod, W, H, M = self.meta[:5]
         P, B = xyz.shape[0], self.cams.shape[0]
@@ -668,12 +836,20 @@ class PendingProjectionBackward:
         # captured launch: lr / bias corrections come from the capture's device block at execution time, and the launch
         # is a no-op when a capacity check of the same replay has raised the flag word
         dyn, flag = (_ptr(cap_ctx.dyn), _ptr(cap_ctx.flag)) if cap_ctx is not None else (None, None)
+        if sums is not None:  # K10's sums and flags of each camera in place of the record's columns
+            PB = ctypes.c_void_p * B
+            grad_args = [PB(*[e.acc64.data_ptr() for e in sums]), PB(*[e.touched.data_ptr() for e in sums])]
+        else:
+            grad_args = [_ptr(self.g_means2D), _ptr(self.g_conic_opacity), _ptr(self.g_rgb), self.gstride]
         args = [P, B, deg, M, _ptr(xyz), _ptr(scaling), smod, _ptr(rotation), _ptr(f_dc), _ptr(f_rest), _ptr(opacity),
-                _ptr(self.cams), W, H, _ptr(self.radii), _ptr(self.cov3D), _ptr(self.clamped), _ptr(self.g_means2D),
-                _ptr(self.g_conic_opacity), _ptr(self.g_rgb), self.gstride, tabs[1], tabs[2],
-                None if cap_ctx is not None else D(*lrs), tabs[3], tabs[4], tabs[5],
+                _ptr(self.cams), W, H, _ptr(self.radii), _ptr(self.cov3D), _ptr(self.clamped)] + grad_args + \
+               [tabs[1], tabs[2], None if cap_ctx is not None else D(*lrs), tabs[3], tabs[4], tabs[5],
                 None if cap_ctx is not None else I64(*steps), float(grad_scale)]
-        if sparse:
+        if sums is not None:
+            name, timed = "gsr_preprocess_backward_adam_raw_batched_sums", "preprocess_backward_adam"
+            args += [tf, dyn, flag]
+            deferred_rounding_stats["fused_from_sums"] += B
+        elif sparse:
             if cache is None:
                 cache = {}
             need = int(lib.gsr_sparse_step_workspace_bytes(P))
@@ -765,6 +941,7 @@ class _PreprocessGaussiansRawBatched(torch.autograd.Function):
                 _ptr(means2D), _ptr(depths), _ptr(radii), _ptr(cov3D), _ptr(conic_opacity), _ptr(rgb), _ptr(clamped),
                 _stream()), "gsr_preprocess_forward_raw_batched")
         ctx.meta = (int(sh_degree), float(scale_modifier), int(width), int(height), M, aa)
+        ctx.m2_ptr = means2D.data_ptr()  # (deferred rounding: the key a render op's backward files its record under)
         ctx.save_for_backward(xyz, scaling, rotation, features_dc, features_rest, opacity, cams, radii, cov3D, clamped)
         # per-camera outputs are separate autograd outputs (dense views of the camera-major buffers): a caller
         # that uses camera k alone gets its gradient straight back, without the zeros + copy of a select-backward
@@ -799,24 +976,53 @@ class _PreprocessGaussiansRawBatched(torch.autograd.Function):
                     out[k].copy_(g)
             return out
 
-        if B == 1:  # K10's [P,9] record (or any common-stride column views) goes straight into the kernel
+        params = (xyz, scaling, rotation, f_dc, f_rest, opacity)
+        # records whose rounding the render ops' backward left out (deferred rounding, above): the sums go to the fused
+        # launch when every gradient IS its record's view and the sink takes the backward; else they are rounded now
+        entries = [_take_deferred(ctx.m2_ptr + 8 * k * P, grads[5 * k]) if _DEFERRED else None for k in range(B)]
+        deferred = None
+        if any(e is not None for e in entries):
+            for k, e in enumerate(entries):
+                for col, (off, cols) in enumerate(((0, 2), (2, 3), (5, 4))):
+                    g = grads[5 * k + col]
+                    if e is not None and g is not None and not e.is_view(g, off, cols):
+                        raise RuntimeError(
+                            "diff_gaussian_rasterization: the rounding of a view's gradient record was deferred, but "
+                            "another gradient reached means2D / rgb / conic_opacity of that view and autograd has added "
+                            "it to the unrounded record; call set_deferred_rounding(False) for such a graph")
+            whole = all(e is not None and all(grads[5 * k + c] is not None for c in range(3))
+                        for k, e in enumerate(entries))
+            sink = deferred_backward_sink()
+            if whole and not ctx.needs_input_grad[6] and B <= DEFER_MAX_CAMERAS and M == 16 and sink is not None and \
+                    not getattr(sink, "sparse", False) and deferred_rounding() and sink.accepts(params):
+                deferred = entries
+            else:
+                for e in entries:
+                    if e is not None:
+                        e.materialize()
+        if deferred is not None and B > 1:
+            g_means2D = g_rgb = g_conic_opacity = None  # (PendingProjectionBackward.round_records assembles them)
+            gstride = 0
+        elif B == 1:  # K10's [P,9] record (or any common-stride column views) goes straight into the kernel
             g_means2D, g_rgb, g_conic_opacity, gstride = _grad_triple(grads[0], grads[1], grads[2], P, dev)
+            if deferred is not None:  # (whoever takes these views instead of the sums has the record rounded first)
+                g_means2D, g_rgb, g_conic_opacity = (_lazy_view(g, deferred[0])
+                                                     for g in (g_means2D, g_rgb, g_conic_opacity))
         else:
             rec = _batched_record(grads, B, P)
             if rec is not None:  # column views of ONE [B,P,9] record (the exchange's backward): read through the stride
                 g_means2D, g_rgb, g_conic_opacity, gstride = rec[:, 0:2], rec[:, 2:5], rec[:, 5:9], 9
             else:
                 g_means2D, g_rgb, g_conic_opacity, gstride = assemble(0, 2), assemble(1, 3), assemble(2, 4), 0
-        params = (xyz, scaling, rotation, f_dc, f_rest, opacity)
         d_cams = None
         if ctx.needs_input_grad[6]:  # pose refinement: dL/dcams [B,40], before K11 is launched or handed on
             d_cams = preprocess_backward_cameras(xyz, (f_dc, f_rest), cams, W, H, deg, radii, cov3D, clamped,
                                                  g_means2D, g_conic_opacity, g_rgb, gstride)
         sink = deferred_backward_sink()
-        if sink is not None and M == 16 and sink.accepts(params):
+        if deferred is not None or (sink is not None and M == 16 and sink.accepts(params)):
             # K11 runs inside the optimizer's step (fused with Adam); `.grad` of the six parameters stays None
             sink.offer(PendingProjectionBackward(params, cams, radii, cov3D, clamped, g_means2D, g_conic_opacity,
-                                                 g_rgb, gstride, ctx.meta, ctx.tanfov0))
+                                                 g_rgb, gstride, ctx.meta, ctx.tanfov0, deferred))
             return (None,) * 6 + (d_cams,) + (None,) * 6
         return _launch_k11(params, cams, radii, cov3D, clamped, g_means2D, g_conic_opacity, g_rgb, gstride, ctx.meta,
                            ctx.tanfov0, ctx.cuda_args_list) + (d_cams,) + (None,) * 6
@@ -1255,6 +1461,11 @@ class _RenderGaussians(torch.autograd.Function):
             # the forward left
             record = acc64 = touched = None
             zero_buf, zero_bytes = None, 0
+            # deferred rounding (see _DEFERRED): the backward files sums and flags for the fused K11 + Adam launch.  The
+            # buffers are the same, record included: leaving its 36 P bytes out of K8's clear measured nothing
+            # (profiles/k10_k11_handoff_ab.txt), and a record nobody rounded reads as zeros, not as garbage
+            ctx.defer = all(ctx.needs_input_grad[:3]) and _ZERO_IN_FORWARD[0] and \
+                _defer_armed(cuda_args, P, _TOUCHED_ROWS[0])
             if any(ctx.needs_input_grad[:3]) and P > 0 and _ZERO_IN_FORWARD[0]:
                 if _TOUCHED_ROWS[0]:
                     zero_bytes = 108 * P + ((P + 15) & ~15)
@@ -1361,14 +1572,28 @@ class _RenderGaussians(torch.autograd.Function):
             cap_stats = ctx.cuda_args.get("stats_collector") if isinstance(ctx.cuda_args, dict) else None
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("bwd0", id(cap_stats))
+            defer = record_is_zero and getattr(ctx, "defer", False)
             with kernel_timer.range("composite_backward", P=P, D=ctx.num_rendered, **ctx.px_meta), \
                     zhx_range(ctx.cuda_args, "b10 render time"):
                 seg_ws, seg_bytes, row_lo, row_hi = ctx.seg
-                check(lib.gsr_render_backward(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
-                                              _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(final_T),
-                                              _ptr(n_contrib), _ptr(g_out), _ptr(record), _ptr(out_img),
-                                              _ptr(seg_ws), seg_bytes, row_lo, row_hi, 1 if record_is_zero else 0,
-                                              _ptr(acc64), _ptr(touched), _stream()), "gsr_render_backward")
+                if defer:  # K10 alone: the sums and flags are the result
+                    check(lib.gsr_render_backward_sums(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                                                       _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg),
+                                                       _ptr(final_T), _ptr(n_contrib), _ptr(g_out), _ptr(out_img),
+                                                       _ptr(seg_ws), seg_bytes, row_lo, row_hi, _ptr(acc64),
+                                                       _ptr(touched), _stream()), "gsr_render_backward_sums")
+                    entry = _DeferredRecord(record, acc64, touched, current_stream(dev))
+                    if _defer_armed(ctx.cuda_args, P, True):
+                        _register_deferred(means2D.data_ptr(), entry)
+                    else:  # (the switch or the sink changed since the forward)
+                        entry.materialize()
+                else:
+                    check(lib.gsr_render_backward(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                                                  _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(final_T),
+                                                  _ptr(n_contrib), _ptr(g_out), _ptr(record), _ptr(out_img),
+                                                  _ptr(seg_ws), seg_bytes, row_lo, row_hi,
+                                                  1 if record_is_zero else 0, _ptr(acc64), _ptr(touched), _stream()),
+                          "gsr_render_backward")
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("bwd1", id(cap_stats))
             if timing != "off":

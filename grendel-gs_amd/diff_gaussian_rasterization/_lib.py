@@ -115,6 +115,9 @@ SIGNATURES = {
                                             [c_void_p] * 7),
     "gsr_preprocess_backward_adam_raw_batched": (c_int, _K11_ADAM_PREFIX + [c_void_p, c_void_p]),
     "gsr_preprocess_backward_adam_raw_batched_dyn": (c_int, _K11_ADAM_PREFIX + [c_void_p] * 4),
+    "gsr_preprocess_backward_adam_raw_batched_sums": (c_int, [c_int] * 4 + [c_void_p, c_void_p, c_float] +
+                                                      [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 12 + [c_float] +
+                                                      [c_void_p] * 4),
     "gsr_sparse_step_workspace_bytes": (c_size_t, [c_int]),
     "gsr_preprocess_backward_adam_raw_batched_sparse": (c_int, _K11_ADAM_PREFIX + [c_void_p, c_void_p, c_void_p,
                                                                                     c_size_t, c_void_p, c_void_p,
@@ -139,6 +142,11 @@ SIGNATURES = {
                                                                            c_void_p]),
     "gsr_render_backward": (c_int, [c_int, c_int, c_int] + [c_void_p] * 13 + [c_size_t, c_int, c_int, c_int, c_void_p,
                                                                             c_void_p, c_void_p]),
+    "gsr_render_backward_sums": (c_int, [c_int, c_int, c_int] + [c_void_p] * 12 + [c_size_t, c_int, c_int, c_void_p,
+                                                                                 c_void_p, c_void_p]),
+    "gsr_render_record_materialize": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gsr_set_deferred_rounding": (c_int, [c_int]),
+    "gsr_deferred_rounding": (c_int, []),
     "gsr_composite_walked": (c_int, [ctypes.POINTER(ctypes.c_ulonglong), c_int]),
     "gsr_render_contrib": (c_int, [c_int, c_int, c_int] + [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 4),
     "gsr_contrib_merge_rows": (c_int, [c_int64] + [c_void_p] * 8),

@@ -17,7 +17,11 @@ as reset_opacity -- materialized for the tensors that are still current), `zero_
 backward before the step materializes both.  What changes: code that READS `.grad` of the raw parameters between
 backward and step sees None -- the reference's own `param.grad /= bsz` loop (train_internal.py:319-324) would be such a
 reader and silently do nothing, so the scale has to be passed as `grad_scale` (constructor or step()), as bench.py
-does.  `means2D.grad` (densification statistics) is unaffected: it comes from K10, not K11.
+does.  `means2D.grad` (densification statistics) is unaffected: it comes from K10, not K11.  (Where this optimizer is
+the only reader of K10's gradient record -- a training view of the gaussian_renderer mirror at world size 1 -- the fused
+launch reads K10's fp64 sums and row flags and the record is rounded only if somebody else reads it, `means2D.grad`
+included: diff_gaussian_rasterization, "deferred rounding"; `GSR_DEFER_ROUNDING=0` keeps the rounding launch.  Not
+with `sparse`, whose classification reads the record.)
 
 `sparse=True` (opt-in, needs fuse_backward; default from the environment variable GSR_SPARSE_ADAM, read at construction:
 "" and "0" mean off) makes the fused launch a SPARSE one (include/gsraster.h:

@@ -43,13 +43,16 @@ def _keep_grad_view(t):
     reads `means2D.grad[:, :2]` (scene/gaussian_model.py:1046-1052) -- without the copy: retain_grad() CLONES the
     incoming gradient, which here is a column view of K10's [P,9] record (a strided 8-of-36-byte read: 9 us per
     iteration at 1 M Gaussians, 51 us at 6 M).  Nobody writes the record after K10 (K11 and the mirror exchange read
-    it), so the view itself is kept as `.grad`.  Accumulates like retain_grad() if the tensor is used twice."""
+    it), so the view itself is kept as `.grad`.  Accumulates like retain_grad() if the tensor is used twice.
+    When the record's rounding is deferred to the fused K11 + Adam launch (diff_gaussian_rasterization: deferred
+    rounding) the view is kept as a lazy_record_view: whoever reads it first has the record rounded then."""
     import weakref
     ref, first = weakref.ref(t), [True]
 
     def hook(g):
         x = ref()
         if x is not None:  # (reading .grad of a non-leaf that has none warns: the first call is remembered instead)
+            g = _dgr.lazy_record_view(g)
             x.grad = g if first[0] else x.grad + g
             first[0] = False
 
@@ -879,6 +882,12 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
         redistributed = tuple([p[c] for p in params] for c in range(5))
         sizes = [[[p[0].shape[0] for p in params]]]
         _fill(pkg, redistributed, sizes)
+        if mode == "train" and not pose_grad and not _INVDEPTH[0] and len(cuda_args_list) <= _dgr.DEFER_MAX_CAMERAS:
+            # nothing but the projection backward reads these views' gradient records (no exchange, no K11c, no depth
+            # path; `.grad` of means2D is kept lazily, above): their rounding may be left to the fused K11 + Adam launch
+            # (which takes that many cameras: a larger batch keeps the rounding launches)
+            for ca in cuda_args_list:
+                ca["_gsr_defer_record"] = True
         if _INVDEPTH[0]:
             pkg["_invdepth_xyz"] = raw[0]  # (the depth path of the inverse-depth map: dL/ddepth -> dL/dxyz)
         return pkg

@@ -361,6 +361,26 @@ int gsr_render_backward(int P, int width, int height, const int32_t *ranges, con
                         const int32_t *n_contrib, const float *dL_dpixels, float *dL_record, const float *out_color,
                         void *seg_ws, size_t seg_bytes, int row_lo, int row_hi, int record_is_zero, double *acc64,
                         uint8_t *touched, gsr_stream_t stream);
+/* Deferred rounding.  gsr_render_backward_sums is gsr_render_backward without its last launch: K10 adds into acc64 and
+ * sets touched[], nothing is rounded and no record is written.  Both must have been cleared by the forward (zero_ptr);
+ * the caller may then leave the record's 36 P bytes out of the cleared range (diff_gaussian_rasterization does not: it
+ * measured nothing, and a record that was cleared reads as zeros until it is rounded).  The sums and flags are what gsr_preprocess_backward_adam_raw_batched_sums (below) reads in place of a record.
+ * gsr_render_record_materialize runs the rounding left out, on any stream ordered behind that backward: the record is
+ * then bit for bit what gsr_render_backward would have written (record_is_zero == 0: the record was not cleared, the
+ * rows without a flag are written too), so deferring is never a one-way door.
+ * gsr_set_deferred_rounding(mode): the process-wide switch a caller that owns the record consults before it defers
+ * (gsr_deferred_rounding() -> 0 | 1); -1 = the environment's GSR_DEFER_ROUNDING (0 | 1, default 1), 0 off, 1 on.  The
+ * library itself never defers: the two entry points above do what they say whatever the switch. */
+int gsr_render_backward_sums(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                             const float *means2D, const float *conic_opacity, const float *rgb,
+                             const uint8_t *compute_locally, const float *bg, const float *final_T,
+                             const int32_t *n_contrib, const float *dL_dpixels, const float *out_color, void *seg_ws,
+                             size_t seg_bytes, int row_lo, int row_hi, double *acc64, uint8_t *touched,
+                             gsr_stream_t stream);
+int gsr_render_record_materialize(int P, const double *acc64, const uint8_t *touched, float *dL_record,
+                                  int record_is_zero, gsr_stream_t stream);
+int gsr_set_deferred_rounding(int mode);
+int gsr_deferred_rounding(void);
 /* Measurement aid (bench.py's roofline leg; the reference has nothing to bind here): list entries the composite kernels
  * WALKED since the last reset, summed over launches -- out2[0] K8, out2[1] K10; per tile the entries its longest-walking
  * quadrant goes through (K8: up to the chunk in which the last pixel saturates; K10: the largest n_contrib of the
@@ -897,6 +917,25 @@ int gsr_preprocess_backward_adam_raw_batched_dyn(int P, int B, int sh_degree, in
                                                  const double *beta2s, const double *epss, const int64_t *steps,
                                                  float grad_scale, const float *tanfov0, const float *dyn_dev,
                                                  const uint32_t *skip_flag_dev, gsr_stream_t stream);
+/* The same dense launch reading K10's fp64 sums and row flags (gsr_render_backward_sums) where the others read a
+ * record: acc64 / touched are HOST arrays of B <= 8 device pointers, camera c's [P,9] sums and [P] flags (GSR_EINVAL
+ * for more cameras, a null entry or sums that are not 8-byte aligned).  A row whose flag is set in camera c and whose
+ * radius there is > 0 has its nine sums converted with one (float) each -- means2D 0:2, rgb 2:5, conic_opacity 5:9, the
+ * bits gsr_render_record_materialize stores -- and is differentiated as above.  A row whose flag is clear contributes
+ * nothing for that camera, exactly as a culled one: its record row would be zeros.  Its sums, cov3D and clamp flags
+ * are not read.  Parameters and second moments come out bit for bit as from the record; a first moment that is an
+ * exact zero may differ in its sign (the zero-gradient path adds +0.0f where K11's arithmetic on zeros could add
+ * -0.0f).  dyn_dev / skip_flag_dev as in _dyn, may be NULL. */
+int gsr_preprocess_backward_adam_raw_batched_sums(int P, int B, int sh_degree, int sh_coeffs, float *xyz, float *scaling,
+                                                  float scale_modifier, float *rotation, float *features_dc,
+                                                  float *features_rest, float *opacity, const float *cams, int width,
+                                                  int height, const int32_t *radii, const float *cov3D,
+                                                  const uint8_t *clamped, const double *const *acc64,
+                                                  const uint8_t *const *touched, float *const *exp_avgs,
+                                                  float *const *exp_avg_sqs, const double *lrs, const double *beta1s,
+                                                  const double *beta2s, const double *epss, const int64_t *steps,
+                                                  float grad_scale, const float *tanfov0, const float *dyn_dev,
+                                                  const uint32_t *skip_flag_dev, gsr_stream_t stream);
 
 /* Sparse Adam: the fused K11 + Adam update over the rows that received a gradient (opt-in; LAZY Adam, not what the
  * reference's dense optimizer does -- so there is no reference call site for this entry point: the dense pair
