@@ -267,4 +267,27 @@ int gsr_depth_backward_means3d(int P, const int32_t *radii, const float *viewmat
                                        reinterpret_cast<hipStream_t>(stream));
 }
 
+int gsr_render_absgrad(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                       const float *means2D, const float *conic_opacity, const float *rgb,
+                       const uint8_t *compute_locally, const float *bg, const float *final_T, const int32_t *n_contrib,
+                       const float *dL_dpixels, int row_lo, int row_hi, float *absgrad, double *acc64,
+                       gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    // (point_list may be NULL: every list can be empty)
+    if (!ranges || !means2D || !conic_opacity || !rgb || !compute_locally || !bg || !final_T || !n_contrib ||
+        !dL_dpixels || !absgrad || !acc64)
+        return GSR_EINVAL;
+    return gsr_launch_composite_absgrad(P, width, height, ranges, point_list, means2D, conic_opacity, rgb,
+                                        compute_locally, bg, final_T, n_contrib, dL_dpixels, row_lo, row_hi, absgrad,
+                                        acc64, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_absgrad_merge_rows(int64_t n, const int32_t *idx, const float *src, float *dst, gsr_stream_t stream) {
+    if (n < 0) return GSR_EINVAL;
+    if (n == 0) return 0;
+    if (!idx || !src || !dst) return GSR_EINVAL;
+    return gsr_launch_absgrad_merge_rows((long long)n, idx, src, dst, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -412,26 +412,37 @@ def redistribute_gaussians(self, destination=None, group=None):
 
 
 # ----------------------------------------------------------------------- statistics / opacity reset
-def add_densification_stats(self, viewspace_point_tensor, update_filter):
+def add_densification_stats(self, viewspace_point_tensor, update_filter, absgrad=None):
     """scene/gaussian_model.py:1046-1052: accumulate |d loss / d means2D| (the op's NDC-scaled gradient) of the
     Gaussians visible in this view.  Same values as the reference's `x[filter] += norm(grad[filter, :2])` for ANY filter,
     without its boolean indexing (a `nonzero` host sync + gather + scatter per statement): the rows outside the filter
-    receive + 0."""
+    receive + 0.
+    `absgrad` (extension of this build, see update_densification_stats): a [P,2] tensor whose norm is accumulated
+    instead of the signed gradient's; `viewspace_point_tensor.grad` is then not read."""
     f = update_filter.view(-1, 1)
-    n = torch.linalg.vector_norm(viewspace_point_tensor.grad[:, :2], dim=-1, keepdim=True)
+    g = viewspace_point_tensor.grad if absgrad is None else absgrad
+    n = torch.linalg.vector_norm(g[:, :2], dim=-1, keepdim=True)
     self.xyz_gradient_accum += torch.where(f, n, torch.zeros((), dtype=n.dtype, device=n.device))
     self.denom += f
 
 
-def update_densification_stats(self, viewspace_point_tensor, radii):
+def update_densification_stats(self, viewspace_point_tensor, radii, absgrad=None):
     """What densification.py:13-25 of the reference does after every backward of the densification phase -- for the
     visible Gaussians (radii > 0): max_radii2D = max(max_radii2D, radii), then add_densification_stats -- WITHOUT the
     boolean indexing (two `nonzero` host syncs and six gather / scatter kernels per camera and iteration: measured 0.54 ms
     of a 1.18 ms step at 10^6 Gaussians).  The mask is implied by the data: an invisible Gaussian has radius 0 (the maximum
     leaves max_radii2D alone, radii are never negative) and a means2D gradient of exactly 0 (K10 never touches its row
     of the zero-initialised record; the mirror exchange scatter-adds into zeros), so the unmasked updates change the
-    same rows by the same amounts, bit for bit; `denom` counts the rows with radius > 0."""
-    g = viewspace_point_tensor.grad
+    same rows by the same amounts, bit for bit; `denom` counts the rows with radius > 0.
+    `absgrad` (extension of this build; None: everything above, bit for bit): the camera's [P,2] absolute screen-space
+    gradient (gaussian_renderer.set_absgrad / collect_absgrad; include/gsraster.h: gsr_render_absgrad) -- its norm
+    replaces the signed gradient's norm in xyz_gradient_accum, `viewspace_point_tensor.grad` is not read, max_radii2D
+    and denom are as before.  The sum of magnitudes is at least the magnitude of the sum, and several times larger on
+    the large Gaussians it is meant to find, so `densify_grad_threshold` NEEDS RETUNING under it (gsplat's default
+    goes from 0.0002 to 0.0008 with absgrad); this project fixes no value."""
+    if absgrad is not None and (absgrad.dim() != 2 or absgrad.shape[0] != radii.shape[0] or absgrad.shape[1] < 2):
+        raise ValueError("update_densification_stats: `absgrad` must be [P, 2] with one row per entry of `radii`")
+    g = viewspace_point_tensor.grad if absgrad is None else absgrad
     if (radii.dtype == torch.int32 and g.dtype == torch.float32 and g.dim() == 2 and g.stride(1) == 1 and
             all(t.dtype == torch.float32 and t.is_contiguous() for t in (self.max_radii2D, self.xyz_gradient_accum,
                                                                          self.denom))):

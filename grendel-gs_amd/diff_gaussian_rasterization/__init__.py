@@ -30,7 +30,7 @@ from ._lib import check, lib
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "_C", "load_image_tiles_by_pos",
            "merge_image_tiles_by_pos", "set_timing_mode", "fused_l1_ssim_band", "fused_band_loss", "fused_band_loss_exposure", "fused_activations", "pack_camera",
            "preprocess_gaussians_raw_batched", "knn_mean_dist2", "group_rows", "gather_rows", "densify_plan", "densify_move", "exchange_need",
-           "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "densify_stats",
+           "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "absgrad_rows", "densify_stats",
            "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing", "image_metrics", "metrics_from_sums"]
 
 BLOCK_X, BLOCK_Y, ONE_DIM_BLOCK_SIZE = 16, 16, 256
@@ -1412,6 +1412,12 @@ class _RenderGaussians(torch.autograd.Function):
         if invd and _CAPTURE[0] is not None:
             raise RuntimeError("diff_gaussian_rasterization: cuda_args['invdepth'] is not available under graph capture "
                                "(the map needs the view's final lists)")
+        # opt-in: the backward launches the absolute-gradient kernel behind K10 (gsr_render_absgrad) and leaves its
+        # [P,2] result in cuda_args.  The pair count stays deferred: the backward runs on final lists
+        ctx.absgrad = bool(cuda_args.get("absgrad")) if isinstance(cuda_args, dict) else False
+        if ctx.absgrad and _CAPTURE[0] is not None:
+            raise RuntimeError("diff_gaussian_rasterization: cuda_args['absgrad'] is not available under graph capture "
+                               "(its result is handed over through cuda_args, outside the captured buffers)")
         with _on(dev):
             if timing != "off":
                 ev0 = torch.cuda.Event(enable_timing=True)
@@ -1594,6 +1600,17 @@ class _RenderGaussians(torch.autograd.Function):
                                                   _ptr(seg_ws), seg_bytes, row_lo, row_hi,
                                                   1 if record_is_zero else 0, _ptr(acc64), _ptr(touched), _stream()),
                           "gsr_render_backward")
+            if getattr(ctx, "absgrad", False):
+                # the same lists, mask, band, final_T, n_contrib and dL/dpixels, behind K10 on the same stream; the
+                # record (rounded or not) is not read
+                absg = torch.empty((P, 2), dtype=torch.float32, device=dev)
+                abs64 = torch.empty((P, 2), dtype=torch.float64, device=dev)
+                with kernel_timer.range("composite_absgrad", P=P):
+                    check(lib.gsr_render_absgrad(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                                                 _ptr(conic_opacity), _ptr(rgb), _ptr(mask), _ptr(bg), _ptr(final_T),
+                                                 _ptr(n_contrib), _ptr(g_out), row_lo, row_hi, _ptr(absg), _ptr(abs64),
+                                                 _stream()), "gsr_render_absgrad")
+                ctx.cuda_args[_ABSGRAD_KEY] = absg
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("bwd1", id(cap_stats))
             if timing != "off":
@@ -1620,6 +1637,7 @@ class _RenderGaussians(torch.autograd.Function):
         return d_means2D, d_conic_opacity, d_rgb, None, None, None, None, None, None
 
 
+_ABSGRAD_KEY = "_gsr_absgrad"  # where _RenderGaussians.backward leaves the [P,2] tensor when cuda_args["absgrad"] is set
 _INVDEPTH_KEY = "_gsr_invdepth"  # what _RenderGaussians leaves in cuda_args when cuda_args["invdepth"] is set
 
 
@@ -2228,6 +2246,26 @@ def scatter_add_rows(idx, src, n_rows, dst=None):
         raise ValueError("dst must be a contiguous fp32 [n_rows, 9] tensor")
     with _on(src.device):
         check(lib.gsr_scatter_add_rows(src.shape[0], _ptr(idx), _ptr(src), _ptr(dst), _stream()), "gsr_scatter_add_rows")
+    return dst
+
+
+def absgrad_rows(idx, src, n_rows, dst=None):
+    """-> dst fp32 [n_rows, 2] with dst[idx[r]] += src[r] (gsr_absgrad_merge_rows: the absolute-gradient rows that came
+    back from another rank; duplicates in idx accumulate, rows with idx[r] < 0 are skipped); `dst`: an existing
+    contiguous [n_rows, 2] tensor to add into (default: a fresh zero tensor)"""
+    src = _f32c(src, "src")
+    if not idx.is_cuda:
+        raise RuntimeError("diff_gaussian_rasterization: `idx` must live on the gfx950 device (no CPU fallback)")
+    if src.dim() != 2 or src.shape[1] != 2 or idx.dtype != torch.int32 or not idx.is_contiguous() or \
+            idx.numel() != src.shape[0]:
+        raise ValueError("src must be [n, 2] fp32 and idx contiguous int32 [n]")
+    if dst is None:
+        dst = torch.zeros((n_rows, 2), dtype=torch.float32, device=src.device)
+    elif tuple(dst.shape) != (n_rows, 2) or dst.dtype != torch.float32 or not dst.is_contiguous():
+        raise ValueError("dst must be a contiguous fp32 [n_rows, 2] tensor")
+    with _on(src.device):
+        check(lib.gsr_absgrad_merge_rows(src.shape[0], _ptr(idx), _ptr(src), _ptr(dst), _stream()),
+              "gsr_absgrad_merge_rows")
     return dst
 
 

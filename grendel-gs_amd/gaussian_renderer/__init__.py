@@ -92,6 +92,8 @@ def get_cuda_args_final(strategy, mode="train"):
     }
     if _INVDEPTH[0]:  # (opt-in: without it the dictionary is the reference's, key for key)
         ca["invdepth"] = True
+    if _ABSGRAD[0]:
+        ca["absgrad"] = True
     return ca
 
 
@@ -113,6 +115,61 @@ def set_invdepth(on):
 
 def get_invdepth():
     return _INVDEPTH[0]
+
+
+# ------------------------------------------------------------------------------ absolute gradients (opt-in)
+_ABSGRAD = [os.environ.get("GSR_ABSGRAD", "0") not in ("", "0")]
+_LAST_ROUTES = [None]  # the latest batch's {camera: (send_idx, send_splits, recv_splits, group)}, kept while _ABSGRAD is set
+
+
+def set_absgrad(on):
+    """True (default False; GSR_ABSGRAD=1 in the environment: True): every camera's backward also computes the ABSOLUTE
+    screen-space gradient of the rows it rendered (AbsGS's homodirectional gradient, gsplat's `absgrad`; include/
+    gsraster.h: gsr_render_absgrad) with a kernel of its own behind K10; collect_absgrad(pkg, strategies) hands it to
+    densification (densification_ops.update_densification_stats(..., absgrad=...)) in the model's rows.  Extension of
+    this build: the reference has one densification signal.  The image, the loss and every gradient are unchanged, and
+    with the switch off nothing changes at all.  While it is on, a batch's exchange runs one all-to-all-v per camera
+    (never one for the whole batch): each camera's route is kept for the return trip."""
+    _ABSGRAD[0] = bool(on)
+
+
+def get_absgrad():
+    return _ABSGRAD[0]
+
+
+def collect_absgrad(pkg, batched_strategies):
+    """-> one fp32 [P_local, 2] tensor per camera: the absolute screen-space gradient of THIS rank's Gaussians, summed
+    over every band that rendered them, in means2D.grad's units.  Call it after the backward of the batch `pkg` was
+    rendered for (set_absgrad(True) before distributed_preprocess3dgs_and_all2all_final), on EVERY rank.
+      * no exchange (world size 1): the render's rows are the model's rows -- the operator's tensor itself;
+      * with an exchange: score_contributions' return trip -- every rank sends the values of the rows it received back
+        with ONE all-to-all-v per camera along the camera's own route (the exchange's split sizes, swapped; 8 bytes per
+        row) and the owner merges them through the exchange's send_idx into zeros (gsr_absgrad_merge_rows: a Gaussian
+        needed by two bands arrives twice, slab padding carries index -1).
+    A rank that renders no part of a camera, or took the < 10-Gaussian stand-in, takes part and sends zeros."""
+    cas = pkg["batched_cuda_args"]
+    if not all(ca.get("absgrad") for ca in cas):
+        raise RuntimeError("collect_absgrad: the batch was prepared with gaussian_renderer.set_absgrad off")
+    routes = pkg.get("_absgrad_routes")
+    out = []
+    for k in range(len(batched_strategies)):
+        a = cas[k].get(_dgr._ABSGRAD_KEY)  # None: not rendered here, or the stand-in (nothing was drawn)
+        P_local = pkg["batched_locally_preprocessed_radii"][k].shape[0]
+        dev = pkg["batched_locally_preprocessed_radii"][k].device
+        if routes is None:
+            out.append(a if a is not None else torch.zeros((P_local, 2), dtype=torch.float32, device=dev))
+            continue
+        send_idx, send_splits, recv_splits, group = routes[k]
+        n_recv, n_send = sum(recv_splits), sum(send_splits)
+        if a is not None and a.shape[0] != n_recv:
+            raise RuntimeError(f"collect_absgrad: camera {k} rendered {a.shape[0]} rows, its exchange delivered {n_recv}")
+        msg = a if a is not None else torch.zeros((n_recv, 2), dtype=torch.float32, device=dev)
+        back = torch.empty((n_send, 2), dtype=torch.float32, device=dev)
+        dist.all_to_all_single(back, msg, output_split_sizes=send_splits, input_split_sizes=recv_splits, group=group)
+        if dev.type == "cuda":
+            send_idx.record_stream(torch.cuda.current_stream(dev))  # (an overlapped exchange allocated it on its side stream)
+        out.append(_dgr.absgrad_rows(send_idx, back, P_local))
+    return out
 
 
 class _InvDepthNoGrad(torch.autograd.Function):
@@ -456,6 +513,8 @@ class _ExchangeGroup(torch.autograd.Function):
         recv = torch.empty((n_recv, N_DIFF + N_AUX), dtype=msg.dtype, device=dev)
         dist.all_to_all_single(recv, msg, output_split_sizes=recv_splits, input_split_sizes=send_splits, group=group)
         _LAST_ROUTE[0] = (send_idx, send_splits, recv_splits, group)  # (score_contributions sends statistics back along it)
+        if _ABSGRAD[0]:  # (one camera per exchange then, see _batched_exchange_final: collect_absgrad's return trips)
+            holder.setdefault("routes", {})[k0] = _LAST_ROUTE[0]
         if perm is None:  # one exchange per camera (always, with capacity slabs): the message is camera-major already
             outs = list(_dgr.exchange_unpack(recv))
         else:             # several cameras in one exact exchange: (source, camera)-major -> camera-major
@@ -663,8 +722,9 @@ def _batched_exchange_final(m2_views, rgb_views, co_views, radii_views, depths_v
     for st in batched_strategies:
         for g in st.gpu_ids:
             renders[g % W] += 1
-    grouped = bool(speculate and B > 1 and _EXCHANGE_OPTIONS["group"] and max(renders) <= 1)
-    pipelined = (pipeline or speculate) and B > 1 and not grouped   # one exchange per camera ...
+    # (absolute gradients go back to their owners camera by camera, along each camera's own route: no grouping then)
+    grouped = bool(speculate and B > 1 and _EXCHANGE_OPTIONS["group"] and max(renders) <= 1 and not _ABSGRAD[0])
+    pipelined = (pipeline or speculate or _ABSGRAD[0]) and B > 1 and not grouped   # one exchange per camera ...
     # ... on the side stream -- not inside a hipGraph capture: the process group's watchdog thread polls the events of
     # collectives issued from a stream that has not joined the capture yet, which HIP forbids (measured: the capture
     # aborts with hipErrorCapturedEvent); a captured iteration keeps its exchanges on the capturing stream
@@ -754,6 +814,7 @@ def _batched_exchange_final(m2_views, rgb_views, co_views, radii_views, depths_v
     if gather_work is not None:
         gather_work.wait()          # stream-level join with the (long finished) size all-gather; the host does not wait
         planner.stage(all_counts)   # asynchronous copy to pinned memory + event, behind the unpack in stream order
+    _LAST_ROUTES[0] = holder.get("routes")
     pending = (planner, chunkcnt, counts, sizes, planner.pending) if (speculate and cap_ctx is None) else None
     return out[0], out[1], out[2], out[3], out[4], sizes, (events, token), pending
 
@@ -909,6 +970,8 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
         if token is not None and mine:  # anchor of the exchange chain: the render op of the LAST camera this rank renders
             cuda_args_list[mine[-1]]["_exchange_token"] = token
         pkg["_exchange_token"] = token
+        if _ABSGRAD[0]:
+            pkg["_absgrad_routes"] = _LAST_ROUTES[0]
         pkg.pop("_exchange_pending", None)
         if pending is not None:
             planner, chunkcnt, counts, lazy, staged = pending

@@ -468,6 +468,43 @@ int gsr_render_invdepth_backward(int P, int width, int height, const int32_t *ra
 int gsr_depth_backward_means3d(int P, const int32_t *radii, const float *viewmatrix, const float *dL_ddepth,
                                int row_stride, float *dL_dmeans3D, int overwrite, gsr_stream_t stream);
 
+/* ABSOLUTE screen-space gradient of a rendered view (densification).  The reference accumulates the norm of the signed
+ * means2D gradient, which cancels on a large Gaussian whose pixels pull its centre in opposite directions; this is the
+ * homodirectional gradient of AbsGS (`absgrad` of gsplat): the magnitude of every pixel's contribution, summed.  There is
+ * NO reference call site.  The float64 closed form of tests/absgrad_refs.py is the arbiter; its signed sums are, up to the
+ * sign, columns 0:2 of gsr_render_backward's record.  New symbols only: gsr_abi_version does not move.
+ * A walk over the lists gsr_render_forward drew from, with that call's final_T and n_contrib and the dL_dpixels
+ * gsr_render_backward is given: the entry at list position k (0-based) of a local tile is BLENDED on a pixel p iff
+ * k + 1 <= n_contrib[p], power <= 0 and alpha_i = min(0.99, o_i exp(power)) >= 1/255 -- gsr_render_backward's rule, in the
+ * composite kernels' own arithmetic; nothing is re-decided.  With g_c = dL_dpixels[c][p], T_i the transmittance in front
+ * of i, w_j = alpha_j T_j and G_i = exp(power),
+ *   dL/dalpha_i(p) = sum_c g_c (T_i c_i,c - S_i,c / (1 - alpha_i)) - (T_final / (1 - alpha_i)) sum_c bg_c g_c,
+ *   S_i,c          = the sum of w_j c_j,c over the blended j behind i,
+ *   q_i(p)         = o_i G_i dL/dalpha_i(p)      (the 0.99 clamp is the identity in the backward, as in gsr_render_backward),
+ *   (dx, dy)       = mean_i - pixel,
+ *   absgrad[i]     = ( (W/2) sum_p | q_i(p) (A dx + B dy) | ,  (H/2) sum_p | q_i(p) (B dx + C dy) | ),
+ * the sums over the pixels of all local tiles (of the band, for a band launch) that blend i.  Without the absolute values
+ * the two sums are -dL_dmeans2D of gsr_render_backward; the units are the same: pixel gradient x (W/2, H/2).  Only the
+ * colour loss's dL_dpixels enters (a loss on the inverse-depth map does not).
+ * ranges, point_list, means2D, conic_opacity, rgb, compute_locally, bg, row_lo / row_hi: as gsr_render_forward (whole
+ * grid, host band, -1 = device hull behind the range table).  The segment workspace is not used: the walk goes back to
+ * front over the whole list from final_T.
+ *   absgrad fp32 [P,2], FULLY overwritten; rows that are blended nowhere are exactly 0.0f.
+ *   acc64: [P,2] doubles, device scratch of the caller, cleared by the call: the per-quadrant sums (fp32, a fixed order
+ *   over the 64 pixels) are added into it in fp64 and each sum is rounded once into `absgrad` (gsr_render_backward's reason:
+ *   the fp32 result does not depend on the order the tiles finish, but for the rare sum within fp64 rounding of an fp32
+ *   rounding boundary).
+ * gsr_absgrad_merge_rows: dst[idx[r]][0:2] += src[r][0:2] for the n rows that came back from another rank -- the two-column
+ * counterpart of gsr_scatter_add_rows: rows with idx[r] < 0 are skipped, duplicate indices add (atomics).
+ * P < 0 (n < 0), a non-positive frame, or a missing pointer with P > 0 (n > 0; point_list may be NULL: every list can be
+ * empty): GSR_EINVAL before any device work; P == 0 (n == 0) returns 0 and touches nothing. */
+int gsr_render_absgrad(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                       const float *means2D, const float *conic_opacity, const float *rgb,
+                       const uint8_t *compute_locally, const float *bg, const float *final_T, const int32_t *n_contrib,
+                       const float *dL_dpixels, int row_lo, int row_hi, float *absgrad, double *acc64,
+                       gsr_stream_t stream);
+int gsr_absgrad_merge_rows(int64_t n, const int32_t *idx, const float *src, float *dst, gsr_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * N1  fused band-local L1 + SSIM loss -- the arithmetic of final_system_loss_computation,
  * gaussian_renderer/loss_distribution.py:2536-2585 (pixelwise_l1_with_mask / pixelwise_ssim_with_mask,
