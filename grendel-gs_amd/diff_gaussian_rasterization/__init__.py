@@ -2115,6 +2115,99 @@ def fused_activations(scaling, rotation, opacity, features_dc, features_rest):
     return _FusedActivations.apply(scaling, rotation, opacity, features_dc, features_rest)
 
 
+# ---- the 3D smoothing filter of Mip-Splatting (include/gsraster.h: gsr_filter3d_*) -----------------------------------
+def filter3d_focal_max(tanfovx, width):
+    """the largest fx = width / (2 tanfovx) over the cameras, with K1's float32 roundings, on the host"""
+    import numpy as np
+
+    t = np.atleast_1d(np.asarray(tanfovx, dtype=np.float32))
+    return float((np.float32(int(width)) / (np.float32(2.0) * t)).max())
+
+
+def compute_filter3d(xyz, cams_block, width, height, all_reduce_max=None, focal_max=None, return_parts=False):
+    """-> filter_3D [N,1] float32 (Mip-Splatting's shape): sqrt(0.2) x (depth in the nearest camera of `cams_block`
+    [C,40] (pack_camera records) that sees the row) / focal_max; rows that no camera sees take the largest such depth,
+    and zeros when nothing is seen at all.  include/gsraster.h (gsr_filter3d_distance) has the definition.
+    `all_reduce_max`: at world size > 1, a callable that MAX-all-reduces a one-element device tensor in place; it runs
+    between the two launches, on every rank (also one with no rows), and nothing is read back to the host.
+    `focal_max`: the largest fx over ALL training cameras (filter3d_focal_max); when None it is formed from
+    cams_block's tanfovx column, which is one small device-to-host copy.
+    `return_parts`: also (dist [N], seen uint8 [N])."""
+    if not (xyz.is_cuda and cams_block.is_cuda):
+        raise RuntimeError("compute_filter3d: device tensors required (no CPU fallback)")
+    xyz, cams = _f32c(xyz.detach(), "xyz"), _f32c(cams_block.detach(), "cams_block")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError("xyz must be [N, 3]")
+    if cams.dim() != 2 or cams.shape[1] != 40:
+        raise ValueError("cams_block must be [C, 40]")
+    N, C = xyz.shape[0], cams.shape[0]
+    dev = xyz.device
+    if focal_max is None:
+        if C == 0:
+            raise ValueError("compute_filter3d: no cameras and no focal_max")
+        focal_max = filter3d_focal_max(cams[:, 35].cpu().numpy(), width)
+    n_part = lib.gsr_filter3d_num_partials(N)
+    dist = torch.empty((N,), dtype=torch.float32, device=dev)
+    seen = torch.empty((N,), dtype=torch.uint8, device=dev)
+    partials = torch.empty((max(n_part, 1),), dtype=torch.float32, device=dev)
+    out = torch.empty((N, 1), dtype=torch.float32, device=dev)
+    with _on(dev), kernel_timer.range("filter3d_distance"):
+        check(lib.gsr_filter3d_distance(N, C, _ptr(xyz), _ptr(cams), int(width), int(height), _ptr(dist), _ptr(seen),
+                                        _ptr(partials), _stream()), "gsr_filter3d_distance")
+        gmax = None
+        if all_reduce_max is not None:
+            # (the one float the ranks exchange: a max over a few thousand partials, once per hundred iterations)
+            gmax = partials[:n_part].amax().reshape(1) if n_part else torch.zeros(1, dtype=torch.float32, device=dev)
+            all_reduce_max(gmax)
+        check(lib.gsr_filter3d_finalize(N, _ptr(dist), _ptr(seen), _ptr(partials), n_part, _ptr(gmax),
+                                        float(focal_max), _ptr(out), _stream()), "gsr_filter3d_finalize")
+    return (out, dist, seen) if return_parts else out
+
+
+class _Filter3DApply(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scaling, opacity, filter_3D):
+        if not (scaling.is_cuda and opacity.is_cuda and filter_3D.is_cuda):
+            raise RuntimeError("filter3d_apply: device tensors required (no CPU fallback)")
+        scaling, opacity = _f32c(scaling, "scaling"), _f32c(opacity, "opacity")
+        f = _f32c(filter_3D.detach(), "filter_3D")
+        N = scaling.shape[0]
+        if scaling.dim() != 2 or scaling.shape[1] != 3 or opacity.numel() != N or f.numel() != N:
+            raise ValueError(f"filter3d_apply: scaling [N,3], opacity [N,1] and filter_3D [N,1] expected, got "
+                             f"{tuple(scaling.shape)}, {tuple(opacity.shape)}, {tuple(f.shape)}")
+        dev = scaling.device
+        scaling_eff, opacity_eff = torch.empty_like(scaling), torch.empty_like(opacity)
+        with _on(dev), kernel_timer.range("filter3d_apply_forward"):
+            check(lib.gsr_filter3d_apply_forward(N, _ptr(scaling), _ptr(opacity), _ptr(f), _ptr(scaling_eff),
+                                                 _ptr(opacity_eff), _stream()), "gsr_filter3d_apply_forward")
+        ctx.save_for_backward(scaling, opacity, f)
+        ctx.set_materialize_grads(False)
+        return scaling_eff, opacity_eff
+
+    @staticmethod
+    def backward(ctx, g_scaling, g_opacity):
+        scaling, opacity, f = ctx.saved_tensors
+        N, dev = scaling.shape[0], scaling.device
+        if g_scaling is None and g_opacity is None:
+            return None, None, None
+        g_scaling = torch.zeros_like(scaling) if g_scaling is None else g_scaling.float().contiguous()
+        g_opacity = torch.zeros_like(opacity) if g_opacity is None else g_opacity.float().contiguous()
+        d_scaling, d_opacity = torch.empty_like(scaling), torch.empty_like(opacity)
+        with _on(dev), kernel_timer.range("filter3d_apply_backward"):
+            check(lib.gsr_filter3d_apply_backward(N, _ptr(scaling), _ptr(opacity), _ptr(f), _ptr(g_scaling),
+                                                  _ptr(g_opacity), _ptr(d_scaling), _ptr(d_opacity), _stream()),
+                  "gsr_filter3d_apply_backward")
+        return d_scaling, d_opacity, None
+
+
+def filter3d_apply(scaling, opacity, filter_3D):
+    """(_scaling [N,3], _opacity [N,1], filter_3D [N,1]) -> (scaling_eff, opacity_eff): the raw parameters of the
+    Gaussians with the 3D filter folded in -- exp(scaling_eff) = sqrt(exp(_scaling)^2 + f^2), sigmoid(opacity_eff) =
+    sigmoid(_opacity) prod_k s_k / s'_k -- for the raw K1 / K11 in place of the parameters.  One kernel each way;
+    filter_3D gets no gradient; a row with f == 0 keeps its bits, both ways."""
+    return _Filter3DApply.apply(scaling, opacity, filter_3D)
+
+
 def exchange_need(means2D_all, radii_all, bands, width, height):
     """K2 for the whole camera batch in the exchange's layout: means2D_all [B,P,2], radii_all int32 [B,P],
     bands int32 [B,W,2] (tile rows [lo,hi) of camera k rendered by global rank g) ->

@@ -160,6 +160,11 @@ SIGNATURES = {
                                    ctypes.c_uint32, ctypes.c_uint32, c_void_p, c_void_p]),
     "gsr_activate_forward": (c_int, [c_int, c_int] + [c_void_p] * 10),
     "gsr_activate_backward": (c_int, [c_int, c_int] + [c_void_p] * 13),
+    "gsr_filter3d_num_partials": (c_int, [c_int]),
+    "gsr_filter3d_distance": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 4),
+    "gsr_filter3d_finalize": (c_int, [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_float, c_void_p, c_void_p]),
+    "gsr_filter3d_apply_forward": (c_int, [c_int] + [c_void_p] * 6),
+    "gsr_filter3d_apply_backward": (c_int, [c_int] + [c_void_p] * 8),
 }
 
 ABI_VERSION = 15

@@ -137,6 +137,27 @@ def get_absgrad():
     return _ABSGRAD[0]
 
 
+# ------------------------------------------------------------------------------ 3D smoothing filter (opt-in)
+_FILTER3D = [os.environ.get("GSR_FILTER3D", "0") not in ("", "0")]
+
+
+def set_filter3d(on):
+    """True (default False; GSR_FILTER3D=1 in the environment: True): every projection, train and test, runs on the
+    model's parameters with Mip-Splatting's 3D smoothing filter folded in -- diff_gaussian_rasterization.filter3d_apply
+    of (pc._scaling, pc._opacity, pc.filter_3D) in front of the batched K1, one small kernel each way -- and the
+    gradients reach pc._scaling / pc._opacity through it.  pc.filter_3D comes from filter3d.compute_3D_filter(pc,
+    training_cameras), to be called again after every densification event (a missing or wrong-length tensor raises).
+    Extension of this build: the reference has no such filter.  Under FusedAdam(fuse_backward=True) the projection
+    backward is NOT fused into the optimizer step while this is on (the filtered tensors are not its parameters): the
+    plain K11, the filter's backward and the dense Adam run instead, with the same results.  Graph capture raises.  With
+    the switch off nothing changes at all."""
+    _FILTER3D[0] = bool(on)
+
+
+def get_filter3d():
+    return _FILTER3D[0]
+
+
 def collect_absgrad(pkg, batched_strategies):
     """-> one fp32 [P_local, 2] tensor per camera: the absolute screen-space gradient of THIS rank's Gaussians, summed
     over every band that rendered them, in means2D.grad's units.  Call it after the backward of the batch `pkg` was
@@ -853,6 +874,14 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
         raise RuntimeError("distributed_preprocess3dgs_and_all2all_final: the model must live on the gfx950 device "
                            "(there is no CPU path)")
     # exp / normalize / sigmoid / cat of the getters (scene/gaussian_model.py:109-129) happen inside K1 / K11
+    if _FILTER3D[0]:
+        # the 3D smoothing filter: K1 / K11 see the effective raw scaling and opacity (set_filter3d)
+        if _dgr.capturing() is not None:
+            raise RuntimeError("set_filter3d(True): the 3D smoothing filter is not supported inside a graph capture; run "
+                               "the iteration eagerly")
+        from filter3d import _filter_of
+
+        raw[1], raw[5] = _dgr.filter3d_apply(raw[1], raw[5], _filter_of(pc, "set_filter3d(True)"))
     if timers is not None:
         timers.stop("forward_prepare_gaussians")
         timers.start("forward_preprocess_gaussians")
@@ -943,7 +972,8 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
         redistributed = tuple([p[c] for p in params] for c in range(5))
         sizes = [[[p[0].shape[0] for p in params]]]
         _fill(pkg, redistributed, sizes)
-        if mode == "train" and not pose_grad and not _INVDEPTH[0] and len(cuda_args_list) <= _dgr.DEFER_MAX_CAMERAS:
+        if mode == "train" and not pose_grad and not _INVDEPTH[0] and not _FILTER3D[0] and \
+                len(cuda_args_list) <= _dgr.DEFER_MAX_CAMERAS:
             # nothing but the projection backward reads these views' gradient records (no exchange, no K11c, no depth
             # path; `.grad` of means2D is kept lazily, above): their rounding may be left to the fused K11 + Adam launch
             # (which takes that many cameras: a larger batch keeps the rounding launches)

@@ -568,6 +568,13 @@ class GraphedIteration:
             raise RuntimeError("GraphedIteration: an exposure model is set (loss_distribution.set_exposure_model); "
                                "exposure compensation is not captured -- run it eagerly "
                                "(GraphedIteration(..., enabled=False) or call the body directly)")
+        from gaussian_renderer import get_filter3d
+
+        if get_filter3d():
+            # the filtered tensors are not the optimizer's parameters: the fused K11 + Adam launch a capture consists of
+            # declines them
+            raise RuntimeError("GraphedIteration: set_filter3d(True) is on; the 3D smoothing filter is not captured -- "
+                               "run it eagerly (GraphedIteration(..., enabled=False) or call the body directly)")
         for camera in cameras:
             if any(torch.is_tensor(t) and t.requires_grad for t in
                    (camera.world_view_transform, camera.full_proj_transform, camera.camera_center)):

@@ -1031,6 +1031,53 @@ int gsr_activate_backward(int N, int sh_rest, const float *rotation, const float
                           const float *g_shs, float *d_scaling, float *d_rotation, float *d_opacity,
                           float *d_features_dc, float *d_features_rest, gsr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The 3D smoothing filter of Mip-Splatting (Yu et al., CVPR 2024), the companion of gsr_set_antialiasing's 2D filter.
+ * There is NO reference call site for these five entry points: the reference has no such filter.  The float64
+ * restatements of tests/filter3d_refs.py are the arbiter.
+ *
+ * Per Gaussian one scalar f >= 0, a world-space length: a Gaussian may not be smaller than the sampling interval of the
+ * nearest training camera that sees it.  f acts through the scales and the opacity only,
+ *     s'_k = sqrt(s_k^2 + f^2)  (k = 0..2, s = exp(_scaling)),      o' = sigmoid(_opacity) c,  c = prod_k s_k / s'_k.
+ *
+ * gsr_filter3d_distance: xyz [N,3], cams [C,40] (the records of the camera-batched K1: viewmatrix in floats 0..15,
+ *   tanfovx / tanfovy in floats 35 / 36).  Per (row, camera): t = [p, 1] * viewmatrix with K1's expression, in K1's order
+ *   and with one rounding per operation, so t.z has the bits K1 writes to `depths`; fx = width / (2 tanfovx) and
+ *   fy = height / (2 tanfovy) as in K1.  The pair is VALID iff
+ *       t.z > 0.2f,   |fx t.x| <= (0.65f width) t.z,   |fy t.y| <= (0.65f height) t.z
+ *   (Mip-Splatting's 15 % margin around the screen, written without the division).  Per row: dist [N] = min t.z over the
+ *   valid cameras (0 when there is none) and seen [N] = 1 / 0.  partials [gsr_filter3d_num_partials(N)]: per workgroup
+ *   the max of dist over its rows; 0 = none seen, which no valid t.z can be.  No atomics.
+ * gsr_filter3d_finalize: m = *global_max when global_max != NULL (a device float: the max over ALL ranks' partials, which
+ *   a caller at world size > 1 forms with one MAX all-reduce between the two calls; partials may then be NULL), else the
+ *   max of the n_partials partials (n_partials must be gsr_filter3d_num_partials(N)).  filter_out [N]:
+ *       f = (float32(sqrt(0.2)) d) / focal_max,   d = dist of a seen row,  d = m of an unseen row
+ *   (Mip-Splatting's distance[~valid] = distance[valid].max()), and f = 0 for every row when m == 0: the identity filter.
+ *   focal_max: the largest fx over the cameras, formed by the caller on the host; must be > 0.
+ * gsr_filter3d_apply_forward: (_scaling [N,3], _opacity [N], filter [N]) -> the EFFECTIVE RAW parameters
+ *       scaling_eff_k = log s'_k = (1/2) log(exp(2 _scaling_k) + f^2),      opacity_eff = logit(sigmoid(_opacity) c),
+ *   which the raw K1 / K11 entry points take in place of _scaling / _opacity.  Computed in log space -- with
+ *   d_k = log(f^2 / s_k^2):  log(s'_k / s_k) = (max(d_k, 0) + log1p(exp(-|d_k|))) / 2,  log c = -(their sum),
+ *   opacity_eff = _opacity + log c - log1p((1 - c) exp(_opacity)) -- so that no product of squared scales is formed.
+ *   A row with f == 0 returns its inputs bit for bit.
+ * gsr_filter3d_apply_backward: with g_s [N,3], g_o [N] the gradients of the effective tensors, sigma = sigmoid(_opacity),
+ *   r_k = s_k^2 / s'_k^2 and p = sigma c:
+ *       d_scaling_k = g_s_k r_k + g_o (1 - r_k) / (1 - p),      d_opacity = g_o (1 - sigma) / (1 - p),
+ *   with 1 - r_k = f^2 / s'_k^2 and 1 - p = (1 - sigma) + sigma (1 - c) formed without a subtraction.  f gets no
+ *   gradient.  A row with f == 0 returns g_s, g_o bit for bit.
+ * All: N == 0 returns 0 without a launch; a NULL pointer that would be dereferenced, N < 0, C < 0 or a non-positive
+ * image size return GSR_EINVAL. */
+int gsr_filter3d_num_partials(int N);
+int gsr_filter3d_distance(int N, int C, const float *xyz, const float *cams, int width, int height, float *dist,
+                          uint8_t *seen, float *partials, gsr_stream_t stream);
+int gsr_filter3d_finalize(int N, const float *dist, const uint8_t *seen, const float *partials, int n_partials,
+                          const float *global_max, float focal_max, float *filter_out, gsr_stream_t stream);
+int gsr_filter3d_apply_forward(int N, const float *scaling, const float *opacity, const float *filter,
+                               float *scaling_eff, float *opacity_eff, gsr_stream_t stream);
+int gsr_filter3d_apply_backward(int N, const float *scaling, const float *opacity, const float *filter,
+                                const float *g_scaling, const float *g_opacity, float *d_scaling, float *d_opacity,
+                                gsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
