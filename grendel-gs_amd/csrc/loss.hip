@@ -92,14 +92,27 @@ __device__ __forceinline__ float expo_apply(const float *e, float x0, float x1, 
     return fmaf(e[0], x0, fmaf(e[1], x1, fmaf(e[2], x2, e[3])));
 }
 
+// Per-pixel loss mask (MASK; include/gsraster.h, N1m): one byte per pixel of the band, shared by the channels,
+// m = byte * (1/255f) -- exactly 1 for byte 255, exactly 0 for byte 0 (tests/test_masked_loss_refs_cpu.py walks all 256).
+__device__ __forceinline__ float mask_weight(uint8_t b) { return (float)b * (1.0f / 255.0f); }
+// The MASK instantiations of the kernels below take the mask pointer as one more (last) kernel argument; the others have
+// no such argument: their signatures and instruction streams are those of the kernels before the mask existed.
+__device__ __forceinline__ const uint8_t *mask_pointer() { return nullptr; }
+__device__ __forceinline__ const uint8_t *mask_pointer(const uint8_t *p) { return p; }
+
 // EXPO: the halo tile is staged as (x', y) from the three channels of the pixel; everything behind the staging is the
 // same code.  `expo` is not looked at by the plain instantiations.
-template <bool VEC, bool EXPO>
+// MASK: the staged pair is (m x', m y) -- one multiply each, so that m = 1 hands both through bit for bit and m = 0
+// stages zeros whatever finite value lies in the image; `mask` ([rows, W], one channel of the ground truth's layout) is
+// not looked at by the other instantiations.
+template <bool VEC, bool EXPO, bool MASK = false, typename... MaskArg>
 __global__ void __launch_bounds__(LT)
 l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restrict__ image, long long img_cstride,
                        const uint8_t *__restrict__ gt, float *__restrict__ partials, float *__restrict__ M1,
                        float *__restrict__ M2, float *__restrict__ M3, const int *__restrict__ band,
-                       const float *__restrict__ expo) {
+                       const float *__restrict__ expo, MaskArg... mask_arg) {
+    static_assert(sizeof...(MaskArg) == (MASK ? 1 : 0), "the mask pointer is an argument of the MASK kernels only");
+    const uint8_t *__restrict__ mask = mask_pointer(mask_arg...);
     __shared__ v2f sXY[HH][HW + 1];     // (x, y): rendered band / ground truth
     __shared__ v2f hAB[HH][HSTR];       // horizontal pass of (x, y)
     __shared__ v2f hCD[HH][HSTR];       // ... of (x^2, y^2)
@@ -130,7 +143,7 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
             const int ly = tid / HV, q = tid - ly * HV;
             const int gy = oy + ly - 5, gx0 = ox - 8 + 4 * q;
             float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            uchar4 y = make_uchar4(0, 0, 0, 0);
+            uchar4 y = make_uchar4(0, 0, 0, 0), mk = y;
             if (gy >= 0 && gy < rows && gx0 >= 0 && gx0 < W) {  // W % 4 == 0: a vector is inside or outside as a whole
                 if (EXPO) {
                     const float *p = img_0 + (size_t)gy * W + gx0;
@@ -143,13 +156,20 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
                     x = *reinterpret_cast<const float4 *>(img_c + (size_t)gy * W + gx0);
                 }
                 y = *reinterpret_cast<const uchar4 *>(gt_c + (size_t)gy * W + gx0);
+                if (MASK) mk = *reinterpret_cast<const uchar4 *>(mask + (size_t)gy * W + gx0);
             }
             const float xs[4] = {x.x, x.y, x.z, x.w};
             const float ys[4] = {(float)y.x, (float)y.y, (float)y.z, (float)y.w};
+            const uint8_t ms[4] = {mk.x, mk.y, mk.z, mk.w};
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int lx = 4 * q - 3 + i;
-                if (lx >= 0 && lx < HW) sXY[ly][lx] = v2f{xs[i], ys[i] * (1.0f / 255.0f)};
+                if (MASK) {
+                    const float m = mask_weight(ms[i]);
+                    if (lx >= 0 && lx < HW) sXY[ly][lx] = v2f{m * xs[i], m * (ys[i] * (1.0f / 255.0f))};
+                } else {
+                    if (lx >= 0 && lx < HW) sXY[ly][lx] = v2f{xs[i], ys[i] * (1.0f / 255.0f)};
+                }
             }
         }
     } else {
@@ -165,6 +185,11 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
                     v.x = img_c[(size_t)gy * W + gx];
                 }
                 v.y = (float)gt_c[(size_t)gy * W + gx] * (1.0f / 255.0f);
+                if (MASK) {
+                    const float m = mask_weight(mask[(size_t)gy * W + gx]);
+                    v.x = m * v.x;
+                    v.y = m * v.y;
+                }
             }
             sXY[ly][lx] = v;
         }
@@ -284,13 +309,19 @@ l1_ssim_forward_kernel(int rows, int W, int gxT, int gyT, const float *__restric
     }
 }
 
-template <bool VEC>
+// MASK: x' = m x and y' = m y are recomputed at the output pixel from one mask byte read beside the ground-truth byte,
+// g' is the unmasked formula at (x', y') with every product and sum rounded on its own (no contraction: m = 1 then
+// writes the unmasked kernel's bits), and the pixel receives m g' -- a plain +0 where the byte is 0.
+template <bool VEC, bool MASK = false, typename... MaskArg>
 __global__ void __launch_bounds__(LT)
 l1_ssim_backward_kernel(int rows, int W, int gxT, int gyT, const float *__restrict__ image, long long img_cstride,
                         const uint8_t *__restrict__ gt, const float *__restrict__ M1, const float *__restrict__ M2,
                         const float *__restrict__ M3, const float *__restrict__ grad_l1_sum,
                         const float *__restrict__ grad_ssim_sum, float scale_l1, float scale_ssim,
-                        float *__restrict__ grad_image, long long grad_cstride, const int *__restrict__ band) {
+                        float *__restrict__ grad_image, long long grad_cstride, const int *__restrict__ band,
+                        MaskArg... mask_arg) {
+    static_assert(sizeof...(MaskArg) == (MASK ? 1 : 0), "the mask pointer is an argument of the MASK kernels only");
+    const uint8_t *__restrict__ mask = mask_pointer(mask_arg...);
     __shared__ float sM[3][HH][HW + 1];
     __shared__ float hor[3][HH][HSTR];
     int c, ox, oy, nwg;
@@ -378,12 +409,25 @@ l1_ssim_backward_kernel(int rows, int W, int gxT, int gyT, const float *__restri
     for (int o = 0; o < VO; o++) {
         const int gy = oy + ty0 + o;
         if (gy >= rows) break;
-        const float x = image[(long long)c * img_cstride + row_off + (size_t)gy * W + gx];
-        const float y = (float)gt[cbase + (size_t)gy * W + gx] * (1.0f / 255.0f);
-        const float d = x - y;
-        const float sgn = (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f);
-        grad_image[(long long)c * grad_cstride + row_off + (size_t)gy * W + gx] =
-            gl1 * sgn + gss * (cv[0][o] + 2.f * x * cv[1][o] + y * cv[2][o]);
+        if (MASK) {
+            const uint8_t mb = mask[(size_t)gy * W + gx];
+            const float m = mask_weight(mb);
+            const float x = m * image[(long long)c * img_cstride + row_off + (size_t)gy * W + gx];
+            const float y = m * ((float)gt[cbase + (size_t)gy * W + gx] * (1.0f / 255.0f));
+            const float d = x - y;
+            const float sgn = (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f);
+            const float inner = __fadd_rn(__fadd_rn(cv[0][o], __fmul_rn(__fmul_rn(2.f, x), cv[1][o])),
+                                          __fmul_rn(y, cv[2][o]));
+            const float gp = __fadd_rn(__fmul_rn(gl1, sgn), __fmul_rn(gss, inner));
+            grad_image[(long long)c * grad_cstride + row_off + (size_t)gy * W + gx] = mb ? __fmul_rn(m, gp) : 0.f;
+        } else {
+            const float x = image[(long long)c * img_cstride + row_off + (size_t)gy * W + gx];
+            const float y = (float)gt[cbase + (size_t)gy * W + gx] * (1.0f / 255.0f);
+            const float d = x - y;
+            const float sgn = (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f);
+            grad_image[(long long)c * grad_cstride + row_off + (size_t)gy * W + gx] =
+                gl1 * sgn + gss * (cv[0][o] + 2.f * x * cv[1][o] + y * cv[2][o]);
+        }
     }
 }
 
@@ -433,7 +477,9 @@ __global__ void __launch_bounds__(256) l1_ssim_finalize_kernel(int nb, const flo
 //   dL/dA[c][k] = sum_pixels g'[c] x[k],  dL/db[c] = sum_pixels g'[c]:  12 sums per workgroup, published as one row of
 // expo_partials (indexed by tile like the forward's sums; workgroups above a device band's tile count publish zeros) and
 // added up by exposure_finalize_kernel in a fixed order in fp64 -- no atomics, no scratch image, no second pass.
-template <bool VEC>
+// MASK: x' = m (A x + b), y' = m y, and the pixel's g'[c] is multiplied by m (a plain +0 where the byte is 0) before
+// it enters A^T g' and the 12 sums: dL/dA[c][k] = sum m g'[c] x[k], dL/db[c] = sum m g'[c].
+template <bool VEC, bool MASK = false, typename... MaskArg>
 __global__ void __launch_bounds__(LT)
 l1_ssim_backward_exposure_kernel(int rows, int W, int gxT, int gyT, const float *__restrict__ image, long long img_cstride,
                                  const uint8_t *__restrict__ gt, const float *__restrict__ M1,
@@ -441,7 +487,9 @@ l1_ssim_backward_exposure_kernel(int rows, int W, int gxT, int gyT, const float 
                                  const float *__restrict__ grad_l1_sum, const float *__restrict__ grad_ssim_sum,
                                  float scale_l1, float scale_ssim, float *__restrict__ grad_image, long long grad_cstride,
                                  const int *__restrict__ band, const float *__restrict__ expo,
-                                 float *__restrict__ expo_partials) {
+                                 float *__restrict__ expo_partials, MaskArg... mask_arg) {
+    static_assert(sizeof...(MaskArg) == (MASK ? 1 : 0), "the mask pointer is an argument of the MASK kernels only");
+    const uint8_t *__restrict__ mask = mask_pointer(mask_arg...);
     __shared__ float sM[3][HH][HW + 1];
     __shared__ float hor[3][HH][HSTR];
     __shared__ float red[12][LT / 64];
@@ -551,15 +599,28 @@ l1_ssim_backward_exposure_kernel(int rows, int W, int gxT, int gyT, const float 
             float gp = 0.f;
             if (ok[o]) {
                 const int gy = oy + ty0 + o;
-                const float x = expo_apply(e, xin[0][o], xin[1][o], xin[2][o]);
-                const float y = (float)gt[cbase + (size_t)gy * W + gx] * (1.0f / 255.0f);
-                const float d = x - y;
-                const float sgn = (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f);
-                // the plain kernel's gl1 * sgn + gss * (cv0 + 2 x cv1 + y cv2) with its roundings spelled out (every product
-                // and sum rounded, taps above as fma): with an identity E this kernel writes the plain kernel's bits
-                const float inner = __fadd_rn(__fadd_rn(cv[0][o], __fmul_rn(__fmul_rn(2.f, x), cv[1][o])),
-                                              __fmul_rn(y, cv[2][o]));
-                gp = __fadd_rn(__fmul_rn(gl1, sgn), __fmul_rn(gss, inner));
+                if (MASK) {  // the same chain at (m x', m y), its result times m: m = 1 forms the bits of the branch below
+                    const uint8_t mb = mask[(size_t)gy * W + gx];
+                    const float m = mask_weight(mb);
+                    const float x = __fmul_rn(m, expo_apply(e, xin[0][o], xin[1][o], xin[2][o]));
+                    const float y = __fmul_rn(m, (float)gt[cbase + (size_t)gy * W + gx] * (1.0f / 255.0f));
+                    const float d = x - y;
+                    const float sgn = (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f);
+                    const float inner = __fadd_rn(__fadd_rn(cv[0][o], __fmul_rn(__fmul_rn(2.f, x), cv[1][o])),
+                                                  __fmul_rn(y, cv[2][o]));
+                    gp = mb ? __fmul_rn(m, __fadd_rn(__fmul_rn(gl1, sgn), __fmul_rn(gss, inner))) : 0.f;
+                } else {
+                    const float x = expo_apply(e, xin[0][o], xin[1][o], xin[2][o]);
+                    const float y = (float)gt[cbase + (size_t)gy * W + gx] * (1.0f / 255.0f);
+                    const float d = x - y;
+                    const float sgn = (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f);
+                    // the plain kernel's gl1 * sgn + gss * (cv0 + 2 x cv1 + y cv2) with its roundings spelled out (every
+                    // product and sum rounded, taps above as fma): with an identity E this kernel writes the plain
+                    // kernel's bits
+                    const float inner = __fadd_rn(__fadd_rn(cv[0][o], __fmul_rn(__fmul_rn(2.f, x), cv[1][o])),
+                                                  __fmul_rn(y, cv[2][o]));
+                    gp = __fadd_rn(__fmul_rn(gl1, sgn), __fmul_rn(gss, inner));
+                }
             }
 #pragma unroll
             for (int k = 0; k < 3; k++) {
@@ -760,6 +821,66 @@ extern "C" int gsr_l1_ssim_backward_exposure(int channels, int rows_capacity, in
         GSR_LAUNCH_CHECK();
     }
     // (no rows: no partial rows, the 12 sums are zeros)
+    hipLaunchKernelGGL(exposure_finalize_kernel, dim3(1), dim3(256), 0, st, gxT * gyT, exposure_partials, grad_exposure);
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- loss masks (N1m)
+extern "C" int gsr_l1_ssim_forward_masked(int channels, int rows_capacity, int width, const float *image,
+                                          int64_t image_channel_stride, const uint8_t *gt, const uint8_t *mask,
+                                          float *partials, float *dm_dmu1, float *dm_dE11, float *dm_dE12,
+                                          const int32_t *band_rows, const float *exposure, gsr_stream_t stream) {
+    const int rows = rows_capacity;
+    if (channels <= 0 || rows <= 0 || width <= 0 || !mask) return GSR_EINVAL;
+    if (exposure && channels != 3) return GSR_EINVAL;
+    if (!image || !gt || !partials) return GSR_EINVAL;
+    if ((dm_dmu1 || dm_dE11 || dm_dE12) && !(dm_dmu1 && dm_dE11 && dm_dE12)) return GSR_EINVAL;
+    const int gxT = gsr_div_up(width, TS), gyT = gsr_div_up(rows, TS);
+    // (the mask is fetched as uchar4 beside the ground truth's: its base pointer has to allow that too)
+    const bool vec = width % 4 == 0 && image_channel_stride % 4 == 0 && aligned_to(image, 16) && aligned_to(gt, 4) &&
+                     aligned_to(mask, 4);
+    using M = const uint8_t *;
+    auto kernel = exposure ? (vec ? l1_ssim_forward_kernel<true, true, true, M> : l1_ssim_forward_kernel<false, true, true, M>)
+                           : (vec ? l1_ssim_forward_kernel<true, false, true, M> : l1_ssim_forward_kernel<false, false, true, M>);
+    hipLaunchKernelGGL(kernel, dim3(gxT * gyT * channels), dim3(LT), 0, reinterpret_cast<hipStream_t>(stream), rows, width,
+                       gxT, gyT, image, (long long)image_channel_stride, gt, partials, dm_dmu1, dm_dE11, dm_dE12,
+                       band_rows, exposure, mask);
+    GSR_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int gsr_l1_ssim_backward_masked(int channels, int rows_capacity, int width, const float *image,
+                                           int64_t image_channel_stride, const uint8_t *gt, const uint8_t *mask,
+                                           const float *dm_dmu1, const float *dm_dE11, const float *dm_dE12,
+                                           const float *grad_l1_sum, const float *grad_ssim_sum, float scale_l1,
+                                           float scale_ssim, float *grad_image, int64_t grad_channel_stride,
+                                           const int32_t *band_rows, const float *exposure, float *exposure_partials,
+                                           float *grad_exposure, gsr_stream_t stream) {
+    const int rows = rows_capacity;
+    if (channels <= 0 || rows <= 0 || width <= 0 || !mask) return GSR_EINVAL;
+    if (exposure && (channels != 3 || !exposure_partials || !grad_exposure)) return GSR_EINVAL;
+    if (!image || !gt || !dm_dmu1 || !dm_dE11 || !dm_dE12 || !grad_l1_sum || !grad_ssim_sum || !grad_image)
+        return GSR_EINVAL;
+    using M = const uint8_t *;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int gxT = gsr_div_up(width, TS), gyT = gsr_div_up(rows, TS);
+    // (the backward reads single mask bytes: the maps alone decide the vector path, as in the unmasked launches)
+    const bool vec = width % 4 == 0 && aligned_to(dm_dmu1, 16) && aligned_to(dm_dE11, 16) && aligned_to(dm_dE12, 16);
+    if (!exposure) {
+        auto kernel = vec ? l1_ssim_backward_kernel<true, true, M> : l1_ssim_backward_kernel<false, true, M>;
+        hipLaunchKernelGGL(kernel, dim3(gxT * gyT * channels), dim3(LT), 0, st, rows, width, gxT, gyT, image,
+                           (long long)image_channel_stride, gt, dm_dmu1, dm_dE11, dm_dE12, grad_l1_sum, grad_ssim_sum,
+                           scale_l1, scale_ssim, grad_image, (long long)grad_channel_stride, band_rows, mask);
+        GSR_LAUNCH_CHECK();
+        return 0;
+    }
+    auto kernel = vec ? l1_ssim_backward_exposure_kernel<true, true, M> : l1_ssim_backward_exposure_kernel<false, true, M>;
+    hipLaunchKernelGGL(kernel, dim3(gxT * gyT), dim3(LT), 0, st, rows, width, gxT, gyT, image,
+                       (long long)image_channel_stride, gt, dm_dmu1, dm_dE11, dm_dE12, grad_l1_sum, grad_ssim_sum,
+                       scale_l1, scale_ssim, grad_image, (long long)grad_channel_stride, band_rows, exposure,
+                       exposure_partials, mask);
+    GSR_LAUNCH_CHECK();
     hipLaunchKernelGGL(exposure_finalize_kernel, dim3(1), dim3(256), 0, st, gxT * gyT, exposure_partials, grad_exposure);
     GSR_LAUNCH_CHECK();
     return 0;

@@ -2008,6 +2008,102 @@ def fused_band_loss_exposure(image, exposure, gt_u8, y0, y1, lambda_dssim, n, ba
                                         band_rows)
 
 
+class _FusedBandLossMasked(torch.autograd.Function):
+    """_FusedBandLoss (exposure None) or _FusedBandLossExposure of the masked band x' = m x, y' = m y, m = mask / 255 per
+    pixel (include/gsraster.h, N1m): the mask is applied inside the forward's staging and the backward's recomputation --
+    no masked copy of the image, no extra launch.  n stays H*W*3 of the full image.  Returns (loss, Ll1, ssim); the last
+    two are detached."""
+
+    @staticmethod
+    def forward(ctx, image, gt_u8, mask_u8, y0, y1, lambda_dssim, n, band_rows, exposure):
+        expo = exposure is not None
+        if not image.is_cuda or not mask_u8.is_cuda or (expo and not exposure.is_cuda):
+            raise RuntimeError("fused_band_loss_masked: device tensors required (no CPU fallback)")
+        ctx.set_materialize_grads(False)
+        image = image.float().contiguous()
+        C, H, W = image.shape
+        if expo:
+            if C != 3 or tuple(exposure.shape) != (3, 4):
+                raise ValueError(f"exposure compensation needs a [3,H,W] image and a [3,4] exposure, got "
+                                 f"{tuple(image.shape)} and {tuple(exposure.shape)}")
+            exposure = exposure.float().contiguous()
+        gt_u8 = gt_u8.contiguous()
+        dyn = band_rows is not None
+        if dyn and (band_rows.dtype != torch.int32 or not band_rows.is_cuda or band_rows.numel() < 2):
+            raise ValueError("band_rows must be an int32 device tensor { y0, y1 }")
+        rows = int(gt_u8.shape[1]) if dyn else y1 - y0
+        if gt_u8.dtype != torch.uint8 or tuple(gt_u8.shape) != (C, rows, W):
+            raise ValueError(f"gt band must be uint8 [{C},{rows},{W}], got {gt_u8.dtype} {tuple(gt_u8.shape)}")
+        if mask_u8.dtype != torch.uint8 or tuple(mask_u8.shape) not in ((rows, W), (1, rows, W)):
+            raise ValueError(f"mask band must be uint8 [{rows},{W}] or [1,{rows},{W}], got {mask_u8.dtype} "
+                             f"{tuple(mask_u8.shape)}")
+        mask_u8 = mask_u8.contiguous()
+        dev = image.device
+        need_grad = ctx.needs_input_grad[0] or (expo and ctx.needs_input_grad[8])
+        nb = lib.gsr_l1_ssim_num_partials(C, rows, W)
+        partials = torch.empty((max(nb, 1), 2), dtype=torch.float32, device=dev)
+        maps = torch.empty((3, C, rows, W), dtype=torch.float32, device=dev) if need_grad else None
+        out3 = torch.empty((3,), dtype=torch.float32, device=dev)
+        c_l1, c_ssim = (1.0 - lambda_dssim) / n, -lambda_dssim / n
+        m = [_ptr(maps[i]) if need_grad else None for i in range(3)]
+        with _on(dev):
+            if rows > 0:
+                with kernel_timer.range("l1_ssim_forward", Px=rows * W):
+                    img_ptr = _ptr(image) if dyn else ctypes.c_void_p(image.data_ptr() + 4 * y0 * W)
+                    check(lib.gsr_l1_ssim_forward_masked(C, rows, W, img_ptr, H * W, _ptr(gt_u8), _ptr(mask_u8),
+                                                         _ptr(partials), m[0], m[1], m[2], _ptr(band_rows),
+                                                         _ptr(exposure) if expo else None, _stream()),
+                          "gsr_l1_ssim_forward_masked")
+            check(lib.gsr_l1_ssim_finalize(nb, _ptr(partials), c_l1, c_ssim, lambda_dssim, 1.0 / n, _ptr(out3),
+                                           _stream()), "gsr_l1_ssim_finalize")
+        ctx.y0, ctx.y1, ctx.coef, ctx.band_rows, ctx.expo = y0, y1, (c_l1, c_ssim), band_rows, expo
+        if need_grad:
+            ctx.save_for_backward(image, gt_u8, mask_u8, maps, *([exposure] if expo else []))
+        loss, Ll1, ssim = out3[0], out3[1], out3[2]
+        ctx.mark_non_differentiable(Ll1, ssim)
+        return loss, Ll1, ssim
+
+    @staticmethod
+    def backward(ctx, g_loss, _g1, _g2):
+        if g_loss is None:
+            return (None,) * 9
+        image, gt_u8, mask_u8, maps = ctx.saved_tensors[:4]
+        exposure = ctx.saved_tensors[4] if ctx.expo else None
+        C, H, W = image.shape
+        y0, y1 = ctx.y0, ctx.y1
+        dyn = ctx.band_rows is not None
+        rows = int(gt_u8.shape[1]) if dyn else y1 - y0
+        dev = image.device
+        g_loss = g_loss if (g_loss.dtype == torch.float32 and g_loss.is_contiguous()) else g_loss.float().contiguous()
+        grad = torch.empty_like(image) if (rows == H and not dyn) else torch.zeros_like(image)
+        grad_e = e_partials = None
+        if ctx.expo:
+            grad_e = (torch.empty if rows > 0 else torch.zeros)((3, 4), dtype=torch.float32, device=dev)
+            ne = lib.gsr_l1_ssim_exposure_num_partials(rows, W)
+            e_partials = torch.empty((max(ne, 1), 12), dtype=torch.float32, device=dev)
+        off = 0 if dyn else 4 * y0 * W
+        if rows > 0:
+            with _on(dev), kernel_timer.range("l1_ssim_backward", Px=rows * W):
+                check(lib.gsr_l1_ssim_backward_masked(C, rows, W, ctypes.c_void_p(image.data_ptr() + off), H * W,
+                                                      _ptr(gt_u8), _ptr(mask_u8), _ptr(maps[0]), _ptr(maps[1]),
+                                                      _ptr(maps[2]), _ptr(g_loss), _ptr(g_loss), float(ctx.coef[0]),
+                                                      float(ctx.coef[1]), ctypes.c_void_p(grad.data_ptr() + off), H * W,
+                                                      _ptr(ctx.band_rows), _ptr(exposure) if ctx.expo else None,
+                                                      _ptr(e_partials) if ctx.expo else None,
+                                                      _ptr(grad_e) if ctx.expo else None, _stream()),
+                      "gsr_l1_ssim_backward_masked")
+        return grad, None, None, None, None, None, None, None, grad_e
+
+
+def fused_band_loss_masked(image, gt_u8, mask_u8, y0, y1, lambda_dssim, n, band_rows=None, exposure=None):
+    """fused_band_loss of the masked band: x' = m x (with `exposure` = [A | b], float32 [3,4] on the device:
+    x' = m (A x + b)), y' = m gt / 255, m = mask_u8 / 255 -- uint8 [rows, W] or [1, rows, W], one byte per pixel shared by
+    the channels, laid out like one channel of gt_u8 (include/gsraster.h, N1m) -> (loss, Ll1, ssim), with gradients for
+    `image` and, when given, `exposure`.  n = H*W*3 of the full image, masked or not."""
+    return _FusedBandLossMasked.apply(image, gt_u8, mask_u8, int(y0), int(y1), float(lambda_dssim), float(n), band_rows,
+                                      exposure)
+
+
 # ------------------------------------------------------------------------- a19: fused activations
 # ------------------------------------------------------------------------------- N1e: evaluation metrics
 METRICS_QUANTIZE, METRICS_NO_SSIM = 1, 2  # include/gsraster.h: GSR_METRICS_*

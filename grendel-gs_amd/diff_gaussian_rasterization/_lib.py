@@ -63,6 +63,11 @@ SIGNATURES = {
     "gsr_l1_ssim_backward_exposure": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int64,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_l1_ssim_forward_masked": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_l1_ssim_backward_masked": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int64,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_stamp": (c_int, [c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
     "gsr_band_mask": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gsr_l1_ssim_finalize": (c_int, [c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),

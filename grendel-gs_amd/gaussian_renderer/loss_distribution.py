@@ -13,6 +13,7 @@ normalised by the FULL image's pixel count, so that the per-rank partial losses 
 the full-image loss up to the band-border SSIM term.
 """
 import math
+import os
 
 import torch
 import torch.distributed as dist
@@ -26,6 +27,7 @@ from diff_gaussian_rasterization import capturing as _capturing
 from diff_gaussian_rasterization import current_stream as _current_stream
 from diff_gaussian_rasterization import fused_band_loss as _FUSED_LOSS
 from diff_gaussian_rasterization import fused_band_loss_exposure as _FUSED_LOSS_EXPOSURE
+from diff_gaussian_rasterization import fused_band_loss_masked as _FUSED_LOSS_MASKED
 from diff_gaussian_rasterization import fused_l1_ssim_band as _FUSED
 
 
@@ -52,11 +54,23 @@ def _band_of(camera, l, r, device):
     """uint8 rows [l * 16, min(r * 16, H)) of the camera's ground truth, dense, on `device`.  When the image already
     lives on the device (preload_dataset_to_gpu, scene/cameras.py:66-69) the dense band is a strided-slice copy kernel
     per iteration: the last few bands of a camera are kept (a converged partition asks for the same rows again)."""
+    return _rows_of(camera, camera.original_image_backup, "_gsr_bands", l, r, device)
+
+
+def _mask_band_of(camera, l, r, device):
+    """the same rows of the camera's loss mask (alpha_mask_backup, uint8 [H, W] or [1, H, W]) as [1, rows, W], staged and
+    cached exactly like the ground truth's band"""
+    src = camera.alpha_mask_backup
+    if src.dtype != torch.uint8 or src.dim() not in (2, 3) or (src.dim() == 3 and src.shape[0] != 1):
+        raise ValueError(f"alpha_mask_backup must be uint8 [H, W] or [1, H, W], got {src.dtype} {tuple(src.shape)}")
+    return _rows_of(camera, src if src.dim() == 3 else src.unsqueeze(0), "_gsr_mask_bands", l, r, device)
+
+
+def _rows_of(camera, src, cache_name, l, r, device):
     y0, y1 = get_coverage_y_min_max(l, r)
-    src = camera.original_image_backup
     if not src.is_cuda:
         return src[:, y0:y1, :].to(device, non_blocking=True).contiguous()
-    cache = getattr(camera, "_gsr_bands", None)
+    cache = getattr(camera, cache_name, None)
     key = (y0, y1, src.data_ptr(), src._version)
     if cache is None or (cache and cache[0][0][2:] != key[2:]):  # entries are (key, band): another image / new contents
         cache = []
@@ -66,26 +80,71 @@ def _band_of(camera, l, r, device):
     band = src[:, y0:y1, :].to(device, non_blocking=True).contiguous()
     cache = [(key, band)] + cache[:3]
     try:
-        camera._gsr_bands = cache
+        setattr(camera, cache_name, cache)
     except AttributeError:
         pass
     return band
 
 
+# ------------------------------------------------------------------------------- loss masks (opt-in)
+_LOSS_MASKS = [os.environ.get("GSR_LOSS_MASKS", "0") == "1"]
+
+
+def set_loss_masks(on):
+    """Per-pixel loss masks (include/gsraster.h, N1m; GSR_LOSS_MASKS=1 sets the default), off unless asked for.  With the
+    switch on, a camera that carries `alpha_mask_backup` (uint8 [H, W] or [1, H, W]: 255 = the pixel counts, 0 = ignore it,
+    in between a weight) gets the rows of its band staged into camera.alpha_mask by load_camera_from_cpu_to_all_gpu --
+    the same rows, cache and (under distributed_dataset_storage) one more send / receive per task as original_image --
+    and batched_loss_computation takes the loss of m x against m gt inside the fused kernels (fused_band_loss_masked,
+    with the camera's exposure when a model is set); n stays H*W*3.  A camera without a mask, or the switch off, takes
+    the unmasked path call for call.  final_system_loss_computation and evaluation stay unmasked (as they stay
+    uncompensated under an exposure model).  A graphed iteration refuses to capture while the switch is on and a camera
+    of the batch carries a mask (graphed_step.py)."""
+    _LOSS_MASKS[0] = bool(on)
+
+
+def get_loss_masks():
+    return _LOSS_MASKS[0]
+
+
+def camera_carries_mask(camera):
+    """whether the camera has a loss mask SOMEWHERE: alpha_mask_backup on the ranks that hold its pixels; on a rank that
+    holds none (distributed_dataset_storage) the dataset sets camera.has_alpha_mask, which wins when present -- every
+    rank has to give the same answer, the sends and receives are paired by it"""
+    flag = getattr(camera, "has_alpha_mask", None)
+    if flag is not None:
+        return bool(flag)
+    return getattr(camera, "alpha_mask_backup", None) is not None
+
+
+def _set_mask(camera, band):
+    try:
+        camera.alpha_mask = band
+    except AttributeError:
+        if band is not None:
+            raise
+
+
 def load_camera_from_cpu_to_all_gpu(batched_cameras, batched_strategies, gpuid2tasks):
     """camera.original_image <- exactly the uint8 ground-truth rows [row_l*16, min(row_r*16, H)) this rank
     renders.  With `distributed_dataset_storage` only the first rank of a node holds the images and
-    sends the other ranks their bands over xGMI (batched isend/irecv)."""
+    sends the other ranks their bands over xGMI (batched isend/irecv).  With set_loss_masks(True),
+    camera.alpha_mask <- the same rows of alpha_mask_backup as [1, rows, W] (None for a camera without a mask)."""
     args = utils.get_args()
     dev = _device()
     me = utils.GLOBAL_RANK
     if not args.distributed_dataset_storage or args.local_sampling or utils.DEFAULT_GROUP.size() == 1:
         for (k, l, r) in gpuid2tasks[me]:
             batched_cameras[k].original_image = _band_of(batched_cameras[k], l, r, dev)
+        if _LOSS_MASKS[0]:
+            for (k, l, r) in gpuid2tasks[me]:
+                cam = batched_cameras[k]
+                _set_mask(cam, _mask_band_of(cam, l, r, dev) if camera_carries_mask(cam) else None)
         return
 
     root = utils.get_first_rank_on_cur_node()
-    ops, bufs = [], []
+    masks_on = _LOSS_MASKS[0]
+    ops, bufs, mbufs = [], [], []
     if me == root:
         node = range(root, root + utils.IN_NODE_GROUP.size())
         for g in node:
@@ -95,17 +154,32 @@ def load_camera_from_cpu_to_all_gpu(batched_cameras, batched_strategies, gpuid2t
                     bufs.append((k, band))
                 else:
                     ops.append(dist.P2POp(dist.isend, band, g))
+                if masks_on and camera_carries_mask(batched_cameras[k]):  # right behind the task's image, on both sides
+                    mband = _mask_band_of(batched_cameras[k], l, r, dev)
+                    if g == me:
+                        mbufs.append((k, mband))
+                    else:
+                        ops.append(dist.P2POp(dist.isend, mband, g))
     else:
         for (k, l, r) in gpuid2tasks[me]:
             y0, y1 = get_coverage_y_min_max(l, r)
             buf = torch.empty((3, y1 - y0, utils.IMG_W), dtype=torch.uint8, device=dev)
             bufs.append((k, buf))
             ops.append(dist.P2POp(dist.irecv, buf, root))
+            if masks_on and camera_carries_mask(batched_cameras[k]):
+                mbuf = torch.empty((1, y1 - y0, utils.IMG_W), dtype=torch.uint8, device=dev)
+                mbufs.append((k, mbuf))
+                ops.append(dist.P2POp(dist.irecv, mbuf, root))
     if ops:
         for req in dist.batch_isend_irecv(ops):
             req.wait()
     for k, band in bufs:
         batched_cameras[k].original_image = band
+    if masks_on:
+        for (k, l, r) in gpuid2tasks[me]:
+            _set_mask(batched_cameras[k], None)
+        for k, mband in mbufs:
+            _set_mask(batched_cameras[k], mband)
 
 
 def load_camera_from_cpu_to_all_gpu_for_eval(batched_cameras, batched_strategies, gpuid2tasks):
@@ -162,7 +236,8 @@ def _timings_wanted():
 
 def final_system_loss_computation(image, viewpoint_cam, compute_locally, strategy, statistic_collector):
     """-> (Ll1, ssim) partial sums of this rank's row band, each / (H * W * 3); fills
-    statistic_collector["forward_loss_time"] (ms) for the load balancer."""
+    statistic_collector["forward_loss_time"] (ms) for the load balancer.  Unmasked and uncompensated, whatever
+    set_loss_masks / set_exposure_model say (those act on batched_loss_computation only)."""
     assert utils.GLOBAL_RANK in strategy.gpu_ids, "The current gpu must be used to render this camera."
     j = strategy.gpu_ids.index(utils.GLOBAL_RANK)
     y0, y1 = get_coverage_y_min_max(strategy.division_pos[j], strategy.division_pos[j + 1])
@@ -225,7 +300,12 @@ def batched_loss_computation(batched_image, batched_cameras, batched_compute_loc
             if cap is not None:  # (a hipGraph capture: device timestamps instead of events, graphed_step.py)
                 cap.stamp("loss0", id(stats))
             model = _EXPOSURE_MODEL[0]
-            if model is None:
+            mask_band = getattr(camera, "alpha_mask", None) if _LOSS_MASKS[0] else None
+            if mask_band is not None:
+                loss, Ll1, ssim = _FUSED_LOSS_MASKED(image, camera.original_image, mask_band, y0, y1, args.lambda_dssim,
+                                                     utils.get_num_pixels() * 3, band_rows,
+                                                     None if model is None else model.of(camera))
+            elif model is None:
                 loss, Ll1, ssim = _FUSED_LOSS(image, camera.original_image, y0, y1, args.lambda_dssim,
                                               utils.get_num_pixels() * 3, band_rows)
             else:

@@ -568,6 +568,14 @@ class GraphedIteration:
             raise RuntimeError("GraphedIteration: an exposure model is set (loss_distribution.set_exposure_model); "
                                "exposure compensation is not captured -- run it eagerly "
                                "(GraphedIteration(..., enabled=False) or call the body directly)")
+        from gaussian_renderer.loss_distribution import camera_carries_mask, get_loss_masks
+
+        if get_loss_masks() and any(camera_carries_mask(c) for c in cameras):
+            # the captured capacity buffers carry the ground truth only; the loss kernels take a device band's mask already
+            # (gsr_l1_ssim_*_masked), staging it into the capture is a follow-up: nothing is warmed up or captured
+            raise RuntimeError("GraphedIteration: loss masks are on (loss_distribution.set_loss_masks) and a camera of the "
+                               "batch carries alpha_mask_backup; masked losses are not captured -- run it eagerly "
+                               "(GraphedIteration(..., enabled=False) or call the body directly)")
         from gaussian_renderer import get_filter3d
 
         if get_filter3d():

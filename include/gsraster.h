@@ -590,6 +590,50 @@ int gsr_l1_ssim_backward_exposure(int channels, int rows_capacity, int width, co
                                   float *exposure_partials, float *grad_exposure, gsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N1m  per-pixel loss masks fused into N1 / N1x (new symbols of ABI 15; nothing above changes).  `mask`: one uint8 per
+ * pixel, shared by the channels, laid out like ONE channel of the ground-truth band: [rows, width] in the static form,
+ * [rows_capacity, width] with the band in its first rows in the device-band form.  m = byte * (1/255f) in fp32: exactly 1
+ * for byte 255, exactly 0 for byte 0, within 1.5 ulp of byte / 255 in between.  For every pixel INSIDE the band
+ *   x' = m x          (with an exposure E = [A | b]:  x' = m (A x + b), A x + b formed as in N1x)
+ *   y' = m (gt * (1/255f))
+ * and outside the band x' = y' = 0 (the zero padding of N1).  Everything behind that is N1 on (x', y'): the L1 sum, the
+ * SSIM map and the maps dm_* keep their form, n = H * W * 3 of the full image and gsr_l1_ssim_finalize are unchanged
+ * (the loss is NOT renormalised by the mask's pixel count).  Both images are multiplied (gsplat's `masks`); the official
+ * trainer's `image *= alpha_mask` is the same loss wherever the ground truth is already black under the mask.
+ * Backward, with g' = dL/dx' (N1's formula evaluated at (x', y')):
+ *   dL/dx = m g'        with an exposure:  dL/dx[k] = m sum_c A[c][k] g'[c],
+ *                       dL/dA[c][k] = sum_pixels m g'[c] x[k],  dL/db[c] = sum_pixels m g'[c].
+ * Two exact properties:
+ *  1. An all-255 mask gives, bit for bit, the partial sums, the three maps, the image gradient and (with an exposure)
+ *     the exposure gradient of the corresponding unmasked launch (gsr_l1_ssim_forward / _backward, their _band forms,
+ *     the _exposure pair): m = 1 enters as single multiplications, and the masked backward rounds every product and
+ *     sum of g' on its own, which is what the unmasked kernels' code does.
+ *  2. Where m = 0 the gradient is exactly +0 and no output bit depends on the finite value of x there.
+ * No reference call site (the reference has no loss mask); the arbiter is the fp64 torch restatement of the lines above
+ * (tests/masked_loss_refs.py).
+ *
+ * gsr_l1_ssim_forward_masked: the arguments of gsr_l1_ssim_forward_exposure plus `mask` behind `gt`.  band_rows == NULL
+ * selects the static form (`image` points at the band's first row, rows_capacity is the row count); exposure == NULL
+ * means no exposure (any channel count).  The mask is fetched four bytes at a time when its base pointer is 4-byte
+ * aligned and width % 4 == 0 (and the image / gt allow the vector path); otherwise the launch takes the scalar path --
+ * the results are the same bits.  Partials: layout and count of the plain launch of the same shape.
+ * gsr_l1_ssim_backward_masked: the arguments of gsr_l1_ssim_backward_exposure plus `mask` behind `gt`;
+ * exposure_partials / grad_exposure are looked at only with an exposure.  grad_image: the band's rows, fully written.
+ * GSR_EINVAL before any device work: a null mask, channels / rows_capacity / width <= 0, an exposure with channels != 3
+ * (backward: or without exposure_partials / grad_exposure), or any null pointer the unmasked launch refuses. */
+int gsr_l1_ssim_forward_masked(int channels, int rows_capacity, int width, const float *image,
+                               int64_t image_channel_stride, const uint8_t *gt, const uint8_t *mask, float *partials,
+                               float *dm_dmu1, float *dm_dE11, float *dm_dE12, const int32_t *band_rows,
+                               const float *exposure, gsr_stream_t stream);
+int gsr_l1_ssim_backward_masked(int channels, int rows_capacity, int width, const float *image,
+                                int64_t image_channel_stride, const uint8_t *gt, const uint8_t *mask,
+                                const float *dm_dmu1, const float *dm_dE11, const float *dm_dE12,
+                                const float *grad_l1_sum, const float *grad_ssim_sum, float scale_l1, float scale_ssim,
+                                float *grad_image, int64_t grad_channel_stride, const int32_t *band_rows,
+                                const float *exposure, float *exposure_partials, float *grad_exposure,
+                                gsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N1e  fused evaluation metrics of one row band, forward only -- what training_report prints
  * (train_internal.py:471-478: clamp both, l1_loss(...).mean(), psnr(...).mean()), the per-channel PSNR of
  * utils/image_utils.py:19-21, and the SSIM / PSNR metrics.py:78-79 takes of the saved PNGs -- as SUMS over the rows
