@@ -31,7 +31,8 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "_C", "load_im
            "merge_image_tiles_by_pos", "set_timing_mode", "fused_l1_ssim_band", "fused_band_loss", "fused_band_loss_exposure", "fused_activations", "pack_camera",
            "preprocess_gaussians_raw_batched", "knn_mean_dist2", "group_rows", "gather_rows", "densify_plan", "densify_move", "exchange_need",
            "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "absgrad_rows", "densify_stats",
-           "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing", "image_metrics", "metrics_from_sums"]
+           "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing", "image_metrics", "metrics_from_sums",
+           "bilagrid_slice", "bilagrid_tv"]
 
 BLOCK_X, BLOCK_Y, ONE_DIM_BLOCK_SIZE = 16, 16, 256
 
@@ -2102,6 +2103,97 @@ def fused_band_loss_masked(image, gt_u8, mask_u8, y0, y1, lambda_dssim, n, band_
     `image` and, when given, `exposure`.  n = H*W*3 of the full image, masked or not."""
     return _FusedBandLossMasked.apply(image, gt_u8, mask_u8, int(y0), int(y1), float(lambda_dssim), float(n), band_rows,
                                       exposure)
+
+
+# ------------------------------------------------------------------------------- N1g: bilateral-grid colour correction
+def _bilagrid_sizes(grid, what):
+    if grid.dim() != 4 or grid.shape[0] != 12:
+        raise ValueError(f"{what}: a grid is [12, L, GH, GW], got {tuple(grid.shape)}")
+    gl, gh, gw = (int(s) for s in grid.shape[1:])
+    if not (2 <= gl <= 16 and 2 <= gh <= 64 and 2 <= gw <= 64):
+        raise ValueError(f"{what}: grid sizes (GW, GH, L) = ({gw}, {gh}, {gl}) outside 2..64, 2..64, 2..16")
+    return gw, gh, gl
+
+
+class _BilagridSlice(torch.autograd.Function):
+    """x' = A_M c + b_M of the rows [y0, y1) of a rendered image, M the trilinear sample of one camera's bilateral grid at
+    (pixel position, luminance of c) -- include/gsraster.h, N1g: one launch forward, two backward (pieces of xy-cells +
+    the fixed-order fp64 finalize of the lattice gradient)."""
+
+    @staticmethod
+    def forward(ctx, image, grid, y0, y1, height):
+        if not image.is_cuda or not grid.is_cuda:
+            raise RuntimeError("bilagrid_slice: device tensors required (no CPU fallback)")
+        if image.dim() != 3 or image.shape[0] != 3:
+            raise ValueError(f"bilagrid_slice: the image must be [3, H, W], got {tuple(image.shape)}")
+        gw, gh, gl = _bilagrid_sizes(grid, "bilagrid_slice")
+        image, grid = image.float().contiguous(), grid.float().contiguous()
+        _, H, W = image.shape
+        if H != height:
+            raise ValueError(f"bilagrid_slice: the image has {H} rows, `height` says {height}")
+        if not 0 <= y0 <= y1 <= H:
+            raise ValueError(f"bilagrid_slice: rows [{y0}, {y1}) outside an image of {H} rows")
+        dev = image.device
+        # the rows outside the band are cleared, not left undefined: the loss kernels never read them (their zero
+        # padding at a band's edge is a padding, DESIGN.md 3.15), but the tensor is handed to the caller
+        out = torch.empty_like(image) if (y0 == 0 and y1 == H) else zeros_async(image.shape, torch.float32, dev)
+        with _on(dev), kernel_timer.range("bilagrid_forward", Px=(y1 - y0) * W):
+            check(lib.gsr_bilagrid_slice_forward(W, H, y0, y1, _ptr(image), H * W, _ptr(grid), gw, gh, gl, _ptr(out),
+                                                 H * W, _stream()), "gsr_bilagrid_slice_forward")
+        ctx.band = (y0, y1)
+        ctx.save_for_backward(image, grid)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        image, grid = ctx.saved_tensors
+        gw, gh, gl = (int(s) for s in reversed(grid.shape[1:]))
+        _, H, W = image.shape
+        y0, y1 = ctx.band
+        dev = image.device
+        g_out = g_out if (g_out.dtype == torch.float32 and g_out.is_contiguous()) else g_out.float().contiguous()
+        grad = torch.empty_like(image) if (y0 == 0 and y1 == H) else zeros_async(image.shape, torch.float32, dev)
+        grad_grid = torch.empty_like(grid)
+        partials = torch.empty((max(int(lib.gsr_bilagrid_num_partials(W, H, gw, gh, gl)), 1),), dtype=torch.float32,
+                               device=dev)
+        with _on(dev), kernel_timer.range("bilagrid_backward", Px=(y1 - y0) * W):
+            check(lib.gsr_bilagrid_slice_backward(W, H, y0, y1, _ptr(image), H * W, _ptr(grid), gw, gh, gl, _ptr(g_out),
+                                                  H * W, _ptr(grad), H * W, _ptr(partials), _ptr(grad_grid), _stream()),
+                  "gsr_bilagrid_slice_backward")
+        return grad, grad_grid, None, None, None
+
+
+def bilagrid_slice(image, grid, y0, y1, height):
+    """-> the colour-corrected image [3, H, W]: rows [y0, y1) hold x' = A_M c + b_M with M sampled from `grid`
+    ([12, L, GH, GW] float32 on the device, one camera's) at the pixel's position in the FULL image of `height` rows and
+    at the luminance of its colour; the other rows are zero.  Gradients for `image` and `grid`."""
+    return _BilagridSlice.apply(image, grid, int(y0), int(y1), int(height))
+
+
+def bilagrid_tv(grids, weight, grad=None, value=False):
+    """adds weight * dT/dG to `grad` (default: a fresh zero tensor), T the total variation of `grids` [N, 12, L, GH, GW]
+    (include/gsraster.h, N1g), in one launch -> grad, or (grad, T) with value=True (T a float32 device scalar, reduced in
+    fp64 in a fixed order by one more launch)"""
+    if not grids.is_cuda:
+        raise RuntimeError("bilagrid_tv: device tensors required (no CPU fallback)")
+    if grids.dim() != 5:
+        raise ValueError(f"bilagrid_tv: grids are [N, 12, L, GH, GW], got {tuple(grids.shape)}")
+    gw, gh, gl = _bilagrid_sizes(grids[0], "bilagrid_tv")
+    g = grids.detach()
+    g = g if (g.dtype == torch.float32 and g.is_contiguous()) else g.float().contiguous()
+    dev, N = g.device, int(g.shape[0])
+    if grad is None:
+        grad = zeros_async(g.shape, torch.float32, dev)
+    elif grad.dtype != torch.float32 or not grad.is_contiguous() or grad.shape != g.shape or grad.device != dev:
+        raise ValueError("bilagrid_tv: `grad` must be a contiguous float32 device tensor of the grids' shape")
+    T = partials = None
+    if value:
+        T = torch.empty((), dtype=torch.float32, device=dev)
+        partials = torch.empty((max(lib.gsr_bilagrid_tv_num_partials(N, gw, gh, gl), 1),), dtype=torch.float64, device=dev)
+    with _on(dev), kernel_timer.range("bilagrid_tv"):
+        check(lib.gsr_bilagrid_tv(N, gw, gh, gl, _ptr(g), float(weight), _ptr(grad), _ptr(partials), _ptr(T), _stream()),
+              "gsr_bilagrid_tv")
+    return (grad, T) if value else grad
 
 
 # ------------------------------------------------------------------------- a19: fused activations

@@ -170,6 +170,13 @@ SIGNATURES = {
     "gsr_filter3d_finalize": (c_int, [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_float, c_void_p, c_void_p]),
     "gsr_filter3d_apply_forward": (c_int, [c_int] + [c_void_p] * 6),
     "gsr_filter3d_apply_backward": (c_int, [c_int] + [c_void_p] * 8),
+    "gsr_bilagrid_slice_forward": (c_int, [c_int] * 4 + [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p,
+                                           c_int64, c_void_p]),
+    "gsr_bilagrid_num_partials": (c_int64, [c_int] * 5),
+    "gsr_bilagrid_slice_backward": (c_int, [c_int] * 4 + [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p,
+                                            c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gsr_bilagrid_tv_num_partials": (c_int, [c_int] * 4),
+    "gsr_bilagrid_tv": (c_int, [c_int] * 4 + [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 ABI_VERSION = 15

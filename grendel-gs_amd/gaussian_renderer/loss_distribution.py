@@ -23,6 +23,7 @@ import utils.general_utils as utils
 # The fused HIP loss lives in this package's operator module.  A missing / unbuilt libgsraster.so makes this import
 # raise; there is no torch / conv2d restatement of the loss in the product (oracle/loss_oracle.py holds one for the
 # tests, pinned on the reference's own pixelwise_l1_with_mask / pixelwise_ssim_with_mask).
+from diff_gaussian_rasterization import bilagrid_slice as _BILAGRID_SLICE
 from diff_gaussian_rasterization import capturing as _capturing
 from diff_gaussian_rasterization import current_stream as _current_stream
 from diff_gaussian_rasterization import fused_band_loss as _FUSED_LOSS
@@ -220,11 +221,36 @@ def set_exposure_model(model):
     x' = A x + b with model.of(camera) (fused into the loss kernels: fused_band_loss_exposure) and the backward fills the
     model's gradient; with None (the default) the path is the plain one, call for call.  final_system_loss_computation
     and evaluation stay uncompensated.  A graphed iteration refuses to capture while a model is set (graphed_step.py)."""
+    if model is not None and _BILATERAL_GRID[0] is not None:
+        raise ValueError(_BOTH_COLOUR_MODELS)
     _EXPOSURE_MODEL[0] = model
 
 
 def get_exposure_model():
     return _EXPOSURE_MODEL[0]
+
+
+_BILATERAL_GRID = [None]
+_BOTH_COLOUR_MODELS = ("an exposure model (loss_distribution.set_exposure_model) and a bilateral grid "
+                       "(loss_distribution.set_bilateral_grid) cannot both be set: the grid contains the exposure's affine "
+                       "transform; set one of them to None first")
+
+
+def set_bilateral_grid(model):
+    """model (bilagrid.BilateralGridModel) or None.  With a model, batched_loss_computation passes every camera's rendered
+    band through diff_gaussian_rasterization.bilagrid_slice with model.of(camera) and the rank's rows, then calls the loss
+    it would have called, plain or masked (a mask therefore applies to the corrected image), and the backward fills the
+    model's gradient; with None (the default) the path is the plain one, call for call.  ValueError while an exposure
+    model is set (and set_exposure_model refuses while a grid is set): the grid contains the affine transform.
+    final_system_loss_computation and evaluation stay uncorrected.  A graphed iteration refuses to capture while a
+    model is set (graphed_step.py)."""
+    if model is not None and _EXPOSURE_MODEL[0] is not None:
+        raise ValueError(_BOTH_COLOUR_MODELS)
+    _BILATERAL_GRID[0] = model
+
+
+def get_bilateral_grid():
+    return _BILATERAL_GRID[0]
 
 
 def _timings_wanted():
@@ -299,6 +325,11 @@ def batched_loss_computation(batched_image, batched_cameras, batched_compute_loc
             cap = _capturing()
             if cap is not None:  # (a hipGraph capture: device timestamps instead of events, graphed_step.py)
                 cap.stamp("loss0", id(stats))
+            if _BILATERAL_GRID[0] is not None:
+                if band_rows is not None:
+                    raise RuntimeError("batched_loss_computation: the bilateral grid takes its band from the host; a "
+                                       "band that is device data (a graphed iteration) is not supported")
+                image = _BILAGRID_SLICE(image, _BILATERAL_GRID[0].of(camera), y0, y1, image.shape[1])
             model = _EXPOSURE_MODEL[0]
             mask_band = getattr(camera, "alpha_mask", None) if _LOSS_MASKS[0] else None
             if mask_band is not None:

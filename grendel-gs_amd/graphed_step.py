@@ -568,6 +568,14 @@ class GraphedIteration:
             raise RuntimeError("GraphedIteration: an exposure model is set (loss_distribution.set_exposure_model); "
                                "exposure compensation is not captured -- run it eagerly "
                                "(GraphedIteration(..., enabled=False) or call the body directly)")
+        from gaussian_renderer.loss_distribution import get_bilateral_grid
+
+        if get_bilateral_grid() is not None:
+            # a replay would have to read the camera's grid, and the slice its band, as device data (left out, DESIGN.md
+            # 3.15): nothing is warmed up or captured
+            raise RuntimeError("GraphedIteration: a bilateral-grid model is set (loss_distribution.set_bilateral_grid); "
+                               "the colour correction is not captured -- run it eagerly "
+                               "(GraphedIteration(..., enabled=False) or call the body directly)")
         from gaussian_renderer.loss_distribution import camera_carries_mask, get_loss_masks
 
         if get_loss_masks() and any(camera_carries_mask(c) for c in cameras):

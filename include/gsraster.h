@@ -1122,6 +1122,53 @@ int gsr_filter3d_apply_backward(int N, const float *scaling, const float *opacit
                                 const float *g_scaling, const float *g_opacity, float *d_scaling, float *d_opacity,
                                 gsr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * N1g  bilateral-grid colour correction per training image (Wang et al., "Bilateral Guided Radiance Field Processing").
+ * There is no reference call site (the reference has no such model); the arbiter is the fp64 torch restatement of the
+ * lines below (tests/bilagrid_refs.py).  New symbols only: gsr_abi_version does not move.
+ *
+ * One camera's grid G[12][gl][gh][gw], float32, 2 <= gl <= 16, 2 <= gh, gw <= 64; coefficient j = 4c + k is entry [c][k]
+ * of a row-major [3,4] matrix [A | b].  For the pixel (x, y) of a width x height image with colour c = (r, g, b):
+ *       px = (x + 0.5) / width * (gw - 1),   py = (y + 0.5) / height * (gh - 1),
+ *       pz = clamp(0.299 r + 0.587 g + 0.114 b, 0, 1) * (gl - 1)      (products and sums rounded one by one, in this order),
+ *       M  = the trilinear sample of the 12 planes: lower node i0 = min(floor(p), size - 2), t = p - i0, every axis as
+ *            a + t (b - a) (x, then y, then z) -- grid_sample(bilinear, align_corners, border) of a 5-D input,
+ *       x' = A_M c + b_M        (no clamp; an identity grid returns c bit for bit).
+ * y is the row of the FULL image.  `image`, `out`, `grad_out`, `grad_image` point at row 0 of channel 0 of [3, height,
+ * width] images (rows dense, channels their stride apart); only the rows [y0, y1) are read or written.
+ *
+ * gsr_bilagrid_slice_forward: out <- x' for the rows of the band.
+ * gsr_bilagrid_slice_backward: with g' = grad_out,
+ *       grad_grid[j][node] = sum over the band's pixels of w_node g'_c (c_k, or 1 for k = 3)      (fully overwritten:
+ *            nodes no pixel of the band reaches get zeros),
+ *       grad_image[k] = sum_c A_M[c][k] g'_c + lum_k (gl - 1) D,    D = sum_j dM_j/dpz (g' (x) [c, 1])_j,
+ *            dM_j/dpz = the bilinear-in-xy sample of G[j][i0z + 1] - G[j][i0z],  D = 0 exactly where the luminance is
+ *            <= 0 or >= 1 (the band's rows, fully written).
+ *   A workgroup owns at most 32 x 32 pixels of one xy-cell and writes its 4 * gl * 12 corner sums once to `partials`
+ *   (gsr_bilagrid_num_partials(...) floats, scratch, fully written); a second launch adds the rows around each node in a
+ *   fixed order in fp64 and rounds once.  No floating-point atomics: the same bits on every run.
+ * gsr_bilagrid_num_partials: pure host arithmetic; 0 for sizes the launches refuse.
+ * Both: GSR_EINVAL before any device work for a null pointer, grid sizes out of range, width or height <= 0 (or > 2^24),
+ * y0 < 0, y1 > height, y0 > y1.  An empty band (y0 == y1) launches nothing, except that the backward clears grad_grid. */
+int gsr_bilagrid_slice_forward(int width, int height, int y0, int y1, const float *image, int64_t image_channel_stride,
+                               const float *grid, int gw, int gh, int gl, float *out, int64_t out_channel_stride,
+                               gsr_stream_t stream);
+int64_t gsr_bilagrid_num_partials(int width, int height, int gw, int gh, int gl);
+int gsr_bilagrid_slice_backward(int width, int height, int y0, int y1, const float *image, int64_t image_channel_stride,
+                                const float *grid, int gw, int gh, int gl, const float *grad_out,
+                                int64_t grad_out_channel_stride, float *grad_image, int64_t grad_image_channel_stride,
+                                float *partials, float *grad_grid, gsr_stream_t stream);
+/* Total variation of num_grids grids [num_grids][12][gl][gh][gw]:
+ *       T = (1 / num_grids) sum over the axes z, y, x of mean((G shifted by one along the axis - G)^2),
+ * the mean over the 12 (size_axis - 1) (other two sizes) differences of one grid.  gsr_bilagrid_tv ADDS weight * dT/dG to
+ * `grad` (same shape) in one launch.  value != NULL: also *value = T, the per-workgroup sums in fp64 through `partials`
+ * (gsr_bilagrid_tv_num_partials(...) doubles) and one more single-workgroup launch that adds them in a fixed order;
+ * value and partials are given together or not at all.  GSR_EINVAL before any device work: num_grids <= 0, sizes out of
+ * range, a null grids / grad, one of value / partials without the other.  The optimizer step is gsr_adam_step. */
+int gsr_bilagrid_tv_num_partials(int num_grids, int gw, int gh, int gl);
+int gsr_bilagrid_tv(int num_grids, int gw, int gh, int gl, const float *grids, float weight, float *grad,
+                    double *partials, float *value, gsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
