@@ -64,7 +64,8 @@ constexpr int XCHUNK = GSR_XCHUNK;  // Gaussians per wave-chunk: XCHUNK / 64 rou
 
 // rows [miny, maxy) of the 3-sigma tile rect of Gaussian r (the K2 rule) packed as miny | maxy << 16, or 0 when it
 // touches nothing (0 = the empty interval: no band test passes).  Both loads are unconditional, so that the loads of
-// several rounds can be in flight together (the radius no longer gates the load of the position).
+// several rounds can be in flight together (the radius no longer gates the load of the position).  16 bits a side: the
+// entry points refuse a frame of more than 65535 tile rows (tile_rows_fit).
 __device__ __forceinline__ uint32_t rect_rows_packed(int rad, float2 xy, int gx, int gy) {
     int minx, miny, maxx, maxy;
     gsr_get_rect(xy.x, xy.y, rad > 0 ? rad : 0, gx, gy, minx, miny, maxx, maxy);
@@ -302,6 +303,12 @@ scatter_add_rows_kernel(long long n, const int32_t *__restrict__ idx, const floa
 }
 }  // namespace
 
+// the count and pack kernels keep a row interval as miny | maxy << 16 (rect_rows_packed): a taller frame would wrap
+constexpr long long XCHG_MAX_TILE_ROWS = 65535;
+static bool tile_rows_fit(int height) {
+    return ((long long)height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y <= XCHG_MAX_TILE_ROWS;
+}
+
 extern "C" size_t gsr_exchange_chunks(int P) { return P <= 0 ? 0 : (size_t)gsr_div_up(P, XCHUNK); }
 
 extern "C" int gsr_exchange_count(int P, int B_total, int k0, int B, int W, int width, int height,
@@ -309,7 +316,7 @@ extern "C" int gsr_exchange_count(int P, int B_total, int k0, int B, int W, int 
                                   int32_t *chunkcnt, int32_t *counts, gsr_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (P < 0 || B < 1 || B > 65535 || k0 < 0 || k0 + B > B_total || W < 1 || W > 256 || W * B > 512 ||
-        width <= 0 || height <= 0 || !counts)
+        width <= 0 || height <= 0 || !tile_rows_fit(height) || !counts)
         return GSR_EINVAL;
     if (P == 0) {
         GSR_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)W * B, stream));
@@ -332,8 +339,8 @@ static int exchange_pack_impl(bool slab, int P, int B_total, int k0, int B, int 
                               const int32_t *layout, int64_t n_send, float *msg, int32_t *send_idx,
                               hipStream_t stream) {
     if (P < 0 || B < 1 || B > 65535 || k0 < 0 || k0 + B > B_total || W < 1 || W > 256 || W * B > 512 ||
-        width <= 0 || height <= 0 || n_send < 0 || !layout || count_cameras < B || count_first < 0 ||
-        k0 < count_first || k0 - count_first + B > count_cameras)
+        width <= 0 || height <= 0 || !tile_rows_fit(height) || n_send < 0 || !layout || count_cameras < B ||
+        count_first < 0 || k0 < count_first || k0 - count_first + B > count_cameras)
         return GSR_EINVAL;
     SegOffsets seg;
     if (slab) {  // layout = capacities: prefix sums give the segment starts, the total must be the buffer's row count
@@ -384,7 +391,7 @@ extern "C" int gsr_exchange_pack(int P, int B_total, int k0, int B, int W, int w
                                  const int32_t *chunkcnt, const int32_t *segment_offsets, int64_t n_send, float *msg,
                                  int32_t *send_idx, gsr_stream_t stream_) {
     if (P == 0 || n_send == 0) {
-        if (P < 0 || n_send < 0 || !segment_offsets) return GSR_EINVAL;
+        if (P < 0 || n_send < 0 || !segment_offsets || !tile_rows_fit(height)) return GSR_EINVAL;
         return 0;
     }
     return exchange_pack_impl(false, P, B_total, k0, B, W, width, height, count_cameras, count_first, means2D, rgb,

@@ -2654,6 +2654,12 @@ def densify_stats(radii, grad, max_radii2D, accum, denom):
     if radii.dtype != torch.int32 or grad.dtype != torch.float32 or grad.dim() != 2 or grad.stride(1) != 1 or \
             any(t.dtype != torch.float32 or not t.is_contiguous() for t in (max_radii2D, accum, denom)):
         raise ValueError("densify_stats: int32 radii, float32 grad rows and dense float32 accumulators expected")
+    # gsr_densify_stats cannot check sizes: a buffer left over from before a densification event would be written
+    # past its end
+    if radii.dim() != 1 or grad.shape[0] != P or grad.shape[1] < 2 or max_radii2D.numel() != P or \
+            accum.shape[0] != P or accum.numel() != P or denom.shape[0] != P or denom.numel() != P:
+        raise ValueError(f"densify_stats: radii has {P} rows, but grad {tuple(grad.shape)}, max_radii2D "
+                         f"{tuple(max_radii2D.shape)}, accum {tuple(accum.shape)}, denom {tuple(denom.shape)}")
     with _on(radii.device):
         check(lib.gsr_densify_stats(P, _ptr(radii.contiguous()), _ptr(grad), grad.stride(0) if P > 1 else 2,
                                     _ptr(max_radii2D), _ptr(accum), _ptr(denom), _stream()), "gsr_densify_stats")

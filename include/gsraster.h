@@ -703,7 +703,10 @@ int gsr_exchange_need(int P, int B, int W, int width, int height, const float *m
  *       one pack launch per camera when the exchanges are pipelined);
  *   gsr_scatter_add_rows : dst[idx[r]][0:9] += src[r][0:9] -- the backward's mirror step on the gradient rows the
  *       peers send back (dst fp32 [rows][9], zeroed by the caller; a Gaussian needed by two bands is added twice);
- *       rows with idx[r] < 0 are skipped. */
+ *       rows with idx[r] < 0 are skipped.
+ * Tile-row limit: gsr_exchange_count, gsr_exchange_pack and gsr_exchange_pack_slab keep a Gaussian's tile-row interval
+ * in 16 + 16 bits, so they return GSR_EINVAL for a frame of more than 65535 tile rows (height > 65535 * 16 = 1 048 560
+ * pixels).  gsr_exchange_need keeps full ints and has no such limit. */
 size_t gsr_exchange_chunks(int P);
 int gsr_exchange_count(int P, int B_total, int k0, int B, int W, int width, int height, const float *means2D,
                        const int32_t *radii, const int32_t *bands, int32_t *chunkcnt, int32_t *counts,
