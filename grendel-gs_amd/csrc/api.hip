@@ -267,6 +267,34 @@ int gsr_depth_backward_means3d(int P, const int32_t *radii, const float *viewmat
                                        reinterpret_cast<hipStream_t>(stream));
 }
 
+int gsr_render_features(int P, int C, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                        const float *means2D, const float *conic_opacity, const float *features,
+                        const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi, float *out,
+                        gsr_stream_t stream) {
+    if (P < 0 || C < 1 || C > GSR_FEATURES_MAX || width <= 0 || height <= 0 || !out) return GSR_EINVAL;
+    // (point_list may be NULL: every list can be empty)
+    if (P > 0 && (!ranges || !means2D || !conic_opacity || !features || !compute_locally || !n_contrib)) return GSR_EINVAL;
+    return gsr_launch_composite_features(P, C, width, height, ranges, point_list, means2D, conic_opacity, features,
+                                         compute_locally, n_contrib, row_lo, row_hi, out,
+                                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_render_features_backward(int P, int C, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                                 const float *means2D, const float *conic_opacity, const float *features,
+                                 const uint8_t *compute_locally, const int32_t *n_contrib, const float *final_T,
+                                 const float *dL_dout, int row_lo, int row_hi, float *dL_record, float *dL_dfeatures,
+                                 double *acc64, gsr_stream_t stream) {
+    if (P < 0 || C < 1 || C > GSR_FEATURES_MAX || width <= 0 || height <= 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    // (dL_dfeatures may be NULL: the feature gradient is then not formed)
+    if (!ranges || !means2D || !conic_opacity || !features || !compute_locally || !n_contrib || !final_T || !dL_dout ||
+        !dL_record || !acc64)
+        return GSR_EINVAL;
+    return gsr_launch_composite_features_backward(P, C, width, height, ranges, point_list, means2D, conic_opacity,
+                                                  features, compute_locally, n_contrib, final_T, dL_dout, row_lo, row_hi,
+                                                  dL_record, dL_dfeatures, acc64, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gsr_render_absgrad(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
                        const float *means2D, const float *conic_opacity, const float *rgb,
                        const uint8_t *compute_locally, const float *bg, const float *final_T, const int32_t *n_contrib,

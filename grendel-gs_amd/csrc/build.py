@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 OUT_DIR = os.path.join(ROOT, "diff_gaussian_rasterization")
 SO = os.path.join(OUT_DIR, "libgsraster.so")
-UNITS = ["preprocess", "binning", "composite", "contrib", "invdepth", "absgrad", "loss", "bilagrid", "metrics", "optim", "activations", "filter3d", "knn", "compact", "mcmc", "exchange", "api"]
+UNITS = ["preprocess", "binning", "composite", "contrib", "invdepth", "features", "absgrad", "loss", "bilagrid", "metrics", "optim", "activations", "filter3d", "knn", "compact", "mcmc", "exchange", "api"]
 HEADERS = [os.path.join(HERE, "common.h"), os.path.join(HERE, "composite_math.h"), os.path.join(HERE, "radix.h"), os.path.join(HERE, "binning_persist.h"), os.path.join(HERE, "binning_rows.h"), os.path.join(HERE, "binning_host.h"),
            os.path.join(os.path.dirname(ROOT), "include", "gsraster.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall",

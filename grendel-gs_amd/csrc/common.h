@@ -205,6 +205,16 @@ int gsr_launch_composite_invdepth_backward(int P, int W, int H, const int32_t *r
                                            float *dL_record, double *acc64, hipStream_t stream);
 int gsr_launch_depth_to_means3D(int P, const int32_t *radii, const float *viewmatrix, const float *dL_ddepth,
                                 int row_stride, float *dL_dmeans3D, int overwrite, hipStream_t stream);
+int gsr_launch_composite_features(int P, int C, int W, int H, const int32_t *ranges, const uint32_t *point_list,
+                                  const float *means2D, const float *conic_opacity, const float *features,
+                                  const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi,
+                                  float *out, hipStream_t stream);
+int gsr_launch_composite_features_backward(int P, int C, int W, int H, const int32_t *ranges,
+                                           const uint32_t *point_list, const float *means2D,
+                                           const float *conic_opacity, const float *features,
+                                           const uint8_t *compute_locally, const int32_t *n_contrib,
+                                           const float *final_T, const float *dL_dout, int row_lo, int row_hi,
+                                           float *dL_record, float *dL_dfeatures, double *acc64, hipStream_t stream);
 int gsr_launch_composite_absgrad(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
                                  const float *means2D, const float *conic_opacity, const float *rgb,
                                  const uint8_t *compute_locally, const float *bg, const float *final_T,

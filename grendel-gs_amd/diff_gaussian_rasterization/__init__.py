@@ -1413,6 +1413,12 @@ class _RenderGaussians(torch.autograd.Function):
         if invd and _CAPTURE[0] is not None:
             raise RuntimeError("diff_gaussian_rasterization: cuda_args['invdepth'] is not available under graph capture "
                                "(the map needs the view's final lists)")
+        # opt-in: the same view tuple under a sibling key for render_features (an N-channel feature map, kernels of their
+        # own behind K8).  The pair count is then NOT deferred either
+        feat = bool(cuda_args.get("features")) if isinstance(cuda_args, dict) else False
+        if feat and _CAPTURE[0] is not None:
+            raise RuntimeError("diff_gaussian_rasterization: cuda_args['features'] is not available under graph capture "
+                               "(the map needs the view's final lists)")
         # opt-in: the backward launches the absolute-gradient kernel behind K10 (gsr_render_absgrad) and leaves its
         # [P,2] result in cuda_args.  The pair count stays deferred: the backward runs on final lists
         ctx.absgrad = bool(cuda_args.get("absgrad")) if isinstance(cuda_args, dict) else False
@@ -1430,7 +1436,7 @@ class _RenderGaussians(torch.autograd.Function):
                 # (round 6) the pair count is looked at AFTER K8 has been launched -- by the caller, after ALL its cameras
                 # have been launched, when it hands a list through cuda_args["_gsr_pending"] (gaussian_renderer.render_final)
                 point_list, ranges, D = bin_gaussians(means2D, depths, radii, conic_opacity, mask, W, H, cuda_args,
-                                                      defer=contrib is None and not invd)
+                                                      defer=contrib is None and not invd and not feat)
             pend = D if isinstance(D, PendingPairs) else None
             kt.meta["D"] = D = (0 if pend is not None else D)
             if kernel_timer.enabled:
@@ -1501,6 +1507,8 @@ class _RenderGaussians(torch.autograd.Function):
                                    band=(row_lo, row_hi))
             if invd:
                 cuda_args[_INVDEPTH_KEY] = (ranges, lists[0], mask, (row_lo, row_hi), final_T, n_contrib, W, H)
+            if feat:
+                cuda_args[_FEATURES_KEY] = (ranges, lists[0], mask, (row_lo, row_hi), final_T, n_contrib, W, H)
             if _CAPTURE[0] is not None:
                 _CAPTURE[0].stamp("fwd1", id(stats))
             ctx.seg = (seg_ws, seg_bytes, row_lo, row_hi)
@@ -1640,6 +1648,8 @@ class _RenderGaussians(torch.autograd.Function):
 
 _ABSGRAD_KEY = "_gsr_absgrad"  # where _RenderGaussians.backward leaves the [P,2] tensor when cuda_args["absgrad"] is set
 _INVDEPTH_KEY = "_gsr_invdepth"  # what _RenderGaussians leaves in cuda_args when cuda_args["invdepth"] is set
+_FEATURES_KEY = "_gsr_features"  # the same view tuple, left when cuda_args["features"] is set
+FEATURES_MAX = 256  # GSR_FEATURES_MAX of include/gsraster.h
 
 
 class _RenderInvDepth(torch.autograd.Function):
@@ -1682,6 +1692,56 @@ class _RenderInvDepth(torch.autograd.Function):
                                                    _ptr(final_T), _ptr(out), _ptr(g), band[0], band[1], _ptr(record),
                                                    _ptr(acc64), _stream()), "gsr_render_invdepth_backward")
         return record[:, 0:2], record[:, 2:6], record[:, 6], None
+
+
+class _RenderFeatures(torch.autograd.Function):
+    """an N-channel feature map of a view K8 has drawn (include/gsraster.h: gsr_render_features), from the colour render's
+    own lists, mask, band, final_T and n_contrib; backward: the two column groups of the [P,6] record and, when the
+    features require grad, dL/dfeatures [P,C] (otherwise the kernel does not form it)"""
+
+    @staticmethod
+    def forward(ctx, means2D, conic_opacity, features, view):
+        if _CAPTURE[0] is not None:
+            raise RuntimeError("diff_gaussian_rasterization: the feature map is not available under graph capture "
+                               "(it needs the view's final lists)")
+        ranges, point_list, mask, band, final_T, n_contrib, W, H = view
+        means2D, conic_opacity = _f32c(means2D, "means2D"), _f32c(conic_opacity, "conic_opacity")
+        features = _f32c(features, "features")
+        P = means2D.shape[0]
+        if conic_opacity.shape[0] != P or features.dim() != 2 or features.shape[0] != P:
+            raise ValueError(f"render_features: means2D, conic_opacity and features [P,C] must have the {P} rows of the "
+                             f"view")
+        C = int(features.shape[1])
+        if not 1 <= C <= FEATURES_MAX:
+            raise ValueError(f"render_features: C = {C} channels, the kernels take 1 .. {FEATURES_MAX}")
+        dev = means2D.device
+        out = torch.empty((C, H, W), dtype=torch.float32, device=dev)
+        with _on(dev), kernel_timer.range("composite_features", P=P, C=C):
+            check(lib.gsr_render_features(P, C, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D), _ptr(conic_opacity),
+                                          _ptr(features), _ptr(mask), _ptr(n_contrib), band[0], band[1], _ptr(out),
+                                          _stream()), "gsr_render_features")
+        ctx.view = view
+        ctx.feature_grad = bool(ctx.needs_input_grad[2])
+        ctx.save_for_backward(means2D, conic_opacity, features)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        means2D, conic_opacity, features = ctx.saved_tensors
+        ranges, point_list, mask, band, final_T, n_contrib, W, H = ctx.view
+        P, C = features.shape
+        dev = means2D.device
+        g = g.float().contiguous()
+        record = torch.empty((P, 6), dtype=torch.float32, device=dev)
+        d_feat = torch.empty((P, C), dtype=torch.float32, device=dev) if ctx.feature_grad else None
+        acc64 = torch.empty((P, 6 + C if ctx.feature_grad else 6), dtype=torch.float64, device=dev)
+        with _on(dev), kernel_timer.range("composite_features_backward", P=P, C=C):
+            check(lib.gsr_render_features_backward(P, C, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                                                   _ptr(conic_opacity), _ptr(features), _ptr(mask), _ptr(n_contrib),
+                                                   _ptr(final_T), _ptr(g), band[0], band[1], _ptr(record),
+                                                   _ptr(d_feat) if d_feat is not None else None, _ptr(acc64), _stream()),
+                  "gsr_render_features_backward")
+        return record[:, 0:2], record[:, 2:6], d_feat, None
 
 
 class _ViewDepths(torch.autograd.Function):
@@ -1782,6 +1842,19 @@ class GaussianRasterizer(nn.Module):
                 raise ValueError("render_invdepth: `means3D` needs the `radii` of the same rows")
             depths = _ViewDepths.apply(means3D, self.raster_settings.viewmatrix, depths, radii)
         return _RenderInvDepth.apply(means2D, conic_opacity, depths, view)
+
+    def render_features(self, means2D, conic_opacity, features, cuda_args):
+        """-> an N-channel feature map [C,H,W] of the view (extension of this build; include/gsraster.h:
+        gsr_render_features): per pixel and channel the sum of alpha T f[c] over what render_gaussians blended, no
+        background term, exactly 0 outside the locally computed tiles.  `features`: fp32 [P,C], 1 <= C <= FEATURES_MAX.
+        Call it after render_gaussians of the SAME view and rows with cuda_args["features"] set: the colour render leaves
+        its lists, mask, band, final_T and n_contrib in `cuda_args`.  Differentiable in means2D and conic_opacity (added
+        to K10's gradients by autograd) and in `features` when they require grad."""
+        view = cuda_args.get(_FEATURES_KEY) if isinstance(cuda_args, dict) else None
+        if view is None:
+            raise RuntimeError("render_features: call render_gaussians of the same view with cuda_args['features'] set "
+                               "first (it leaves the view's lists and n_contrib in cuda_args)")
+        return _RenderFeatures.apply(means2D, conic_opacity, features, view)
 
 
 # ------------------------------------------------------------------------------- N1: fused loss

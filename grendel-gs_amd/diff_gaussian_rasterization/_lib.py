@@ -158,6 +158,8 @@ SIGNATURES = {
     "gsr_render_invdepth": (c_int, [c_int, c_int, c_int] + [c_void_p] * 7 + [c_int, c_int, c_void_p, c_void_p]),
     "gsr_render_invdepth_backward": (c_int, [c_int, c_int, c_int] + [c_void_p] * 10 + [c_int, c_int] + [c_void_p] * 3),
     "gsr_depth_backward_means3d": (c_int, [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_int, c_void_p]),
+    "gsr_render_features": (c_int, [c_int] * 4 + [c_void_p] * 7 + [c_int, c_int, c_void_p, c_void_p]),
+    "gsr_render_features_backward": (c_int, [c_int] * 4 + [c_void_p] * 9 + [c_int, c_int] + [c_void_p] * 4),
     "gsr_render_absgrad": (c_int, [c_int, c_int, c_int] + [c_void_p] * 10 + [c_int, c_int] + [c_void_p] * 3),
     "gsr_absgrad_merge_rows": (c_int, [c_int64] + [c_void_p] * 4),
     "gsr_publish_flag": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p]),

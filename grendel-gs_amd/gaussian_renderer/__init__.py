@@ -94,6 +94,8 @@ def get_cuda_args_final(strategy, mode="train"):
         ca["invdepth"] = True
     if _ABSGRAD[0]:
         ca["absgrad"] = True
+    if _FEATURES[0]:
+        ca["features"] = True
     return ca
 
 
@@ -115,6 +117,40 @@ def set_invdepth(on):
 
 def get_invdepth():
     return _INVDEPTH[0]
+
+
+# ------------------------------------------------------------------------------ N-channel feature maps (opt-in)
+_FEATURES = [os.environ.get("GSR_FEATURES", "0") not in ("", "0")]
+
+
+def set_features(on):
+    """True (default False; GSR_FEATURES=1 in the environment: True): distributed_preprocess3dgs_and_all2all_final reads
+    pc.render_features -- an fp32 [P, C] tensor on the device, one row per Gaussian of the model, that may require grad
+    (semantic logits, distilled features, normals, a column of ones for the accumulated opacity, ...; a missing or
+    wrong-length tensor raises) -- and render_final leaves pkg["batched_features"]: per camera the map [C,H,W] of
+    include/gsraster.h's gsr_render_features (sum of alpha T f[c] over what the colour render blended, no background
+    term), zero outside this rank's band, or None where the camera is not rendered here or took the
+    fewer-than-10-Gaussians stand-in.  Extension of this build: the reference blends three colour channels.
+    render_final's return value is unchanged, and with the switch off nothing changes at all.
+    World size 1: the map carries gradients into xyz, opacity, scaling and rotation (added to the colour render's by
+    autograd, FusedAdam(fuse_backward=True) included: the projection backward it fuses receives the sum) and into
+    pc.render_features.  World size > 1 raises NotImplementedError before any collective: the feature rows would need
+    their own columns in the exchange.  Graph capture raises.  May be on together with set_invdepth."""
+    _FEATURES[0] = bool(on)
+
+
+def get_features():
+    return _FEATURES[0]
+
+
+def _features_of(pc, P, dev):
+    f = getattr(pc, "render_features", None)
+    if not torch.is_tensor(f) or f.dim() != 2 or f.shape[0] != P or f.shape[1] < 1:
+        raise ValueError(f"set_features(True): pc.render_features must be an fp32 [P, C] tensor with the model's P = {P} "
+                         f"rows, got {tuple(f.shape) if torch.is_tensor(f) else type(f).__name__}")
+    if f.dtype != torch.float32 or f.device != dev:
+        raise ValueError(f"set_features(True): pc.render_features must be float32 on {dev}, got {f.dtype} on {f.device}")
+    return f
 
 
 # ------------------------------------------------------------------------------ absolute gradients (opt-in)
@@ -882,6 +918,15 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
         from filter3d import _filter_of
 
         raw[1], raw[5] = _dgr.filter3d_apply(raw[1], raw[5], _filter_of(pc, "set_filter3d(True)"))
+    feats = None
+    if _FEATURES[0]:
+        if utils.DEFAULT_GROUP.size() > 1 or (_EXCHANGE_OPTIONS["forced"] and dist.is_initialized()):
+            raise NotImplementedError("set_features(True): feature maps are not available at world size > 1: the feature "
+                                      "rows need their own columns in the exchange")
+        if _dgr.capturing() is not None:
+            raise RuntimeError("set_features(True): feature maps are not supported inside a graph capture; run the "
+                               "iteration eagerly")
+        feats = _features_of(pc, raw[0].shape[0], raw[0].device)
     if timers is not None:
         timers.stop("forward_prepare_gaussians")
         timers.start("forward_preprocess_gaussians")
@@ -972,7 +1017,7 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
         redistributed = tuple([p[c] for p in params] for c in range(5))
         sizes = [[[p[0].shape[0] for p in params]]]
         _fill(pkg, redistributed, sizes)
-        if mode == "train" and not pose_grad and not _INVDEPTH[0] and not _FILTER3D[0] and \
+        if mode == "train" and not pose_grad and not _INVDEPTH[0] and not _FILTER3D[0] and not _FEATURES[0] and \
                 len(cuda_args_list) <= _dgr.DEFER_MAX_CAMERAS:
             # nothing but the projection backward reads these views' gradient records (no exchange, no K11c, no depth
             # path; `.grad` of means2D is kept lazily, above): their rounding may be left to the fused K11 + Adam launch
@@ -981,6 +1026,8 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
                 ca["_gsr_defer_record"] = True
         if _INVDEPTH[0]:
             pkg["_invdepth_xyz"] = raw[0]  # (the depth path of the inverse-depth map: dL/ddepth -> dL/dxyz)
+        if feats is not None:
+            pkg["_features_rows"] = feats  # (no exchange: the rendered rows are the model's rows, in order)
         return pkg
     if W * len(params) > 512:
         raise ValueError(f"world size x batch size = {W * len(params)} exceeds the 512 (destination, camera) segments "
@@ -1050,6 +1097,7 @@ def _render_cameras(pkg, batched_strategies):
     timers = utils.get_timers()
     images, masks, late = [], [], []
     invdepth = [None] * len(batched_strategies)  # (left in the package only when a camera's cuda_args ask for the map)
+    features = [None] * len(batched_strategies)  # (likewise)
     mine = [k for k, st in enumerate(batched_strategies) if utils.GLOBAL_RANK in st.gpu_ids]
     dev0 = pkg["batched_means2D_redistributed"][mine[0]].device if mine else None
     two = (_EXCHANGE_OPTIONS["camera_streams"] > 1 and len(mine) > 1 and dev0 is not None and dev0.type == "cuda"
@@ -1099,6 +1147,11 @@ def _render_cameras(pkg, batched_strategies):
                     invdepth[k] = _invdepth_map(pkg, k, cuda_args, means2D, conic_opacity)
                     if two:
                         invdepth[k].record_stream(main)
+                if cuda_args.get("features"):
+                    features[k] = pkg["batched_rasterizers"][k].render_features(means2D, conic_opacity,
+                                                                                 pkg["_features_rows"], cuda_args)
+                    if two:
+                        features[k].record_stream(main)
             if two:
                 image.record_stream(main)  # (allocated on the side stream, consumed by the loss on the caller's)
             if timers is not None:
@@ -1110,6 +1163,8 @@ def _render_cameras(pkg, batched_strategies):
             main.wait_stream(s_)
     if any(ca.get("invdepth") for ca in pkg["batched_cuda_args"]):
         pkg["batched_invdepth"] = invdepth
+    if any(ca.get("features") for ca in pkg["batched_cuda_args"]):
+        pkg["batched_features"] = features
     return images, masks, late
 
 

@@ -468,6 +468,51 @@ int gsr_render_invdepth_backward(int P, int width, int height, const int32_t *ra
 int gsr_depth_backward_means3d(int P, const int32_t *radii, const float *viewmatrix, const float *dL_ddepth,
                                int row_stride, float *dL_dmeans3D, int overwrite, gsr_stream_t stream);
 
+/* N-CHANNEL FEATURE MAP of a rendered view, with gradients (semantic logits, distilled 2D features, normals, an
+ * accumulated-opacity map, expected depth, ...).  The reference's rasterizer blends three colour channels only, so there is
+ * NO reference call site: oracle/torch_oracle.py's `render` with bg = 0, three channels at a time, differentiated by
+ * autograd in float64, is the arbiter (tests/features_refs.py).  New symbols only: gsr_abi_version does not move.
+ * Inputs as gsr_render_invdepth, with `features` fp32 [P, C] row-major in place of `depths` and 1 <= C <=
+ * GSR_FEATURES_MAX; the inverse-depth map is the case C = 1, f = 1 / depth.  The same walk: the entry at list position k
+ * (0-based) of a local tile is BLENDED on a pixel p iff k + 1 <= n_contrib[p], power <= 0 and alpha_i = min(0.99, o_i
+ * exp(power)) >= 1/255, in the composite kernels' own arithmetic; nothing is re-decided.  T starts at 1, w_i = alpha_i T_i,
+ * T <- T - w_i.
+ *
+ * gsr_render_features: out fp32 [C,H,W], FULLY overwritten:
+ *   out[c][p] = sum over the blended entries of w_i f_i[c] -- no background term, no division by 1 - T_final; pixels of
+ *   tiles that are not ours (and of tiles outside the band of a band launch) are exactly +0.  A channel's values do not
+ *   depend on C or on the other channels.  P == 0 writes the all-zero map and touches nothing else.
+ *
+ * gsr_render_features_backward: with g_c = dL_dout[c][p] ([C,H,W]; read on the local tiles only),
+ *   dL/df_i[c]  = sum_p g_c w_i;
+ *   dL/dalpha_i = sum_c g_c (T_i f_i[c] - S_i[c] / (1 - alpha_i)), S_i[c] = the sum of w_j f_j[c] over the blended j behind i;
+ *   from dL/dalpha on, gsr_render_backward's chain: q = o G dL/dalpha (the 0.99 clamp is the identity in the backward),
+ *   (dx, dy) = mean - pixel, dL/dmean = -(A sum q dx + B sum q dy, B sum q dx + C sum q dy) (W/2, H/2),
+ *   dL/d(A, B, C) = -(sum q dx^2 / 2, sum q dx dy, sum q dy^2 / 2), dL/do = sum q / o.
+ *   dL_record fp32 [P,6], FULLY overwritten: [0:2] dL_dmeans2D, [2:6] dL_dconic_opacity.  dL_dfeatures fp32 [P,C], FULLY
+ *   overwritten -- or NULL: the feature gradient is not formed (a constant feature, such as an all-ones column whose map
+ *   is the accumulated opacity 1 - T_final), dL_record is the same bits.  Rows blended nowhere are +0.0f in both.
+ *   acc64: device scratch of the caller, cleared by the call: [P, 6 + C] doubles, or [P, 6] with dL_dfeatures == NULL;
+ *   per-quadrant fp32 sums (a fixed order over the 64 pixels) are added into it in fp64 and each sum is rounded once
+ *   (gsr_render_backward's reason).  The channels are processed GSR_FEATURES_CHUNK at a time; every chunk walks the lists
+ *   again from final_T and recomputes alpha (nothing per (pixel, entry) is kept in device memory), and the chunks'
+ *   geometry sums add in fp64.  P == 0 returns 0 and touches nothing.
+ *
+ * row_lo / row_hi: whole grid (0, 0), host band, or -1 = the device hull behind the range table, as gsr_render_invdepth.
+ * Both: a negative size, a non-positive frame, C outside [1, GSR_FEATURES_MAX], or a missing pointer with P > 0:
+ * GSR_EINVAL before any device work (the forward needs `out` for P == 0 too). */
+#define GSR_FEATURES_MAX 256
+#define GSR_FEATURES_CHUNK 16
+int gsr_render_features(int P, int C, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                        const float *means2D, const float *conic_opacity, const float *features,
+                        const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi, float *out,
+                        gsr_stream_t stream);
+int gsr_render_features_backward(int P, int C, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                                 const float *means2D, const float *conic_opacity, const float *features,
+                                 const uint8_t *compute_locally, const int32_t *n_contrib, const float *final_T,
+                                 const float *dL_dout, int row_lo, int row_hi, float *dL_record, float *dL_dfeatures,
+                                 double *acc64, gsr_stream_t stream);
+
 /* ABSOLUTE screen-space gradient of a rendered view (densification).  The reference accumulates the norm of the signed
  * means2D gradient, which cancels on a large Gaussian whose pixels pull its centre in opposite directions; this is the
  * homodirectional gradient of AbsGS (`absgrad` of gsplat): the magnitude of every pixel's contribution, summed.  There is
