@@ -295,6 +295,51 @@ int gsr_render_features_backward(int P, int C, int width, int height, const int3
                                                   dL_record, dL_dfeatures, acc64, reinterpret_cast<hipStream_t>(stream));
 }
 
+int gsr_normal_rows_forward(int P, const float *xyz, const float *scaling, const float *rotation, const int32_t *radii,
+                            const float *viewmatrix, float *rows, gsr_stream_t stream) {
+    if (P < 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!xyz || !scaling || !rotation || !radii || !viewmatrix || !rows) return GSR_EINVAL;
+    return gsr_launch_normal_rows_forward(P, xyz, scaling, rotation, radii, viewmatrix, rows,
+                                          reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_normal_rows_backward(int P, const float *xyz, const float *scaling, const float *rotation, const int32_t *radii,
+                             const float *viewmatrix, const float *dL_drows, float *dL_dxyz, float *dL_drotation,
+                             gsr_stream_t stream) {
+    if (P < 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!xyz || !scaling || !rotation || !radii || !viewmatrix || !dL_drows || !dL_dxyz || !dL_drotation)
+        return GSR_EINVAL;
+    return gsr_launch_normal_rows_backward(P, xyz, scaling, rotation, radii, viewmatrix, dL_drows, dL_dxyz, dL_drotation,
+                                           reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_normal_consistency_num_partials(int width, int height) {
+    if (width <= 0 || height <= 0) return 0;
+    return gsr_normal_consistency_tiles(width, height, nullptr);
+}
+
+int gsr_normal_consistency_forward(int width, int height, const float *feature_map, float tanfovx, float tanfovy,
+                                   float weight, double *partials, float *loss, float *normals, gsr_stream_t stream) {
+    if (width < 0 || height < 0 || !(tanfovx > 0.f) || !(tanfovy > 0.f)) return GSR_EINVAL;
+    if (width == 0 || height == 0) return 0;
+    // (normals may be NULL: the map of n_d is then not written)
+    if (!feature_map || !partials || !loss) return GSR_EINVAL;
+    return gsr_launch_normal_consistency_forward(width, height, feature_map, tanfovx, tanfovy, weight, partials, loss,
+                                                 normals, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_normal_consistency_backward(int width, int height, const float *feature_map, float tanfovx, float tanfovy,
+                                    float weight, const float *dL_dloss, float *dL_dfeature_map, gsr_stream_t stream) {
+    if (width < 0 || height < 0 || !(tanfovx > 0.f) || !(tanfovy > 0.f)) return GSR_EINVAL;
+    if (width == 0 || height == 0) return 0;
+    // (dL_dloss may be NULL: 1)
+    if (!feature_map || !dL_dfeature_map) return GSR_EINVAL;
+    return gsr_launch_normal_consistency_backward(width, height, feature_map, tanfovx, tanfovy, weight, dL_dloss,
+                                                  dL_dfeature_map, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gsr_render_absgrad(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
                        const float *means2D, const float *conic_opacity, const float *rgb,
                        const uint8_t *compute_locally, const float *bg, const float *final_T, const int32_t *n_contrib,

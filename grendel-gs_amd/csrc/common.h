@@ -215,6 +215,16 @@ int gsr_launch_composite_features_backward(int P, int C, int W, int H, const int
                                            const uint8_t *compute_locally, const int32_t *n_contrib,
                                            const float *final_T, const float *dL_dout, int row_lo, int row_hi,
                                            float *dL_record, float *dL_dfeatures, double *acc64, hipStream_t stream);
+int gsr_launch_normal_rows_forward(int P, const float *xyz, const float *scaling, const float *rotation,
+                                   const int32_t *radii, const float *viewmatrix, float *rows, hipStream_t stream);
+int gsr_launch_normal_rows_backward(int P, const float *xyz, const float *scaling, const float *rotation,
+                                    const int32_t *radii, const float *viewmatrix, const float *g, float *d_xyz,
+                                    float *d_rotation, hipStream_t stream);
+int gsr_normal_consistency_tiles(int W, int H, int *tiles_x);
+int gsr_launch_normal_consistency_forward(int W, int H, const float *F, float tanfovx, float tanfovy, float weight,
+                                          double *partials, float *loss, float *normals, hipStream_t stream);
+int gsr_launch_normal_consistency_backward(int W, int H, const float *F, float tanfovx, float tanfovy, float weight,
+                                           const float *g_loss, float *dL_dF, hipStream_t stream);
 int gsr_launch_composite_absgrad(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
                                  const float *means2D, const float *conic_opacity, const float *rgb,
                                  const uint8_t *compute_locally, const float *bg, const float *final_T,

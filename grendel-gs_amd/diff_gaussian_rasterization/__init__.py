@@ -2469,6 +2469,101 @@ def filter3d_apply(scaling, opacity, filter_3D):
     return _Filter3DApply.apply(scaling, opacity, filter_3D)
 
 
+# ---- depth-normal consistency (include/gsraster.h: gsr_normal_rows_*, gsr_normal_consistency_*) ---------------------
+NORMALS_TILE = (64, 8)  # GSR_NORMALS_TILE_X, GSR_NORMALS_TILE_Y of include/gsraster.h: the loss kernels' pixel tile
+
+
+class _NormalRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, scaling, rotation, radii, viewmatrix):
+        if not (xyz.is_cuda and scaling.is_cuda and rotation.is_cuda and radii.is_cuda and viewmatrix.is_cuda):
+            raise RuntimeError("normal_rows: device tensors required (no CPU fallback)")
+        xyz, scaling, rotation = _f32c(xyz, "xyz"), _f32c(scaling, "scaling"), _f32c(rotation, "rotation")
+        view = _f32c(viewmatrix.detach(), "viewmatrix")
+        radii = radii.detach().to(torch.int32).contiguous()
+        P = xyz.shape[0]
+        if xyz.shape != (P, 3) or scaling.shape != (P, 3) or rotation.shape != (P, 4) or radii.shape != (P,) or \
+                view.numel() != 16:
+            raise ValueError(f"normal_rows: xyz [P,3], scaling [P,3], rotation [P,4], radii [P] and a 4 x 4 view matrix "
+                             f"expected, got {tuple(xyz.shape)}, {tuple(scaling.shape)}, {tuple(rotation.shape)}, "
+                             f"{tuple(radii.shape)}, {tuple(view.shape)}")
+        dev = xyz.device
+        rows = torch.empty((P, 5), dtype=torch.float32, device=dev)
+        with _on(dev), kernel_timer.range("normal_rows_forward", P=P):
+            check(lib.gsr_normal_rows_forward(P, _ptr(xyz), _ptr(scaling), _ptr(rotation), _ptr(radii), _ptr(view),
+                                              _ptr(rows), _stream()), "gsr_normal_rows_forward")
+        ctx.save_for_backward(xyz, scaling, rotation, radii, view)
+        return rows
+
+    @staticmethod
+    def backward(ctx, g):
+        xyz, scaling, rotation, radii, view = ctx.saved_tensors
+        P, dev = xyz.shape[0], xyz.device
+        g = g.float().contiguous()
+        d_xyz, d_rot = torch.empty_like(xyz), torch.empty_like(rotation)
+        with _on(dev), kernel_timer.range("normal_rows_backward", P=P):
+            check(lib.gsr_normal_rows_backward(P, _ptr(xyz), _ptr(scaling), _ptr(rotation), _ptr(radii), _ptr(view),
+                                               _ptr(g), _ptr(d_xyz), _ptr(d_rot), _stream()),
+                  "gsr_normal_rows_backward")
+        return d_xyz, None, d_rot, None, None  # (dL/dscaling is zero: k is a constant)
+
+
+def normal_rows(xyz, scaling, rotation, radii, viewmatrix):
+    """(_xyz [P,3], _scaling [P,3], _rotation [P,4] -- the RAW parameters --, the view's radii [P], its view matrix) ->
+    rows [P,5] = (1, t_z, n): per Gaussian the depth in the camera and its shortest axis, rotated into the camera and
+    flipped to face it (include/gsraster.h: gsr_normal_rows_forward); rows with radii <= 0 are zeros.  Blended by
+    GaussianRasterizer.render_features they give the [5,H,W] map normal_consistency reads.  One kernel each way;
+    gradients to xyz (through t_z) and rotation, none to scaling (the choice of the axis is a constant) and none to the
+    view matrix (it is detached: no pose gradient flows through the rows)."""
+    return _NormalRows.apply(xyz, scaling, rotation, radii, viewmatrix)
+
+
+class _NormalConsistency(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feature_map, tanfovx, tanfovy, weight, return_normals):
+        F = _f32c(feature_map, "feature_map")
+        if F.dim() != 3 or F.shape[0] != 5:
+            raise ValueError(f"normal_consistency: a [5,H,W] map (A, D, N) expected, got {tuple(F.shape)}")
+        H, W = int(F.shape[1]), int(F.shape[2])
+        dev = F.device
+        loss = torch.zeros((), dtype=torch.float32, device=dev) if H * W == 0 else \
+            torch.empty((), dtype=torch.float32, device=dev)
+        normals = torch.empty((3, H, W), dtype=torch.float32, device=dev) if return_normals else None
+        partials = torch.empty((max(lib.gsr_normal_consistency_num_partials(W, H), 1),), dtype=torch.float64, device=dev)
+        with _on(dev), kernel_timer.range("normal_consistency_forward"):
+            check(lib.gsr_normal_consistency_forward(W, H, _ptr(F), float(tanfovx), float(tanfovy), float(weight),
+                                                     _ptr(partials), _ptr(loss), _ptr(normals), _stream()),
+                  "gsr_normal_consistency_forward")
+        ctx.save_for_backward(F)  # (the backward recomputes z, c and n_d from the map in LDS: nothing else is kept)
+        ctx.consts = (float(tanfovx), float(tanfovy), float(weight))
+        if return_normals:
+            ctx.mark_non_differentiable(normals)
+            return loss, normals
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (F,) = ctx.saved_tensors
+        tanfovx, tanfovy, weight = ctx.consts
+        H, W = int(F.shape[1]), int(F.shape[2])
+        dF = torch.empty_like(F)
+        g = g.float().contiguous()
+        with _on(F.device), kernel_timer.range("normal_consistency_backward"):
+            check(lib.gsr_normal_consistency_backward(W, H, _ptr(F), tanfovx, tanfovy, weight, _ptr(g), _ptr(dF),
+                                                      _stream()), "gsr_normal_consistency_backward")
+        return dF, None, None, None, None
+
+
+def normal_consistency(feature_map, tanfovx, tanfovy, weight=1.0, return_normals=False):
+    """the depth-normal consistency term of 2DGS on a [5,H,W] map (A, D, N) -- what render_features blends from
+    normal_rows --: weight / (H W) sum over the interior pixels of 1 - A* (N . n_d), n_d the normal of the surface the
+    depth map D / A describes (finite differences of the unprojected depth), A* = A held constant; include/gsraster.h
+    (gsr_normal_consistency_forward) has the definition.  -> the scalar, and n_d [3,H,W] with `return_normals` (for
+    viewers; not differentiable).  One fused kernel each way (plus a one-workgroup sum): the gradient goes to N directly
+    and to D and A through the depth; no atomics, the same bits on every run."""
+    return _NormalConsistency.apply(feature_map, tanfovx, tanfovy, weight, return_normals)
+
+
 def exchange_need(means2D_all, radii_all, bands, width, height):
     """K2 for the whole camera batch in the exchange's layout: means2D_all [B,P,2], radii_all int32 [B,P],
     bands int32 [B,W,2] (tile rows [lo,hi) of camera k rendered by global rank g) ->

@@ -94,7 +94,7 @@ def get_cuda_args_final(strategy, mode="train"):
         ca["invdepth"] = True
     if _ABSGRAD[0]:
         ca["absgrad"] = True
-    if _FEATURES[0]:
+    if _FEATURES[0] or _NORMALS[0]:
         ca["features"] = True
     return ca
 
@@ -151,6 +151,47 @@ def _features_of(pc, P, dev):
     if f.dtype != torch.float32 or f.device != dev:
         raise ValueError(f"set_features(True): pc.render_features must be float32 on {dev}, got {f.dtype} on {f.device}")
     return f
+
+
+# ------------------------------------------------------------------------------ depth-normal consistency (opt-in)
+_NORMALS = [os.environ.get("GSR_NORMALS", "0") not in ("", "0")]
+
+
+def set_normal_consistency(on):
+    """True (default False; GSR_NORMALS=1 in the environment: True): distributed_preprocess3dgs_and_all2all_final builds,
+    per camera of the batch, the surfel rows [P,5] = (1, depth, normal facing that camera) of include/gsraster.h's
+    gsr_normal_rows_forward from the raw parameters and the view's radii (one launch per camera), and render_final blends
+    camera k's rows into pkg["batched_features"][k]: the [5,H,W] map (A, D, N) that
+    loss_distribution.normal_consistency_loss turns into the depth-normal consistency term of 2DGS / PGSR / RaDe-GS
+    (diff_gaussian_rasterization.normal_consistency).  Extension of this build: the reference has no such term.
+    render_final's return value is unchanged, and with the switch off nothing changes at all.
+    World size 1: the term carries gradients into xyz, opacity, scaling and rotation through the feature map's backward
+    and, through the rows, into xyz and rotation once more; FusedAdam(fuse_backward=True) keeps working -- the rows'
+    gradients reach `.grad` through autograd and the step then takes the projection backward unfused.  Not together with
+    set_features(True) (both would own the per-Gaussian rows; ValueError).  World size > 1 raises NotImplementedError
+    before any collective: the rows would need their own columns in the exchange.  Graph capture raises.  Pose refinement
+    (a camera tensor that requires grad) raises NotImplementedError: the rows carry no gradient to the view matrix."""
+    if on and _FEATURES[0]:
+        raise ValueError("set_normal_consistency(True): not available together with set_features(True): both hand "
+                         "render_features their own per-Gaussian rows")
+    _NORMALS[0] = bool(on)
+
+
+def get_normal_consistency():
+    return _NORMALS[0]
+
+
+def _refuse_normals():
+    """the refusals of set_normal_consistency(True), before anything is launched or exchanged"""
+    if _FEATURES[0]:
+        raise ValueError("set_normal_consistency(True): not available together with set_features(True): both hand "
+                         "render_features their own per-Gaussian rows")
+    if utils.DEFAULT_GROUP.size() > 1 or (_EXCHANGE_OPTIONS["forced"] and dist.is_initialized()):
+        raise NotImplementedError("set_normal_consistency(True): the depth-normal term is not available at world size "
+                                  "> 1: the surfel rows need their own columns in the exchange")
+    if _dgr.capturing() is not None:
+        raise RuntimeError("set_normal_consistency(True): the depth-normal term is not supported inside a graph capture; "
+                           "run the iteration eagerly")
 
 
 # ------------------------------------------------------------------------------ absolute gradients (opt-in)
@@ -899,6 +940,8 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
     # timing mode a user may have set
     from gaussian_renderer.workload_division import timings_have_consumer
     timing = "deferred" if (mode != "train" or timings_have_consumer()) else "off"
+    if _NORMALS[0]:
+        _refuse_normals()
     if timers is not None:
         timers.start("forward_prepare_gaussians")
     raw = [getattr(pc, n, None) for n in ("_xyz", "_scaling", "_rotation", "_features_dc", "_features_rest", "_opacity")]
@@ -975,6 +1018,9 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
             except AttributeError:
                 pass
         packed.append(cached[1])
+    if _NORMALS[0] and pose_grad:
+        raise NotImplementedError("set_normal_consistency(True): not available with pose refinement (a camera tensor "
+                                  "requires grad): the surfel rows carry no gradient to the view matrix")
     rs0 = rasterizers[0].raster_settings
     if len(packed) == 1:
         cams_block = packed[0].view(1, -1)
@@ -1018,6 +1064,7 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
         sizes = [[[p[0].shape[0] for p in params]]]
         _fill(pkg, redistributed, sizes)
         if mode == "train" and not pose_grad and not _INVDEPTH[0] and not _FILTER3D[0] and not _FEATURES[0] and \
+                not _NORMALS[0] and \
                 len(cuda_args_list) <= _dgr.DEFER_MAX_CAMERAS:
             # nothing but the projection backward reads these views' gradient records (no exchange, no K11c, no depth
             # path; `.grad` of means2D is kept lazily, above): their rounding may be left to the fused K11 + Adam launch
@@ -1028,6 +1075,11 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
             pkg["_invdepth_xyz"] = raw[0]  # (the depth path of the inverse-depth map: dL/ddepth -> dL/dxyz)
         if feats is not None:
             pkg["_features_rows"] = feats  # (no exchange: the rendered rows are the model's rows, in order)
+        if _NORMALS[0]:
+            # view-dependent rows: one tensor per camera, from the model's own raw parameters (the 3D filter's effective
+            # scales keep the order of the axes) and the radii K1 left for that view
+            pkg["_features_rows"] = [_dgr.normal_rows(pc._xyz, pc._scaling, pc._rotation, p[3],
+                                                      r.raster_settings.viewmatrix) for p, r in zip(params, rasterizers)]
         return pkg
     if W * len(params) > 512:
         raise ValueError(f"world size x batch size = {W * len(params)} exceeds the 512 (destination, camera) segments "
@@ -1148,8 +1200,9 @@ def _render_cameras(pkg, batched_strategies):
                     if two:
                         invdepth[k].record_stream(main)
                 if cuda_args.get("features"):
-                    features[k] = pkg["batched_rasterizers"][k].render_features(means2D, conic_opacity,
-                                                                                 pkg["_features_rows"], cuda_args)
+                    rows = pkg["_features_rows"]  # (a list: per-camera rows, set_normal_consistency)
+                    features[k] = pkg["batched_rasterizers"][k].render_features(
+                        means2D, conic_opacity, rows[k] if isinstance(rows, list) else rows, cuda_args)
                     if two:
                         features[k].record_stream(main)
             if two:

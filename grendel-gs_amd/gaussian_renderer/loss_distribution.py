@@ -383,3 +383,32 @@ def invdepth_weight(iteration, init=1.0, final=0.01, max_steps=30_000):
         raise ValueError("invdepth_weight: `init` and `final` must both be positive (or both 0)")
     t = min(max(iteration / float(max_steps), 0.0), 1.0)
     return math.exp(math.log(init) * (1.0 - t) + math.log(final) * t)
+
+
+# ------------------------------------------------------------------------------ depth-normal consistency (opt-in)
+def normal_consistency_loss(pkg, batched_cameras, weight):
+    """the depth-normal consistency term of the batch, for the trainer to add to its loss: the sum over the cameras
+    rendered here of diff_gaussian_rasterization.normal_consistency on the [5,H,W] map (A, D, N) that render_final left
+    in pkg["batched_features"] under gaussian_renderer.set_normal_consistency(True) -- weight / (H W) times the sum over
+    the interior pixels of 1 - A (N . n_d), one fused HIP kernel each way per camera (extension of this build: the
+    reference has no such term; 2DGS uses weight 0.05 from iteration 7 000 on).  Cameras that are not rendered here or
+    took the fewer-than-10-Gaussians stand-in contribute nothing.  The surfel rows' gradients reach xyz and rotation through
+    autograd as ordinary `.grad`; FusedAdam(fuse_backward=True) then takes its step unfused (its own rule for parameters
+    that carry another gradient)."""
+    import diff_gaussian_rasterization as _dgr
+
+    maps = pkg.get("batched_features")
+    if maps is None or not isinstance(pkg.get("_features_rows"), list):
+        raise RuntimeError("normal_consistency_loss: call gaussian_renderer.set_normal_consistency(True) before the "
+                           "batch is preprocessed and rendered (pkg carries no surfel map)")
+    total = None
+    for camera, fmap in zip(batched_cameras, maps):
+        if fmap is None:
+            continue
+        if fmap.shape[0] != 5:
+            raise ValueError(f"normal_consistency_loss: a [5,H,W] surfel map expected, got {tuple(fmap.shape)}")
+        term = _dgr.normal_consistency(fmap, math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5), weight)
+        total = term if total is None else total + term
+    if total is None:
+        raise RuntimeError("normal_consistency_loss: no camera of the batch was rendered on this rank")
+    return total

@@ -513,6 +513,54 @@ int gsr_render_features_backward(int P, int C, int width, int height, const int3
                                  const float *dL_dout, int row_lo, int row_hi, float *dL_record, float *dL_dfeatures,
                                  double *acc64, gsr_stream_t stream);
 
+/* DEPTH-NORMAL CONSISTENCY (the regulariser of 2DGS, PGSR, RaDe-GS, GOF, CityGaussianV2): surfel rows for
+ * gsr_render_features and a fused image-space loss on the map they blend into.  The reference has no such term, so there
+ * is NO reference call site: tests/normal_refs.py restates both definitions in float64 torch with autograd.  New symbols
+ * only: gsr_abi_version does not move.
+ *
+ * (a) gsr_normal_rows_forward: rows fp32 [P,5], FULLY overwritten, from the RAW parameters xyz [P,3], scaling [P,3]
+ *   (log-scales), rotation [P,4] (un-normalised, (r, x, y, z)), the view's radii [P] and the view matrix (row-vector
+ *   convention, t = [p, 1] V):
+ *     k = argmin_j scaling[j] (a tie takes the lowest index; log-scales order like the scales),
+ *     q^ = q / max(|q|, 1e-12), R = the rotation matrix of q^, a_w = R[:,k], a_c[j] = sum_m a_w[m] V[m][j],
+ *     sigma = -1 if a_c . t > 0, else +1 (the normal faces the camera), n = sigma a_c,
+ *     rows[i] = (1, t_z, n_x, n_y, n_z); t_z is K1's depth bit for bit.  Rows with radii <= 0 are five +0.
+ *   Blended by gsr_render_features (C = 5) they give F = (A, D, N): accumulated opacity, expected depth times A, normal.
+ * gsr_normal_rows_backward: from dL_drows [P,5], with sigma and k constants: dL_dxyz [P,3] = dL_drows[1] V[0:3][2];
+ *   dL_drotation [P,4] through a_w = R[:,k] and the normalisation (dq - q^ (q^ . dq)) / max(|q|, 1e-12), the inner
+ *   product taken as 0 where |q| <= 1e-12 (gsr_preprocess_backward_raw's rule); dL/dscaling is zero and not written.
+ *   Both FULLY overwritten, rows with radii <= 0 are +0.  No atomics.
+ *
+ * (b) gsr_normal_consistency_forward on feature_map fp32 [5,H,W] = (A, D, N_x, N_y, N_z):
+ *     z(p) = D / A where A > 1e-6, else 0;  ray(p) = (((2x+1)/W - 1) tanfovx, ((2y+1)/H - 1) tanfovy, 1);  X = z ray;
+ *     on interior pixels (1 <= x <= W-2, 1 <= y <= H-2): dx = X(x+1,y) - X(x-1,y), dy = X(x,y+1) - X(x,y-1),
+ *     c = dy x dx (facing the camera on a fronto-parallel plane), n_d = c / |c| where |c|^2 > 1e-24, else 0 with zero
+ *     gradient, e = 1 - A* (N . n_d) with A* = A held constant (the detached weight of 2DGS); e = 0 on border pixels;
+ *     loss[0] = weight / (H W) sum_p e(p), in fp32 from fp64 sums.
+ *   One workgroup per GSR_NORMALS_TILE_X x GSR_NORMALS_TILE_Y pixels writes one fp64 partial; `partials`: device scratch
+ *   of the caller, gsr_normal_consistency_num_partials(width, height) doubles, summed in a fixed order.  `normals`: fp32
+ *   [3,H,W], FULLY overwritten with n_d (0 on the border), or NULL.
+ * gsr_normal_consistency_backward: dL_dfeature_map fp32 [5,H,W], FULLY overwritten, times dL_dloss[0] (device; NULL: 1):
+ *     dL/dN = -weight / (H W) A* n_d;  with v = -weight / (H W) A* (I - n_d n_d^T) N / |c|: dL/d(dx) = v x dy,
+ *     dL/d(dy) = dx x v, dL/dX(p) = dL/d(dx)(p - e_x) - dL/d(dx)(p + e_x) + dL/d(dy)(p - e_y) - dL/d(dy)(p + e_y) over
+ *     the interior neighbours, dL/dz = dL/dX . ray, dL/dD = dL/dz / A, dL/dA = -dL/dz D / A^2 (through z only), both 0
+ *     where A <= 1e-6.  A gather: no atomics, the same bits on every run.
+ *
+ * P == 0 and an empty image (width or height 0) return 0 without a launch and touch nothing.  A negative size, a
+ * tangent that is not positive, or a missing pointer otherwise: GSR_EINVAL before any device work. */
+#define GSR_NORMALS_TILE_X 64
+#define GSR_NORMALS_TILE_Y 8
+int gsr_normal_rows_forward(int P, const float *xyz, const float *scaling, const float *rotation, const int32_t *radii,
+                            const float *viewmatrix, float *rows, gsr_stream_t stream);
+int gsr_normal_rows_backward(int P, const float *xyz, const float *scaling, const float *rotation, const int32_t *radii,
+                             const float *viewmatrix, const float *dL_drows, float *dL_dxyz, float *dL_drotation,
+                             gsr_stream_t stream);
+int gsr_normal_consistency_num_partials(int width, int height);
+int gsr_normal_consistency_forward(int width, int height, const float *feature_map, float tanfovx, float tanfovy,
+                                   float weight, double *partials, float *loss, float *normals, gsr_stream_t stream);
+int gsr_normal_consistency_backward(int width, int height, const float *feature_map, float tanfovx, float tanfovy,
+                                    float weight, const float *dL_dloss, float *dL_dfeature_map, gsr_stream_t stream);
+
 /* ABSOLUTE screen-space gradient of a rendered view (densification).  The reference accumulates the norm of the signed
  * means2D gradient, which cancels on a large Gaussian whose pixels pull its centre in opposite directions; this is the
  * homodirectional gradient of AbsGS (`absgrad` of gsplat): the magnitude of every pixel's contribution, summed.  There is
