@@ -4,30 +4,24 @@
 // pull its centre in opposite directions.
 //
 // The quantity needs dL/dalpha per (pixel, entry) BEFORE the sum over the pixels, which K10 (composite.hip) forms and
-// contracts at once; K10 has no register left to carry a second contraction.  The kernel here walks the same lists once
-// more, as contrib.hip and invdepth.hip do: a pixel's walk ends where K8's ended (n_contrib), the (pixel, entry) pairs
-// taken are K10's `take` rule -- position + 1 <= n_contrib, power <= 0, alpha >= 1/255 -- in the arithmetic of
-// composite_math.h, and the chain is K10's (its reciprocal refined by one Newton step).  K8 and K10 are untouched; a
+// contracts at once; K10 has no register left to carry a second contraction.  The kernel here is a side pass in the
+// shape of tile_walk.h, and the chain is K10's (its reciprocal refined by one Newton step).  K8 and K10 are untouched; a
 // trainer that does not ask for the quantity never launches this.
 //
-// composite_absgrad_kernel: the shape of composite_invdepth_backward_kernel.  One wave = one 8x8 quadrant, lane = pixel;
-// the list is walked back to front from final_T in 64-entry chunks, one entry per lane (index read + gather + quadrant
-// test), the relevant entries compacted in walk order into records in a wave-private LDS slab -- the three colours
-// beside the geometry -- and read back with wave-uniform addresses.  With alpha of the entry, inv = 1 / (1 - alpha),
-// Tn = T inv the transmittance in front of it, rho = (the colour blended behind it) . g / (its own T (1 - alpha)) one
-// scalar recurrence (K10 carries R . g, not R: the three channels only ever enter through the pixel's g),
+// composite_absgrad_kernel: a back-to-front walk from final_T, the three colours beside the geometry in the record.
+// With alpha of the entry, inv = 1 / (1 - alpha), Tn = T inv the transmittance in front of it, rho = (the colour blended
+// behind it) . g / (its own T (1 - alpha)) one scalar recurrence (K10 carries R . g, not R: the three channels only ever
+// enter through the pixel's g),
 //     dL/dalpha = (c . g - rho) Tn - inv T_final (bg . g)
 //     q = o G dL/dalpha                      (G = exp(power); the min(0.99, .) clamp is the identity in the backward)
 //     m = ( |q (2 a2 dx + b2 dy)| , |q (b2 dx + 2 c2 dy)| ),   (dx, dy) = entry - pixel,
 // a2 = -A log2(e) / 2, b2 = -B log2(e), c2 = -C log2(e) / 2 the slab's pre-scaled conic: (2 a2, b2, 2 c2) is (A, B, C)
 // times -log2(e), a factor that is constant over the pixels and whose sign the magnitude drops, so it is taken out of
 // the sum and applied once per (quadrant, entry) as ln 2 -- the slab needs no second copy of the conic.
-// The reduction over the quadrant's 64 pixels is the LDS TRANSPOSE of invdepth.hip over a batch of CB = 8 entries: phase
-// A (lane = pixel) stores m of every entry of the batch into a wave-private matrix [slot][pixel]; phase B (lane = (slot,
-// row of the quadrant)) adds its row's eight pixels in pixel order and three xor steps combine the rows: a fixed order,
-// fp32, non-negative terms.  Lanes 0 and 1 of the slot scale the two sums by ln 2 (W/2, H/2) and add them into the
-// caller's fp64 sums [P,2], two adjacent lanes per (quadrant, entry) into one 16-byte row.  Entries no pixel of the
-// quadrant blends issue nothing.  The segment workspace of K8 / K10 is not used: the walk is the whole list.
+// The transpose carries m: phase B adds its row's eight pixels in pixel order, non-negative terms.  Lanes 0 and 1 of the
+// slot scale the two sums by ln 2 (W/2, H/2) and add them into the caller's fp64 sums [P,2], two adjacent lanes per
+// (quadrant, entry) into one 16-byte row.  Entries no pixel of the quadrant blends issue nothing.  The segment workspace
+// of K8 / K10 is not used: the walk is the whole list.
 // (LDS: 4.1 KiB matrix + 3.7 KiB slab and ids per wave, 31.1 KiB per workgroup -- five workgroups per CU of its 160 KiB,
 // as the inverse-depth backward.)
 // A rounding pass then writes the whole fp32 [P,2]: each sum rounded once; rows that are blended nowhere are 0.0f.  The
@@ -37,30 +31,11 @@
 // absgrad_merge_rows_kernel: dst[idx[r]][0:2] += src[r][0:2], the return trip of a multi-rank render.
 #include "common.h"
 #include "composite_math.h"
+#include "tile_walk.h"
 
 namespace {
 
-constexpr int CB = 8;                   // entries per batch
-constexpr int MSTR = 66;                // row stride of the magnitude matrix in 8-byte elements (16-byte aligned rows)
-constexpr int NO_POS = 0x7fffffff;      // position word of an inert slot: no n_contrib reaches it
 constexpr float LN2 = 0.6931471805599453f;  // 1 / log2(e): (2 a2, b2, 2 c2) -> -(A, B, C)
-
-// block -> tile as in K8 / the contribution kernel; -1: this workgroup has no tile
-__device__ __forceinline__ int absgrad_tile_of_block(const int2 *__restrict__ ranges, int gx, int tiles, int band,
-                                                     int band_first, int band_tiles) {
-    if (band) {
-        if (band_first < 0) {  // `band_tiles` is a capacity, the band is the row hull behind the range table
-            const int gy = tiles / gx;
-            int2 hull = ranges[tiles];
-            if (hull.x < 0 || hull.y > gy || hull.x >= hull.y) hull = make_int2(0, 0);
-            band_first = hull.x * gx;
-            band_tiles = min((hull.y - hull.x) * gx, band_tiles);
-            if ((int)blockIdx.x >= band_tiles) return -1;
-        }
-        return band_first + gsr_xcd_span_of_block(blockIdx.x, band_tiles);
-    }
-    return composite_tile_of_block(ranges, gx, tiles);
-}
 
 __global__ void __launch_bounds__(256)
 composite_absgrad_kernel(int W, int H, int gx, int tiles, const int2 *__restrict__ ranges,
@@ -70,7 +45,8 @@ composite_absgrad_kernel(int W, int H, int gx, int tiles, const int2 *__restrict
                          const int32_t *__restrict__ n_contrib, const float *__restrict__ final_T,
                          const float *__restrict__ dL_dpixels, int band, int band_first, int band_tiles,
                          double *__restrict__ acc64) {
-    const int tile = absgrad_tile_of_block(ranges, gx, tiles, band, band_first, band_tiles);
+    // tile_walk.h's quadrant_begin, spelled out: through the helper VGPRs grow (81 -> 82) (EXPERIMENTS.md, 2026-11-26)
+    const int tile = side_pass_tile_of_block(ranges, gx, tiles, band, band_first, band_tiles);
     if (tile < 0 || !compute_locally[tile]) return;  // (no workgroup barrier below: waves leave on their own)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tx = tile % gx, ty = tile / gx;
@@ -104,28 +80,18 @@ composite_absgrad_kernel(int W, int H, int gx, int tiles, const int2 *__restrict
     const int bslot = lane >> 3, bpart = lane & 7;  // phase B: this lane's slot of the batch and its row of the quadrant
     float rho = 0.f;  // (colour blended BEHIND the current position) . g / (the transmittance behind the current position)
     for (int c = ((wlen - 1) / 64) * 64; c >= 0; c -= 64) {  // wave-uniform, back to front
-        const bool have = c + lane < wlen;
-        const uint32_t id = have ? point_list[range.x + c + lane] : 0u;
-        const Entry e = load_entry(have, id, means2D, conic_opacity, (float)qx0, (float)qy0);
-        const unsigned long long m = __ballot(e.relevant);
-        const int nrel = __popcll(m);
-        if (e.relevant) {  // compacted in WALK order: rank = relevant lanes above
-            const int pos = __popcll((m >> lane) >> 1);
-            const float *col = rgb + 3 * (size_t)id;
-            wslab[3 * pos] = make_float4(e.x, e.y, e.a2, e.b2);
-            wslab[3 * pos + 1] = make_float4(e.c2, e.o, __int_as_float(c + lane + 1), 0.f);
-            wslab[3 * pos + 2] = make_float4(col[0], col[1], col[2], 0.f);
-            wid[pos] = id;
-        }
-        {   // the <= CB - 1 slots behind the last entry are inert: every word written
-            const int pad = (-nrel) & (CB - 1);
-            if (lane < pad) {
-                wslab[3 * (nrel + lane)] = make_float4(0.f, 0.f, 0.f, 0.f);
-                wslab[3 * (nrel + lane) + 1] = make_float4(0.f, 0.f, __int_as_float(NO_POS), 0.f);
-                wslab[3 * (nrel + lane) + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
-                wid[nrel + lane] = 0u;
-            }
-        }
+        const int nrel = stage_chunk<BACK_TO_FRONT, 3>(
+            c, lane, wlen, range.x, qx0, qy0, point_list, means2D, conic_opacity, wslab,
+            [](uint32_t) { return 0.f; },
+            [&](int slot, uint32_t id) {
+                const float *col = rgb + 3 * (size_t)id;
+                wslab[3 * slot + 2] = make_float4(col[0], col[1], col[2], 0.f);
+                wid[slot] = id;
+            },
+            [&](int slot) {
+                wslab[3 * slot + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
+                wid[slot] = 0u;
+            });
         __builtin_amdgcn_wave_barrier();  // the wave's own LDS stores above precede its loads below
         for (int b0 = 0; b0 < nrel; b0 += CB) {  // wave-uniform
             // phase A, lane = pixel.  A lane that does not take an entry runs the same arithmetic with alpha = 0:
@@ -136,6 +102,8 @@ composite_absgrad_kernel(int W, int H, int gx, int tiles, const int2 *__restrict
                 const float4 q0 = wslab[3 * (b0 + s)], q1 = wslab[3 * (b0 + s) + 1];  // wave-uniform address: LDS broadcasts
                 const float4 q2 = wslab[3 * (b0 + s) + 2];
                 const float dx = q0.x - pxf, dy = q0.y - pyf;
+                // tile_walk.h's pair_decision, spelled out: through the helper this kernel measured slower than the
+                // parent beyond the parent's own spread (EXPERIMENTS.md, 2026-11-26)
                 const float pe = entry_exponent(q0, q1, dx, dy);
                 const float aar = entry_alpha_raw(q1, pe);  // o exp(power), unclamped
                 const float aal = fminf(0.99f, aar);

@@ -3,16 +3,10 @@
 // K8 (composite.hip) decides what every pixel blends; this kernel walks the same lists once more, forward only, and
 // tells every Gaussian what it was worth in the image K8 drew: on how many pixels it was blended (`hits`), its largest
 // blend weight w = alpha T on any of them (`wmax`: RadSplat's importance) and the sum of its weights (`wsum`:
-// LightGaussian's).  Nothing is re-decided: a pixel's walk ends where K8's ended (n_contrib), and the (pixel, entry)
-// pairs taken are K10's `take` rule -- position + 1 <= n_contrib, power <= 0, alpha >= 1/255 -- in the arithmetic of
-// composite_math.h, which K8 and K10 compile too.  K8 and K10 themselves are untouched; a trainer that does not ask
-// for the statistics never launches this kernel.
+// LightGaussian's).  A side pass in the shape of tile_walk.h, front to back, the id in the record's last word.  K8 and
+// K10 themselves are untouched; a trainer that does not ask for the statistics never launches this kernel.
 //
-// Shape of the work: K8's.  One wave = one 8x8 quadrant, lane = pixel; the list is walked in 64-entry chunks, one entry
-// per lane (index read + gather + quadrant test), the relevant entries are compacted in list order into records in a
-// wave-private LDS slab and read back with wave-uniform addresses.  The walk of a wave ends at the largest n_contrib of
-// its quadrant (K10's bound): entries behind every pixel's stop are never loaded.
-// The reduction over the quadrant's pixels is an LDS TRANSPOSE over a batch of CB = 8 entries: phase A (lane = pixel)
+// The reduction over the quadrant's pixels is the LDS transpose over a batch of CB = 8 entries: phase A (lane = pixel)
 // walks the batch, carries T, and stores every entry's w (0 where the pixel does not blend it) into a wave-private
 // matrix [slot][pixel]; the blend ballot's popcount -- `hits` -- goes into one byte of a scalar register pair.  Phase B (lane = (slot, eighth of the quadrant)) reads its eight pixels with two 16-byte reads, takes
 // their max and their sum in pixel order, and three xor steps combine the eighths: a fixed order, fp32.  Lane 8 * slot
@@ -20,18 +14,16 @@
 // into the caller's arrays: a 64-bit integer add, an unsigned 32-bit max on the float's bits (non-negative floats order
 // as their bit patterns, so the max is exact and independent of the order) and an fp64 add (the quadrant's fp32 sum,
 // widened).  (A 64-lane xor butterfly per entry instead -- twelve dependent cross-lane moves -- measured 3.9 x K8's time
-// for this kernel alone; EXPERIMENTS.md.)  The slots behind a chunk's last relevant entry, up to the batch size, are
-// INERT records: their position word fails `position + 1 <= n_contrib` on every pixel.
+// for this kernel alone; EXPERIMENTS.md.)
 // The four quadrant waves of a tile never synchronise: each issues its own atomics, so a row receives at most
 // 4 x local tiles fp64 additions per launch.  Rows that are blended nowhere are never written.
 #include "common.h"
 #include "composite_math.h"
+#include "tile_walk.h"
 
 namespace {
 
-constexpr int CB = 8;            // entries per transpose batch
 constexpr int WSTR = 64 + 4;     // row stride of the w matrix in floats: phase B's 16-byte reads of the 8 slots spread over the banks
-constexpr int NO_POS = 0x7fffffff;  // position word of an inert slot: no n_contrib reaches it
 
 __global__ void __launch_bounds__(256)
 composite_contrib_kernel(int W, int H, int gx, int tiles, const int2 *__restrict__ ranges,
@@ -40,63 +32,19 @@ composite_contrib_kernel(int W, int H, int gx, int tiles, const int2 *__restrict
                          const int32_t *__restrict__ n_contrib, int band, int band_first, int band_tiles,
                          unsigned long long *__restrict__ hits, unsigned int *__restrict__ wmax,
                          double *__restrict__ wsum) {
-    // block -> tile as in K8: the band's tiles only when the caller named the band (band_first < 0: `band_tiles` is a
-    // capacity, the band is the row hull behind the range table), else XCD-contiguous spans of the hull's tiles first
-    int tile;
-    if (band) {
-        if (band_first < 0) {
-            const int gy = tiles / gx;
-            int2 hull = ranges[tiles];
-            if (hull.x < 0 || hull.y > gy || hull.x >= hull.y) hull = make_int2(0, 0);
-            band_first = hull.x * gx;
-            band_tiles = min((hull.y - hull.x) * gx, band_tiles);
-            if ((int)blockIdx.x >= band_tiles) return;
-        }
-        tile = band_first + gsr_xcd_span_of_block(blockIdx.x, band_tiles);
-    } else {
-        tile = composite_tile_of_block(ranges, gx, tiles);
-    }
-    if (!compute_locally[tile]) return;  // (no workgroup barrier below: waves leave on their own)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tx = tile % gx, ty = tile / gx;
-    const int qx0 = tx * GSR_BLOCK_X + (wave & 1) * 8, qy0 = ty * GSR_BLOCK_Y + (wave >> 1) * 8;
-    const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const int2 range = ranges[tile];
-    const int n = range.y - range.x;
-    const float pxf = (float)px, pyf = (float)py;
-    // where K8 stopped on this pixel; never beyond the list, whatever the caller's array holds
-    const int last = inside ? min(n_contrib[(size_t)py * W + px], n) : 0;
-    int wlen = last;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wlen = max(wlen, __shfl_xor(wlen, d, 64));
-    if (wlen <= 0) return;
+    Quadrant qd;
+    if (!quadrant_begin(qd, W, H, gx, tiles, ranges, compute_locally, n_contrib, band, band_first, band_tiles)) return;
 
     __shared__ __attribute__((aligned(16))) float4 slab[4][64 * 2];   // [wave][slot]: {x, y, a2, b2 | c2, o, position + 1, id}
     __shared__ __attribute__((aligned(16))) float wmat[4][CB * WSTR];  // [wave][slot of the batch][pixel] = w
-    float4 *wslab = slab[wave];
-    float *wm = wmat[wave];
-    const int bslot = lane >> 3, bpart = lane & 7;  // phase B: this lane's slot of the batch and its eighth of the pixels
+    float4 *wslab = slab[qd.wave];
+    float *wm = wmat[qd.wave];
+    const int bslot = qd.lane >> 3, bpart = qd.lane & 7;  // phase B: this lane's slot of the batch and its eighth of the pixels
     float T = 1.0f;
-    for (int c = 0; c < wlen; c += 64) {  // wave-uniform
-        const bool have = c + lane < wlen;
-        const uint32_t id = have ? point_list[range.x + c + lane] : 0u;
-        const Entry e = load_entry(have, id, means2D, conic_opacity, (float)qx0, (float)qy0);
-        const unsigned long long m = __ballot(e.relevant);
-        const int nrel = __popcll(m);
-        if (e.relevant) {
-            const int pos = __popcll(m & ((1ull << lane) - 1ull));
-            wslab[2 * pos] = make_float4(e.x, e.y, e.a2, e.b2);
-            wslab[2 * pos + 1] = make_float4(e.c2, e.o, __int_as_float(c + lane + 1), __uint_as_float(id));
-        }
-        {   // the walk takes CB slots at a time: the <= CB - 1 slots behind the last entry are made inert (both quads
-            // written: nothing stale is ever read)
-            const int pad = (-nrel) & (CB - 1);
-            if (lane < pad) {
-                wslab[2 * (nrel + lane)] = make_float4(0.f, 0.f, 0.f, 0.f);
-                wslab[2 * (nrel + lane) + 1] = make_float4(0.f, 0.f, __int_as_float(NO_POS), 0.f);
-            }
-        }
+    for (int c = 0; c < qd.wlen; c += 64) {  // wave-uniform
+        const int nrel = stage_chunk<FRONT_TO_BACK, 2>(
+            c, qd.lane, qd.wlen, qd.range.x, qd.qx0, qd.qy0, point_list, means2D, conic_opacity, wslab,
+            [](uint32_t id) { return __uint_as_float(id); }, [](int, uint32_t) {}, [](int) {});
         __builtin_amdgcn_wave_barrier();  // the wave's own LDS stores above precede its loads below
         for (int b0 = 0; b0 < nrel; b0 += CB) {  // wave-uniform
             // phase A, lane = pixel: alphas are independent, only the short T chain is sequential
@@ -104,13 +52,11 @@ composite_contrib_kernel(int W, int H, int gx, int tiles, const int2 *__restrict
 #pragma unroll
             for (int s = 0; s < CB; s++) {
                 const float4 q0 = wslab[2 * (b0 + s)], q1 = wslab[2 * (b0 + s) + 1];  // wave-uniform address: LDS broadcasts
-                const float pe = entry_exponent(q0, q1, q0.x - pxf, q0.y - pyf);
-                const float al = fminf(0.99f, entry_alpha_raw(q1, pe));
-                const bool take = __float_as_int(q1.z) <= last && entry_power_ok(q1, pe) && al >= ALPHA_MIN;
-                const float w = take ? al * T : 0.f;  // (selected, never multiplied: an inert slot's alpha is not used)
+                const Pair p = pair_decision(q0, q1, qd.pxf, qd.pyf, qd.last);
+                const float w = p.take ? p.alpha * T : 0.f;  // (selected, never multiplied: an inert slot's alpha is not used)
                 T -= w;  // T (1 - alpha) as K8 forms it: T - alpha T
-                wm[s * WSTR + lane] = w;
-                cnt8 |= (unsigned long long)__popcll(__ballot(take)) << (8 * s);
+                wm[s * WSTR + qd.lane] = w;
+                cnt8 |= (unsigned long long)__popcll(__ballot(p.take)) << (8 * s);
             }
             const int hv = (int)((cnt8 >> (8 * bslot)) & 0xffull);
             __builtin_amdgcn_wave_barrier();

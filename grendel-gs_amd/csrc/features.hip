@@ -2,11 +2,10 @@
 //
 // K8 (composite.hip) decides what every pixel blends; the kernels here walk the same lists once more and blend a
 // per-Gaussian vector f_i in R^C instead of a colour: out[c][p] = sum over the blended entries of w f[c], w = alpha T (no
-// background term, no division by 1 - T_final).  Nothing is re-decided: a pixel's walk ends where K8's ended (n_contrib),
-// and the (pixel, entry) pairs taken are K10's `take` rule -- position + 1 <= n_contrib, power <= 0, alpha >= 1/255 -- in
-// the arithmetic of composite_math.h.  The inverse-depth map (invdepth.hip) is the case C = 1, f = 1 / depth; these
-// kernels have its shape and generalise it.  K8 / K10 / the contribution / invdepth / absgrad kernels are untouched; a
-// trainer that does not ask for a feature map never launches these.
+// background term, no division by 1 - T_final).  A side pass in the shape of tile_walk.h.  The inverse-depth map
+// (invdepth.hip) is the case C = 1, f = 1 / depth (tests/test_gpu_features_pixels.py holds the two forwards bit-equal).
+// K8 / K10 / the contribution / invdepth / absgrad kernels are untouched; a trainer that does not ask for a feature map
+// never launches these.
 //
 // CHANNEL CHUNKS.  The C channels are processed CH = 16 at a time (four float4 beside the entry's record in the slab), by
 // a loop INSIDE the kernel: every chunk walks the quadrant's list again and recomputes alpha -- alpha is never stored per
@@ -15,10 +14,8 @@
 // the slab and are never stored.  The arithmetic of a channel does not depend on C, on the chunk it falls in or on the
 // instantiation: w is the same float and a channel's sum is one fmaf chain in list order.
 //
-// Forward (composite_features_kernel<NQ>): invdepth's forward.  One wave = one 8x8 quadrant, lane = pixel; the list is
-// walked in 64-entry chunks, one entry per lane (index read + gather + quadrant test + the chunk's features), the relevant
-// entries are compacted in list order into records in a wave-private LDS slab (the features beside the position word)
-// and read back with wave-uniform addresses.  Per blended entry one fma per channel into registers, one store per channel
+// Forward (composite_features_kernel<NQ>): invdepth's forward, the chunk's feature quads behind the record's two
+// geometry quads.  Per blended entry one fma per channel into registers, one store per channel
 // per pixel at the end of the channel chunk.  The map is cleared by a fill in front of the launch.
 //   LDS: (2 + NQ) float4 x 72 slots per wave: 6.75 KiB per wave, 27 KiB per workgroup at NQ = 4 (five workgroups per CU of
 //   its 160 KiB); 3.4 KiB / 13.5 KiB at NQ = 1.  119 VGPRs (16 accumulators, and the eight entries of a group in flight
@@ -54,32 +51,13 @@
 // A rounding pass then writes both fp32 records whole: each fp64 sum rounded once; rows blended nowhere are +0.0f.
 #include "common.h"
 #include "composite_math.h"
+#include "tile_walk.h"
 
 namespace {
 
 typedef float feat_f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int CB = 8;                   // entries per batch (forward: per unrolled group of the walk)
-constexpr int MSTR = 66;                // row stride of the (q, u) matrix in 8-byte elements (16-byte aligned rows)
-constexpr int NO_POS = 0x7fffffff;      // position word of an inert slot: no n_contrib reaches it
 constexpr int CH = GSR_FEATURES_CHUNK;  // channels per chunk of the wide instantiation (NQ = 4 float4)
-
-// block -> tile as in K8 / the contribution kernel; -1: this workgroup has no tile
-__device__ __forceinline__ int features_tile_of_block(const int2 *__restrict__ ranges, int gx, int tiles, int band,
-                                                      int band_first, int band_tiles) {
-    if (band) {
-        if (band_first < 0) {  // `band_tiles` is a capacity, the band is the row hull behind the range table
-            const int gy = tiles / gx;
-            int2 hull = ranges[tiles];
-            if (hull.x < 0 || hull.y > gy || hull.x >= hull.y) hull = make_int2(0, 0);
-            band_first = hull.x * gx;
-            band_tiles = min((hull.y - hull.x) * gx, band_tiles);
-            if ((int)blockIdx.x >= band_tiles) return -1;
-        }
-        return band_first + gsr_xcd_span_of_block(blockIdx.x, band_tiles);
-    }
-    return composite_tile_of_block(ranges, gx, tiles);
-}
 
 // channels [ch0 + 4 k, ch0 + 4 k + 4) of row `id` of the [P, C] table, zeros beyond C (rows are not 16-byte aligned)
 __device__ __forceinline__ float4 feature_quad(const float *__restrict__ features, uint32_t id, int C, int c0) {
@@ -100,7 +78,9 @@ composite_features_kernel(int C, int W, int H, int gx, int tiles, const int2 *__
                           const uint8_t *__restrict__ compute_locally, const int32_t *__restrict__ n_contrib, int band,
                           int band_first, int band_tiles, float *__restrict__ out) {
     constexpr int REC = 2 + NQ;  // float4 per slot: {x, y, a2, b2 | c2, o, position + 1, - | NQ feature quads}
-    const int tile = features_tile_of_block(ranges, gx, tiles, band, band_first, band_tiles);
+    // tile_walk.h's quadrant_begin, spelled out: through the helper the C = 16 forward measured slower than the parent
+    // beyond its spread (+0.0008 ms per view) (EXPERIMENTS.md, 2026-11-26)
+    const int tile = side_pass_tile_of_block(ranges, gx, tiles, band, band_first, band_tiles);
     if (tile < 0 || !compute_locally[tile]) return;  // (no workgroup barrier below: waves leave on their own)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tx = tile % gx, ty = tile / gx;
@@ -126,37 +106,24 @@ composite_features_kernel(int C, int W, int H, int gx, int tiles, const int2 *__
 #pragma unroll
         for (int k = 0; k < 4 * NQ; k++) acc[k] = 0.f;
         for (int c = 0; c < wlen; c += 64) {  // wave-uniform
-            const bool have = c + lane < wlen;
-            const uint32_t id = have ? point_list[range.x + c + lane] : 0u;
-            const Entry e = load_entry(have, id, means2D, conic_opacity, (float)qx0, (float)qy0);
-            const unsigned long long m = __ballot(e.relevant);
-            const int nrel = __popcll(m);
-            if (e.relevant) {
-                const int pos = __popcll(m & ((1ull << lane) - 1ull));
-                wslab[REC * pos] = make_float4(e.x, e.y, e.a2, e.b2);
-                wslab[REC * pos + 1] = make_float4(e.c2, e.o, __int_as_float(c + lane + 1), 0.f);
+            const int nrel = stage_chunk<FRONT_TO_BACK, REC>(
+                c, lane, wlen, range.x, qx0, qy0, point_list, means2D, conic_opacity, wslab,
+                [](uint32_t) { return 0.f; },
+                [&](int slot, uint32_t id) {
 #pragma unroll
-                for (int k = 0; k < NQ; k++) wslab[REC * pos + 2 + k] = feature_quad(features, id, C, ch0 + 4 * k);
-            }
-            {   // the walk takes CB slots at a time: the <= CB - 1 slots behind the last entry are made inert (every word
-                // written: nothing stale is ever read; features = 0)
-                const int pad = (-nrel) & (CB - 1);
-                if (lane < pad) {
-                    wslab[REC * (nrel + lane)] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    wslab[REC * (nrel + lane) + 1] = make_float4(0.f, 0.f, __int_as_float(NO_POS), 0.f);
+                    for (int k = 0; k < NQ; k++) wslab[REC * slot + 2 + k] = feature_quad(features, id, C, ch0 + 4 * k);
+                },
+                [&](int slot) {  // (inert: features = 0)
 #pragma unroll
-                    for (int k = 0; k < NQ; k++) wslab[REC * (nrel + lane) + 2 + k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            }
+                    for (int k = 0; k < NQ; k++) wslab[REC * slot + 2 + k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                });
             __builtin_amdgcn_wave_barrier();  // the wave's own LDS stores above precede its loads below
             for (int b0 = 0; b0 < nrel; b0 += CB) {  // wave-uniform
 #pragma unroll
                 for (int s = 0; s < CB; s++) {
                     const float4 q0 = wslab[REC * (b0 + s)], q1 = wslab[REC * (b0 + s) + 1];  // wave-uniform: LDS broadcasts
-                    const float pe = entry_exponent(q0, q1, q0.x - pxf, q0.y - pyf);
-                    const float al = fminf(0.99f, entry_alpha_raw(q1, pe));
-                    const bool take = __float_as_int(q1.z) <= last && entry_power_ok(q1, pe) && al >= ALPHA_MIN;
-                    const float w = take ? al * T : 0.f;  // (selected, never multiplied: an inert slot's alpha is not used)
+                    const Pair p = pair_decision(q0, q1, pxf, pyf, last);
+                    const float w = p.take ? p.alpha * T : 0.f;  // (selected, never multiplied: an inert slot's alpha is not used)
                     T -= w;  // T (1 - alpha) as K8 forms it: T - alpha T
 #pragma unroll
                     for (int k = 0; k < NQ; k++) {
@@ -187,7 +154,9 @@ composite_features_backward_kernel(int C, int W, int H, int gx, int tiles, const
                                    const float *__restrict__ final_T, const float *__restrict__ dL_dout, int band,
                                    int band_first, int band_tiles, double *__restrict__ acc64) {
     constexpr int REC = 3 + NQ;  // float4 per slot: {x, y, a2, b2 | c2, o, position + 1, - | A, B, C, opacity | NQ feature quads}
-    const int tile = features_tile_of_block(ranges, gx, tiles, band, band_first, band_tiles);
+    // tile_walk.h's quadrant_begin, spelled out: through the helper VGPRs grow with the feature gradient (144 -> 152,
+    // 172 -> 180) (EXPERIMENTS.md, 2026-11-26)
+    const int tile = side_pass_tile_of_block(ranges, gx, tiles, band, band_first, band_tiles);
     if (tile < 0 || !compute_locally[tile]) return;  // (no workgroup barrier below: waves leave on their own)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tx = tile % gx, ty = tile / gx;
@@ -241,31 +210,21 @@ composite_features_backward_kernel(int C, int W, int H, int gx, int tiles, const
         float T = T_final;
         float rho = 0.f;  // sum_c g_c (channel c blended BEHIND the current position) / (the transmittance behind it)
         for (int c = ((wlen - 1) / 64) * 64; c >= 0; c -= 64) {  // wave-uniform, back to front
-            const bool have = c + lane < wlen;
-            const uint32_t id = have ? point_list[range.x + c + lane] : 0u;
-            const Entry e = load_entry(have, id, means2D, conic_opacity, (float)qx0, (float)qy0);
-            const unsigned long long m = __ballot(e.relevant);
-            const int nrel = __popcll(m);
-            if (e.relevant) {  // compacted in WALK order: rank = relevant lanes above
-                const int pos = __popcll((m >> lane) >> 1);
-                wslab[REC * pos] = make_float4(e.x, e.y, e.a2, e.b2);
-                wslab[REC * pos + 1] = make_float4(e.c2, e.o, __int_as_float(c + lane + 1), 0.f);
-                wslab[REC * pos + 2] = conic_opacity[id];
+            const int nrel = stage_chunk<BACK_TO_FRONT, REC>(
+                c, lane, wlen, range.x, qx0, qy0, point_list, means2D, conic_opacity, wslab,
+                [](uint32_t) { return 0.f; },
+                [&](int slot, uint32_t id) {
+                    wslab[REC * slot + 2] = conic_opacity[id];
 #pragma unroll
-                for (int k = 0; k < NQ; k++) wslab[REC * pos + 3 + k] = feature_quad(features, id, C, ch0 + 4 * k);
-                wid[pos] = id;
-            }
-            {   // the <= CB - 1 slots behind the last entry are inert: every word written, an opacity that divides
-                const int pad = (-nrel) & (CB - 1);
-                if (lane < pad) {
-                    wslab[REC * (nrel + lane)] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    wslab[REC * (nrel + lane) + 1] = make_float4(0.f, 0.f, __int_as_float(NO_POS), 0.f);
-                    wslab[REC * (nrel + lane) + 2] = make_float4(0.f, 0.f, 0.f, 1.f);
+                    for (int k = 0; k < NQ; k++) wslab[REC * slot + 3 + k] = feature_quad(features, id, C, ch0 + 4 * k);
+                    wid[slot] = id;
+                },
+                [&](int slot) {  // an opacity that divides
+                    wslab[REC * slot + 2] = make_float4(0.f, 0.f, 0.f, 1.f);
 #pragma unroll
-                    for (int k = 0; k < NQ; k++) wslab[REC * (nrel + lane) + 3 + k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    wid[nrel + lane] = 0u;
-                }
-            }
+                    for (int k = 0; k < NQ; k++) wslab[REC * slot + 3 + k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    wid[slot] = 0u;
+                });
             __builtin_amdgcn_wave_barrier();  // the wave's own LDS stores above precede its loads below
             for (int b0 = 0; b0 < nrel; b0 += CB) {  // wave-uniform
                 // phase A, lane = pixel.  A lane that does not take an entry runs the same arithmetic with alpha = 0:
@@ -274,11 +233,8 @@ composite_features_backward_kernel(int C, int W, int H, int gx, int tiles, const
 #pragma unroll
                 for (int s = 0; s < CB; s++) {
                     const float4 q0 = wslab[REC * (b0 + s)], q1 = wslab[REC * (b0 + s) + 1];  // wave-uniform: LDS broadcasts
-                    const float pe = entry_exponent(q0, q1, q0.x - pxf, q0.y - pyf);
-                    const float aar = entry_alpha_raw(q1, pe);  // o exp(power), unclamped
-                    const float aal = fminf(0.99f, aar);
-                    const bool take = __float_as_int(q1.z) <= last && entry_power_ok(q1, pe) && aal >= ALPHA_MIN;
-                    const float ar = take ? aar : 0.f, al = take ? aal : 0.f;  // (selected, never multiplied)
+                    const Pair p = pair_decision(q0, q1, pxf, pyf, last);
+                    const float ar = p.take ? p.raw : 0.f, al = p.take ? p.alpha : 0.f;  // (selected, never multiplied)
                     float cg = 0.f;  // sum_c g_c f_c over the chunk, channel order
 #pragma unroll
                     for (int k = 0; k < NQ; k++) {
@@ -293,7 +249,7 @@ composite_features_backward_kernel(int C, int W, int H, int gx, int tiles, const
                     wm[s * MSTR + lane] = make_float2(ar * (Tn * dot), al * Tn);
                     rho = fmaf(al, dot, rho);
                     T = Tn;
-                    any8 |= (__ballot(take) != 0ull ? 1u : 0u) << s;
+                    any8 |= (__ballot(p.take) != 0ull ? 1u : 0u) << s;
                 }
                 __builtin_amdgcn_wave_barrier();
                 // phase B, lane = (slot, row): the row's eight pixels in order, then the rows by xor 1, 2, 4

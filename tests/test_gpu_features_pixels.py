@@ -21,6 +21,7 @@ import torch
 import composite_refs as R
 import contrib_refs as CR
 import features_refs as FR
+import invdepth_refs as IR
 import test_gpu_composite_pixels as PX
 from helpers import assert_rows_close
 
@@ -142,6 +143,27 @@ def test_a_channel_is_its_one_channel_forward_bit_for_bit(device, case, C):
         code, one = _map(case, device, feat[:, c:c + 1].contiguous())
         assert code == 0 and torch.equal(_bits(one[0]), _bits(out[c])), f"{case.id}: channel {c} of {C} differs"
     assert bool(out.any())
+
+
+@pytest.mark.parametrize("case", SWEEP_CASES[-3:], ids=[c.id for c in SWEEP_CASES[-3:]])
+def test_one_channel_of_reciprocal_depths_is_the_inverse_depth_map_bit_for_bit(device, case):
+    """features.hip's claim: invdepth.hip is the case C = 1, f = 1 / depth.  Both forwards are one fmaf(w, ., acc) chain in
+    list order over a correctly rounded fp32 reciprocal (here: torch's on the host, IEEE division)."""
+    d = PX._dev(case, device)
+    _, nc = _k8(case, device)
+    dep = IR.depths_of(case).to(torch.float32).contiguous()
+    code, one = _map(case, device, (1.0 / dep).reshape(-1, 1).contiguous().to(device))
+    assert code == 0, f"gsr_render_features returned {code}"
+    inv = torch.full((case.H, case.W), NAN, dtype=torch.float32, device=device)
+    dep_d = dep.to(device)
+    code = PX._lib().gsr_render_invdepth(case.P, case.W, case.H, PX._p(d.ranges), PX._p(d.point_list), PX._p(d.means2D),
+                                         PX._p(d.co), PX._p(dep_d), PX._p(d.mask), PX._p(nc), 0, 0, PX._p(inv),
+                                         PX._stream())
+    torch.cuda.synchronize()
+    assert code == 0, f"gsr_render_invdepth returned {code}"
+    differ = int((_bits(one[0]) != _bits(inv)).sum())
+    print(f"FEATURES {case.id}: {differ} of {inv.numel()} pixels differ between the C = 1 map and the inverse-depth map")
+    assert differ == 0 and bool(inv.any())
 
 
 VARIANTS = [c for c in CASES if c.family in R.VARIANT_FAMILIES and c.P > 0]
