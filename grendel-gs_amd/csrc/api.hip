@@ -267,6 +267,33 @@ int gsr_depth_backward_means3d(int P, const int32_t *radii, const float *viewmat
                                        reinterpret_cast<hipStream_t>(stream));
 }
 
+int gsr_render_distortion(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                          const float *means2D, const float *conic_opacity, const float *depths,
+                          const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1, float c2,
+                          int row_lo, int row_hi, float *maps, gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0 || !maps) return GSR_EINVAL;
+    // (point_list may be NULL: every list can be empty)
+    if (P > 0 && (!ranges || !means2D || !conic_opacity || !depths || !compute_locally || !n_contrib)) return GSR_EINVAL;
+    return gsr_launch_composite_distortion(P, width, height, ranges, point_list, means2D, conic_opacity, depths,
+                                           compute_locally, n_contrib, c0, c1, c2, row_lo, row_hi, maps,
+                                           reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_render_distortion_backward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                                   const float *means2D, const float *conic_opacity, const float *depths,
+                                   const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1,
+                                   float c2, const float *final_T, const float *maps, const float *dL_dD, int row_lo,
+                                   int row_hi, float *dL_record, double *acc64, gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    if (!ranges || !means2D || !conic_opacity || !depths || !compute_locally || !n_contrib || !final_T || !maps ||
+        !dL_dD || !dL_record || !acc64)
+        return GSR_EINVAL;
+    return gsr_launch_composite_distortion_backward(P, width, height, ranges, point_list, means2D, conic_opacity, depths,
+                                                    compute_locally, n_contrib, c0, c1, c2, final_T, maps, dL_dD, row_lo,
+                                                    row_hi, dL_record, acc64, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gsr_render_features(int P, int C, int width, int height, const int32_t *ranges, const uint32_t *point_list,
                         const float *means2D, const float *conic_opacity, const float *features,
                         const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi, float *out,

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 OUT_DIR = os.path.join(ROOT, "diff_gaussian_rasterization")
 SO = os.path.join(OUT_DIR, "libgsraster.so")
-UNITS = ["preprocess", "binning", "composite", "contrib", "invdepth", "features", "normals", "absgrad", "loss", "bilagrid", "metrics", "optim", "activations", "filter3d", "knn", "compact", "mcmc", "exchange", "api"]
+UNITS = ["preprocess", "binning", "composite", "contrib", "invdepth", "distortion", "features", "normals", "absgrad", "loss", "bilagrid", "metrics", "optim", "activations", "filter3d", "knn", "compact", "mcmc", "exchange", "api"]
 HEADERS = [os.path.join(HERE, "common.h"), os.path.join(HERE, "composite_math.h"), os.path.join(HERE, "tile_walk.h"), os.path.join(HERE, "radix.h"), os.path.join(HERE, "binning_persist.h"), os.path.join(HERE, "binning_rows.h"), os.path.join(HERE, "binning_host.h"),
            os.path.join(os.path.dirname(ROOT), "include", "gsraster.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall",
@@ -20,7 +20,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # per-unit flags.  normals.hip: scalar fp32 forms only (no v_pk_*_f32 pairing by the compiler) -- the same results, and
 # its loss kernels measured 2-3 % faster that way (EXPERIMENTS.md, 2026-11-26); the other units keep the streams they
 # were verified and measured with
-UNIT_FLAGS = {"normals": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_SCALAR_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+UNIT_FLAGS = {"normals": _SCALAR_FP32, "distortion": _SCALAR_FP32}
 
 
 def _hipcc():

@@ -205,6 +205,16 @@ int gsr_launch_composite_invdepth_backward(int P, int W, int H, const int32_t *r
                                            float *dL_record, double *acc64, hipStream_t stream);
 int gsr_launch_depth_to_means3D(int P, const int32_t *radii, const float *viewmatrix, const float *dL_ddepth,
                                 int row_stride, float *dL_dmeans3D, int overwrite, hipStream_t stream);
+int gsr_launch_composite_distortion(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
+                                    const float *means2D, const float *conic_opacity, const float *depths,
+                                    const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1,
+                                    float c2, int row_lo, int row_hi, float *maps, hipStream_t stream);
+int gsr_launch_composite_distortion_backward(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
+                                             const float *means2D, const float *conic_opacity, const float *depths,
+                                             const uint8_t *compute_locally, const int32_t *n_contrib, float c0,
+                                             float c1, float c2, const float *final_T, const float *maps,
+                                             const float *dL_dD, int row_lo, int row_hi, float *dL_record,
+                                             double *acc64, hipStream_t stream);
 int gsr_launch_composite_features(int P, int C, int W, int H, const int32_t *ranges, const uint32_t *point_list,
                                   const float *means2D, const float *conic_opacity, const float *features,
                                   const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi,

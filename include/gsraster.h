@@ -468,6 +468,45 @@ int gsr_render_invdepth_backward(int P, int width, int height, const int32_t *ra
 int gsr_depth_backward_means3d(int P, const int32_t *radii, const float *viewmatrix, const float *dL_ddepth,
                                int row_stride, float *dL_dmeans3D, int overwrite, gsr_stream_t stream);
 
+/* DEPTH DISTORTION term of a rendered view, with gradients (the second geometric regulariser of Mip-NeRF 360 / 2DGS,
+ * beside the depth-normal term below).  The reference has no such term, so there is NO reference call site:
+ * tests/distortion_refs.py restates the Definition as the pairwise double sum in float64 torch with autograd and is the
+ * arbiter.  New symbols only: gsr_abi_version does not move.
+ * Inputs, the walk and the rule by which an entry is BLENDED on a pixel (weight w_i = alpha_i T_i): gsr_render_invdepth's.
+ * DEPTH MEASURE: m_i = c0 + c1 depth_i + c2 / depth_i in fp32 -- (0, 1, 0) the view-space depth, (0, 0, 1) the inverse
+ * depth, (far / (far - near), 0, -far near / (far - near)) the NDC mapping of 2DGS.  CALLER'S CONDITION: every listed row
+ * has depth > 0.
+ *
+ * Definition, per pixel p over its blended entries in list order:
+ *   D[p] = sum_i sum_{j<i} w_i w_j (m_i - m_j)^2  ( = 1/2 sum_{i,j} w_i w_j (m_i - m_j)^2 ).
+ *
+ * gsr_render_distortion: maps fp32 [4,H,W] = (D, A, mu, S), FULLY overwritten: A = sum w, mu = sum w m / A, S = sum w
+ *   (m - mu)^2 -- the pixel's totals, which the backward reads; they are formed by a centred running update, never from
+ *   raw power sums.  Pixels that blend nothing, pixels of tiles that are not ours and of tiles outside the band of a
+ *   band launch are exactly +0 in all four: the maps are assembled across bands by a SUM.  P == 0 writes the all-zero
+ *   maps and touches nothing else.
+ *
+ * gsr_render_distortion_backward: with g = dL_dD[p] ([H,W]; read on the local tiles only) and (A, mu, S) of `maps`,
+ *   dD/dw_i     = e_i = A (m_i - mu)^2 + S  ( = sum_j w_j (m_i - m_j)^2 ),
+ *   dL/dalpha_i = g (T_i e_i - R_i / (1 - alpha_i)), R_i = the sum of w_j e_j over the blended j behind i; from there
+ *   gsr_render_backward's chain to opacity, conic and means2D as in gsr_render_invdepth_backward;
+ *   dL/dm_i     = sum_p 2 g w_i A (m_i - mu), hence dL/ddepth_i = (c1 - c2 / depth_i^2) dL/dm_i, formed in fp64.
+ *   dL_record fp32 [P,7], FULLY overwritten: [0:2] dL_dmeans2D, [2:6] dL_dconic_opacity, [6] dL_ddepth (which
+ *   gsr_depth_backward_means3d carries on); rows blended nowhere are +0.0f.  acc64: [P,7] doubles, device scratch of the
+ *   caller, cleared by the call (gsr_render_invdepth_backward's reason).  P == 0 returns 0 and touches nothing.
+ *
+ * Both: a negative size, a non-positive frame, or a missing pointer with P > 0: GSR_EINVAL before any device work (the
+ * forward needs `maps` for P == 0 too). */
+int gsr_render_distortion(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                          const float *means2D, const float *conic_opacity, const float *depths,
+                          const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1, float c2,
+                          int row_lo, int row_hi, float *maps, gsr_stream_t stream);
+int gsr_render_distortion_backward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                                   const float *means2D, const float *conic_opacity, const float *depths,
+                                   const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1,
+                                   float c2, const float *final_T, const float *maps, const float *dL_dD, int row_lo,
+                                   int row_hi, float *dL_record, double *acc64, gsr_stream_t stream);
+
 /* N-CHANNEL FEATURE MAP of a rendered view, with gradients (semantic logits, distilled 2D features, normals, an
  * accumulated-opacity map, expected depth, ...).  The reference's rasterizer blends three colour channels only, so there is
  * NO reference call site: oracle/torch_oracle.py's `render` with bg = 0, three channels at a time, differentiated by
