@@ -294,6 +294,36 @@ int gsr_render_distortion_backward(int P, int width, int height, const int32_t *
                                                     row_hi, dL_record, acc64, reinterpret_cast<hipStream_t>(stream));
 }
 
+int gsr_render_surfels(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                       const float *means2D, const float *conic_opacity, const float *rows,
+                       const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1, float c2, int row_lo,
+                       int row_hi, float *surfel, float *aux, int32_t *median_pos, gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0 || !surfel || !aux || !median_pos) return GSR_EINVAL;
+    // (point_list may be NULL: every list can be empty)
+    if (P > 0 && (!ranges || !means2D || !conic_opacity || !rows || !compute_locally || !n_contrib)) return GSR_EINVAL;
+    return gsr_launch_composite_surfels(P, width, height, ranges, point_list, means2D, conic_opacity, rows,
+                                        compute_locally, n_contrib, c0, c1, c2, row_lo, row_hi, surfel, aux, median_pos,
+                                        reinterpret_cast<hipStream_t>(stream));
+}
+
+int gsr_render_surfels_backward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                                const float *means2D, const float *conic_opacity, const float *rows,
+                                const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1, float c2,
+                                const float *final_T, const float *surfel, const float *aux, const int32_t *median_pos,
+                                const float *dL_dsurfel, const float *dL_ddist, const float *dL_dmedian, int row_lo,
+                                int row_hi, float *dL_record, float *dL_rows, double *acc64, gsr_stream_t stream) {
+    if (P < 0 || width <= 0 || height <= 0) return GSR_EINVAL;
+    if (P == 0) return 0;
+    // (each of dL_dsurfel, dL_ddist, dL_dmedian may be NULL: zeros)
+    if (!ranges || !means2D || !conic_opacity || !rows || !compute_locally || !n_contrib || !final_T || !surfel || !aux ||
+        !median_pos || !dL_record || !dL_rows || !acc64)
+        return GSR_EINVAL;
+    return gsr_launch_composite_surfels_backward(P, width, height, ranges, point_list, means2D, conic_opacity, rows,
+                                                 compute_locally, n_contrib, c0, c1, c2, final_T, surfel, aux, median_pos,
+                                                 dL_dsurfel, dL_ddist, dL_dmedian, row_lo, row_hi, dL_record, dL_rows,
+                                                 acc64, reinterpret_cast<hipStream_t>(stream));
+}
+
 int gsr_render_features(int P, int C, int width, int height, const int32_t *ranges, const uint32_t *point_list,
                         const float *means2D, const float *conic_opacity, const float *features,
                         const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi, float *out,

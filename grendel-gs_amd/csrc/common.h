@@ -215,6 +215,18 @@ int gsr_launch_composite_distortion_backward(int P, int W, int H, const int32_t 
                                              float c1, float c2, const float *final_T, const float *maps,
                                              const float *dL_dD, int row_lo, int row_hi, float *dL_record,
                                              double *acc64, hipStream_t stream);
+int gsr_launch_composite_surfels(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
+                                 const float *means2D, const float *conic_opacity, const float *rows,
+                                 const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1, float c2,
+                                 int row_lo, int row_hi, float *surfel, float *aux, int32_t *median_pos,
+                                 hipStream_t stream);
+int gsr_launch_composite_surfels_backward(int P, int W, int H, const int32_t *ranges, const uint32_t *point_list,
+                                          const float *means2D, const float *conic_opacity, const float *rows,
+                                          const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1,
+                                          float c2, const float *final_T, const float *surfel, const float *aux,
+                                          const int32_t *median_pos, const float *dL_dsurfel, const float *dL_ddist,
+                                          const float *dL_dmedian, int row_lo, int row_hi, float *dL_record,
+                                          float *dL_rows, double *acc64, hipStream_t stream);
 int gsr_launch_composite_features(int P, int C, int W, int H, const int32_t *ranges, const uint32_t *point_list,
                                   const float *means2D, const float *conic_opacity, const float *features,
                                   const uint8_t *compute_locally, const int32_t *n_contrib, int row_lo, int row_hi,

@@ -1744,6 +1744,80 @@ class _RenderFeatures(torch.autograd.Function):
         return record[:, 0:2], record[:, 2:6], d_feat, None
 
 
+def distortion_coefficients(distortion):
+    """the depth measure m = c0 + c1 z + c2 / z of the distortion term as three floats: None -> (0, 0, 0) (no term),
+    "depth" -> (0, 1, 0), "inverse" -> (0, 0, 1), ("ndc", near, far) -> 2DGS's NDC mapping, or the triple itself"""
+    if distortion is None:
+        return 0.0, 0.0, 0.0
+    if distortion == "depth":
+        return 0.0, 1.0, 0.0
+    if distortion == "inverse":
+        return 0.0, 0.0, 1.0
+    if isinstance(distortion, (tuple, list)) and len(distortion) == 3:
+        if distortion[0] == "ndc":
+            near, far = float(distortion[1]), float(distortion[2])
+            if not 0.0 < near < far:
+                raise ValueError(f"distortion ('ndc', near, far): 0 < near < far expected, got {near}, {far}")
+            return far / (far - near), 0.0, -far * near / (far - near)
+        if not isinstance(distortion[0], str):
+            return tuple(float(c) for c in distortion)
+    raise ValueError(f"distortion: (c0, c1, c2), 'depth', 'inverse', ('ndc', near, far) or None expected, got "
+                     f"{distortion!r}")
+
+
+class _RenderSurfels(torch.autograd.Function):
+    """the surfel geometry maps of a view K8 has drawn (include/gsraster.h: gsr_render_surfels), from the colour render's
+    own lists, mask, band, final_T and n_contrib: one walk forward, one backward.  backward: the two column groups of the
+    [P,6] record and dL/drows [P,5]; an upstream map nobody used is passed as NULL"""
+
+    @staticmethod
+    def forward(ctx, means2D, conic_opacity, rows, view, coef):
+        if _CAPTURE[0] is not None:
+            raise RuntimeError("diff_gaussian_rasterization: the surfel maps are not available under graph capture "
+                               "(they need the view's final lists)")
+        ranges, point_list, mask, band, final_T, n_contrib, W, H = view
+        means2D, conic_opacity = _f32c(means2D, "means2D"), _f32c(conic_opacity, "conic_opacity")
+        rows = _f32c(rows, "rows")
+        P = means2D.shape[0]
+        if conic_opacity.shape[0] != P or rows.dim() != 2 or tuple(rows.shape) != (P, 5):
+            raise ValueError(f"render_surfels: means2D, conic_opacity and rows [P,5] must have the {P} rows of the view")
+        dev = means2D.device
+        surfel = torch.empty((5, H, W), dtype=torch.float32, device=dev)
+        aux = torch.empty((4, H, W), dtype=torch.float32, device=dev)
+        median_pos = torch.empty((H, W), dtype=torch.int32, device=dev)
+        with _on(dev), kernel_timer.range("composite_surfels", P=P):
+            check(lib.gsr_render_surfels(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D), _ptr(conic_opacity),
+                                         _ptr(rows), _ptr(mask), _ptr(n_contrib), coef[0], coef[1], coef[2], band[0],
+                                         band[1], _ptr(surfel), _ptr(aux), _ptr(median_pos), _stream()),
+                  "gsr_render_surfels")
+        ctx.view, ctx.coef = view, coef
+        ctx.set_materialize_grads(False)  # an output nobody used arrives as None and goes on as NULL
+        ctx.save_for_backward(means2D, conic_opacity, rows, surfel, aux, median_pos)
+        dist, med = aux[0], aux[3]
+        ctx.mark_non_differentiable(median_pos)
+        return surfel, dist, med, median_pos
+
+    @staticmethod
+    def backward(ctx, g_surfel, g_dist, g_med, _g_pos):
+        means2D, conic_opacity, rows, surfel, aux, median_pos = ctx.saved_tensors
+        ranges, point_list, mask, band, final_T, n_contrib, W, H = ctx.view
+        P = means2D.shape[0]
+        dev = means2D.device
+        ups = [g.float().contiguous() if g is not None else None for g in (g_surfel, g_dist, g_med)]
+        record = torch.empty((P, 6), dtype=torch.float32, device=dev)
+        d_rows = torch.empty((P, 5), dtype=torch.float32, device=dev)
+        acc64 = torch.empty((P, 10), dtype=torch.float64, device=dev)
+        c = ctx.coef
+        with _on(dev), kernel_timer.range("composite_surfels_backward", P=P):
+            check(lib.gsr_render_surfels_backward(P, W, H, _ptr(ranges), _ptr(point_list), _ptr(means2D),
+                                                  _ptr(conic_opacity), _ptr(rows), _ptr(mask), _ptr(n_contrib), c[0], c[1],
+                                                  c[2], _ptr(final_T), _ptr(surfel), _ptr(aux), _ptr(median_pos),
+                                                  *[_ptr(g) if g is not None else None for g in ups], band[0], band[1],
+                                                  _ptr(record), _ptr(d_rows), _ptr(acc64), _stream()),
+                  "gsr_render_surfels_backward")
+        return record[:, 0:2], record[:, 2:6], d_rows, None, None
+
+
 class _ViewDepths(torch.autograd.Function):
     """K1's `depths` (the same values) with a grad_fn: depth = ([p,1] viewmatrix)[2], so dL/dmeans3D = dL/ddepth times
     the third column of the view matrix (gsr_depth_backward_means3d).  The projection ops themselves keep `depths`
@@ -1855,6 +1929,20 @@ class GaussianRasterizer(nn.Module):
             raise RuntimeError("render_features: call render_gaussians of the same view with cuda_args['features'] set "
                                "first (it leaves the view's lists and n_contrib in cuda_args)")
         return _RenderFeatures.apply(means2D, conic_opacity, features, view)
+
+    def render_surfels(self, means2D, conic_opacity, rows, cuda_args, distortion=None):
+        """-> (surfel [5,H,W] = (A, D, N), distortion [H,W], median_depth [H,W], median_pos int32 [H,W]) of the view
+        (extension of this build; include/gsraster.h: gsr_render_surfels): the map normal_consistency reads, the depth
+        distortion term of 2DGS on m = c0 + c1 z + c2 / z, the depth of the last blended entry with a transmittance above
+        0.5 in front of it, and that entry's list position + 1 -- one walk over the lists each way.  `rows`: fp32 [P,5]
+        as normal_rows makes them.  `distortion`: (c0, c1, c2), "depth", "inverse", ("ndc", near, far), or None (a zero
+        map).  Call it after render_gaussians of the SAME view and rows with cuda_args["features"] set.  Differentiable
+        in means2D, conic_opacity and rows; the choice of the median entry passes no gradient but to that entry's z."""
+        view = cuda_args.get(_FEATURES_KEY) if isinstance(cuda_args, dict) else None
+        if view is None:
+            raise RuntimeError("render_surfels: call render_gaussians of the same view with cuda_args['features'] set "
+                               "first (it leaves the view's lists and n_contrib in cuda_args)")
+        return _RenderSurfels.apply(means2D, conic_opacity, rows, view, distortion_coefficients(distortion))
 
 
 # ------------------------------------------------------------------------------- N1: fused loss

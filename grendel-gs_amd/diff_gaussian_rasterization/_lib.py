@@ -161,6 +161,10 @@ SIGNATURES = {
                                                                                                  c_void_p]),
     "gsr_render_distortion_backward": (c_int, [c_int, c_int, c_int] + [c_void_p] * 7 + [c_float] * 3 + [c_void_p] * 3 +
                                        [c_int, c_int] + [c_void_p] * 3),
+    "gsr_render_surfels": (c_int, [c_int, c_int, c_int] + [c_void_p] * 7 + [c_float] * 3 + [c_int, c_int] +
+                           [c_void_p] * 4),
+    "gsr_render_surfels_backward": (c_int, [c_int, c_int, c_int] + [c_void_p] * 7 + [c_float] * 3 + [c_void_p] * 7 +
+                                    [c_int, c_int] + [c_void_p] * 4),
     "gsr_depth_backward_means3d": (c_int, [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_int, c_void_p]),
     "gsr_render_features": (c_int, [c_int] * 4 + [c_void_p] * 7 + [c_int, c_int, c_void_p, c_void_p]),
     "gsr_render_features_backward": (c_int, [c_int] * 4 + [c_void_p] * 9 + [c_int, c_int] + [c_void_p] * 4),

@@ -194,6 +194,32 @@ def _refuse_normals():
                            "run the iteration eagerly")
 
 
+# ------------------------------------------------------------------------------ surfel geometry pass (opt-in)
+# [on, distortion]; GSR_SURFELS=1 in the environment: on, with no distortion mapping (a zero map) until set_surfel_pass
+_SURFELS = [os.environ.get("GSR_SURFELS", "0") not in ("", "0"), None]
+
+
+def set_surfel_pass(on, distortion=None):
+    """True (default False; GSR_SURFELS=1 in the environment: True, distortion=None): under set_normal_consistency(True), render_final blends camera k's surfel rows with
+    GaussianRasterizer.render_surfels (include/gsraster.h: gsr_render_surfels) where it calls render_features otherwise:
+    one walk over the lists each way with a fixed channel set.  pkg["batched_features"][k] is the same [5,H,W] map (A, D,
+    N), so loss_distribution.normal_consistency_loss works unchanged, and the package gains pkg["batched_distortion"]
+    (the depth distortion term of 2DGS on m = c0 + c1 z + c2 / z; `distortion`: (c0, c1, c2), "depth", "inverse", ("ndc",
+    near, far), or None for a zero map -- loss_distribution.distortion_loss), pkg["batched_median_depth"] and
+    pkg["batched_median_pos"] ([H,W] each, per camera, None where the camera is not rendered here).  It requires
+    set_normal_consistency(True) (ValueError) and shares every refusal of it: world size > 1, graph capture,
+    set_features, pose refinement.  With the switch off the step is what it was, call for call."""
+    if on and not _NORMALS[0]:
+        raise ValueError("set_surfel_pass(True): call set_normal_consistency(True) first (the pass blends its surfel rows)")
+    if on:
+        _dgr.distortion_coefficients(distortion)  # (a malformed mapping raises here, not in the step)
+    _SURFELS[0], _SURFELS[1] = bool(on), (distortion if on else None)
+
+
+def get_surfel_pass():
+    return _SURFELS[0]
+
+
 # ------------------------------------------------------------------------------ absolute gradients (opt-in)
 _ABSGRAD = [os.environ.get("GSR_ABSGRAD", "0") not in ("", "0")]
 _LAST_ROUTES = [None]  # the latest batch's {camera: (send_idx, send_splits, recv_splits, group)}, kept while _ABSGRAD is set
@@ -940,6 +966,8 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
     # timing mode a user may have set
     from gaussian_renderer.workload_division import timings_have_consumer
     timing = "deferred" if (mode != "train" or timings_have_consumer()) else "off"
+    if _SURFELS[0] and not _NORMALS[0]:
+        raise ValueError("set_surfel_pass(True): needs set_normal_consistency(True) (the pass blends its surfel rows)")
     if _NORMALS[0]:
         _refuse_normals()
     if timers is not None:
@@ -1080,6 +1108,8 @@ def distributed_preprocess3dgs_and_all2all_final(batched_viewpoint_cameras, pc, 
             # scales keep the order of the axes) and the radii K1 left for that view
             pkg["_features_rows"] = [_dgr.normal_rows(pc._xyz, pc._scaling, pc._rotation, p[3],
                                                       r.raster_settings.viewmatrix) for p, r in zip(params, rasterizers)]
+            if _SURFELS[0]:
+                pkg["_surfel_pass"] = (_SURFELS[1],)  # (render_final: render_surfels in place of render_features)
         return pkg
     if W * len(params) > 512:
         raise ValueError(f"world size x batch size = {W * len(params)} exceeds the 512 (destination, camera) segments "
@@ -1150,6 +1180,8 @@ def _render_cameras(pkg, batched_strategies):
     images, masks, late = [], [], []
     invdepth = [None] * len(batched_strategies)  # (left in the package only when a camera's cuda_args ask for the map)
     features = [None] * len(batched_strategies)  # (likewise)
+    surfel_pass = pkg.get("_surfel_pass")  # (set_surfel_pass: the distortion mapping, in a tuple)
+    surfels = [[None] * len(batched_strategies) for _ in range(3)]  # distortion, median depth, median position
     mine = [k for k, st in enumerate(batched_strategies) if utils.GLOBAL_RANK in st.gpu_ids]
     dev0 = pkg["batched_means2D_redistributed"][mine[0]].device if mine else None
     two = (_EXCHANGE_OPTIONS["camera_streams"] > 1 and len(mine) > 1 and dev0 is not None and dev0.type == "cuda"
@@ -1201,8 +1233,16 @@ def _render_cameras(pkg, batched_strategies):
                         invdepth[k].record_stream(main)
                 if cuda_args.get("features"):
                     rows = pkg["_features_rows"]  # (a list: per-camera rows, set_normal_consistency)
-                    features[k] = pkg["batched_rasterizers"][k].render_features(
-                        means2D, conic_opacity, rows[k] if isinstance(rows, list) else rows, cuda_args)
+                    if surfel_pass is not None:
+                        features[k], surfels[0][k], surfels[1][k], surfels[2][k] = \
+                            pkg["batched_rasterizers"][k].render_surfels(means2D, conic_opacity, rows[k], cuda_args,
+                                                                         distortion=surfel_pass[0])
+                        if two:
+                            for t in (surfels[0][k], surfels[1][k], surfels[2][k]):
+                                t.record_stream(main)
+                    else:
+                        features[k] = pkg["batched_rasterizers"][k].render_features(
+                            means2D, conic_opacity, rows[k] if isinstance(rows, list) else rows, cuda_args)
                     if two:
                         features[k].record_stream(main)
             if two:
@@ -1218,6 +1258,8 @@ def _render_cameras(pkg, batched_strategies):
         pkg["batched_invdepth"] = invdepth
     if any(ca.get("features") for ca in pkg["batched_cuda_args"]):
         pkg["batched_features"] = features
+    if surfel_pass is not None:
+        pkg["batched_distortion"], pkg["batched_median_depth"], pkg["batched_median_pos"] = surfels
     return images, masks, late
 
 

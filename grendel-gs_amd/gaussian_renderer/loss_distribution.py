@@ -412,3 +412,27 @@ def normal_consistency_loss(pkg, batched_cameras, weight):
     if total is None:
         raise RuntimeError("normal_consistency_loss: no camera of the batch was rendered on this rank")
     return total
+
+
+def distortion_loss(pkg, batched_cameras, weight):
+    """the depth distortion term of the batch (Mip-NeRF 360 / 2DGS), for the trainer to add to its loss: the sum over the
+    cameras rendered here of weight / (H W) times the sum over the pixels of the distortion map that render_final left
+    in pkg["batched_distortion"] under gaussian_renderer.set_surfel_pass(True, distortion=...).  The upstream gradient
+    is a constant map: no kernel of its own, the surfel pass's one backward walk carries it with the depth-normal
+    term's.  Raises when the pass ran without a distortion mapping."""
+    maps = pkg.get("batched_distortion")
+    if maps is None or pkg.get("_surfel_pass") is None:
+        raise RuntimeError("distortion_loss: call gaussian_renderer.set_surfel_pass(True, distortion=...) before the "
+                           "batch is preprocessed and rendered (pkg carries no distortion map)")
+    if pkg["_surfel_pass"][0] is None:
+        raise RuntimeError("distortion_loss: the surfel pass ran without a distortion mapping (set_surfel_pass(True, "
+                           "distortion='depth' | 'inverse' | ('ndc', near, far) | (c0, c1, c2)))")
+    total = None
+    for dmap in maps:
+        if dmap is None:
+            continue
+        term = dmap.sum() * (float(weight) / dmap.numel())
+        total = term if total is None else total + term
+    if total is None:
+        raise RuntimeError("distortion_loss: no camera of the batch was rendered on this rank")
+    return total

@@ -507,6 +507,45 @@ int gsr_render_distortion_backward(int P, int width, int height, const int32_t *
                                    float c2, const float *final_T, const float *maps, const float *dL_dD, int row_lo,
                                    int row_hi, float *dL_record, double *acc64, gsr_stream_t stream);
 
+/* SURFEL GEOMETRY PASS of a rendered view, with gradients: accumulated opacity, expected depth, blended normal, MEDIAN
+ * depth and the depth distortion term above in one forward and one backward walk (what a 2DGS / PGSR / RaDe-GS trainer
+ * asks for per view).  The reference has no such pass, so there is NO reference call site: tests/surfel_refs.py restates
+ * the definitions in float64 torch with autograd and is the arbiter.  New symbols only: gsr_abi_version does not move.
+ * Inputs, the walk and the BLENDED rule: gsr_render_distortion's, with `rows` fp32 [P,5] = (1, z, n_x, n_y, n_z) as
+ * gsr_normal_rows_forward writes them in place of `depths`: columns 1..4 are read, column 0 is taken as the constant 1.
+ * m_i = c0 + c1 z_i + c2 / z_i; (0, 0, 0) gives a zero distortion map.  CALLER'S CONDITION: every listed row has z > 0.
+ *
+ * gsr_render_surfels, all three FULLY overwritten:
+ *   surfel fp32 [5,H,W] = (A, D, N): A = sum w, D = sum w z, N = sum w n -- the map gsr_normal_consistency_* read;
+ *   aux fp32 [4,H,W] = (Dist, mu, S, med): Dist, mu, S as gsr_render_distortion's D, mu, S; med = z of the LAST blended
+ *     entry whose transmittance in front of it is > 0.5 (2DGS's median depth on the Gaussian centre's view depth);
+ *   median_pos int32 [H,W]: that entry's list position + 1, 0 where nothing is blended.
+ *   Pixels that blend nothing, pixels of tiles that are not ours or outside the band are exactly +0 in every map: bands
+ *   assemble by a SUM.  P == 0 writes the all-zero maps and touches nothing else.
+ *
+ * gsr_render_surfels_backward: upstream dL_dsurfel [5,H,W], dL_ddist [H,W], dL_dmedian [H,W], each may be NULL (zeros;
+ *   the record is the same bits as with an all-zero map).  With e_i = g_A + g_D z_i + g_N . n_i + g_Dist (A (m_i - mu)^2
+ *   + S): dL/dalpha_i = T_i e_i - R_i / (1 - alpha_i), R_i = the sum of w_j e_j over the blended j behind i, then
+ *   gsr_render_backward's chain to opacity, conic and means2D;  dL/dz_i = sum_p w_i (g_D + 2 g_Dist A (m_i - mu) (c1 - c2
+ *   / z_i^2)) + the sum of g_med over the pixels whose median_pos names i;  dL/dn_i = sum_p w_i g_N.  The choice of the
+ *   median entry passes no gradient to alpha or the geometry.
+ *   dL_record fp32 [P,6] = [0:2] dL_dmeans2D, [2:6] dL_dconic_opacity; dL_rows fp32 [P,5] = (+0, dL/dz, dL/dn); both FULLY
+ *   overwritten, rows blended nowhere are +0.0f.  acc64: [P,10] doubles, device scratch of the caller, cleared by the
+ *   call.  P == 0 returns 0 and touches nothing.
+ *
+ * row_lo / row_hi as gsr_render_invdepth.  Both: a negative size, a non-positive frame, or a missing pointer with P > 0:
+ * GSR_EINVAL before any device work (the forward needs its three outputs for P == 0 too). */
+int gsr_render_surfels(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                       const float *means2D, const float *conic_opacity, const float *rows,
+                       const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1, float c2, int row_lo,
+                       int row_hi, float *surfel, float *aux, int32_t *median_pos, gsr_stream_t stream);
+int gsr_render_surfels_backward(int P, int width, int height, const int32_t *ranges, const uint32_t *point_list,
+                                const float *means2D, const float *conic_opacity, const float *rows,
+                                const uint8_t *compute_locally, const int32_t *n_contrib, float c0, float c1, float c2,
+                                const float *final_T, const float *surfel, const float *aux, const int32_t *median_pos,
+                                const float *dL_dsurfel, const float *dL_ddist, const float *dL_dmedian, int row_lo,
+                                int row_hi, float *dL_record, float *dL_rows, double *acc64, gsr_stream_t stream);
+
 /* N-CHANNEL FEATURE MAP of a rendered view, with gradients (semantic logits, distilled 2D features, normals, an
  * accumulated-opacity map, expected depth, ...).  The reference's rasterizer blends three colour channels only, so there is
  * NO reference call site: oracle/torch_oracle.py's `render` with bg = 0, three channels at a time, differentiated by
