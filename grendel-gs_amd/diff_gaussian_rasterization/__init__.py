@@ -32,7 +32,7 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "_C", "load_im
            "preprocess_gaussians_raw_batched", "knn_mean_dist2", "group_rows", "gather_rows", "densify_plan", "densify_move", "exchange_need",
            "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "absgrad_rows", "densify_stats",
            "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing", "image_metrics", "metrics_from_sums",
-           "bilagrid_slice", "bilagrid_tv"]
+           "bilagrid_slice", "bilagrid_tv", "vq_assign", "vq_update", "vq_segment_sum", "vq_decode"]
 
 BLOCK_X, BLOCK_Y, ONE_DIM_BLOCK_SIZE = 16, 16, 256
 
@@ -2936,6 +2936,114 @@ def knn_mean_dist2(points):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
     check(lib.gsr_knn_mean_dist2(P, _ptr(pts), _ptr(out), _ptr(ws), nbytes, _stream()), "gsr_knn_mean_dist2")
     return out
+
+
+# ------------------------------------------------------------------ codebook compression (vq.hip; include/gsraster.h)
+def _vq_args(rows, idx, codebook, what):
+    """the checks gsr_vq_* cannot make: device tensors, fp32 rows [P,D] and codebook [K,D], int32 idx [P]"""
+    for t, n in ((rows, "rows"), (idx, "idx"), (codebook, "codebook")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"diff_gaussian_rasterization: `{n}` must live on the gfx950 device (no CPU fallback)")
+    if any(t is not None and (t.dtype != torch.float32 or t.dim() != 2) for t in (rows, codebook)):
+        raise ValueError(f"{what}: rows [P,D] and codebook [K,D] must be float32")
+    if rows is not None and codebook is not None and rows.shape[1] != codebook.shape[1]:
+        raise ValueError(f"{what}: rows have {rows.shape[1]} columns, the codebook {codebook.shape[1]}")
+    if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or
+                            (rows is not None and idx.shape[0] != rows.shape[0])):
+        raise ValueError(f"{what}: idx must be int32 [P]")
+    K, D = (codebook if codebook is not None else rows).shape
+    if codebook is not None and not (1 <= K <= 65536):
+        raise ValueError(f"{what}: 1 <= K <= 65536, got {K}")
+    if not (1 <= D <= 64):
+        raise ValueError(f"{what}: 1 <= D <= 64, got {D}")
+
+
+def _vq_workspace(P, K, D, device):
+    nbytes = lib.gsr_vq_workspace_bytes(P, K, D)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def vq_assign(rows, codebook, return_dist=False):
+    """idx int32 [P]: the nearest centroid of every row under the squared Euclidean distance, the lowest index on a tie
+    (gsr_vq_assign: fp32 MFMA, within fp32 rounding of the exact assignment); with return_dist also dist2 fp32 [P], the
+    squared distance to the chosen centroid.  rows fp32 [P,D], codebook fp32 [K,D], K <= 65536, D <= 64."""
+    _vq_args(rows, None, codebook, "vq_assign")
+    rows, codebook = rows.detach().contiguous(), codebook.detach().contiguous()
+    P, D = rows.shape
+    idx = torch.empty(P, dtype=torch.int32, device=rows.device)
+    dist = torch.empty(P, dtype=torch.float32, device=rows.device) if return_dist else None
+    with _on(rows.device):
+        check(lib.gsr_vq_assign(P, codebook.shape[0], D, _ptr(rows), _ptr(codebook), _ptr(idx), _ptr(dist), _stream()),
+              "gsr_vq_assign")
+    return (idx, dist) if return_dist else idx
+
+
+def vq_update(rows, idx, codebook, weights=None):
+    """one Lloyd step IN PLACE: codebook[k] <- sum w_i rows[i] / sum w_i over idx[i] == k; clusters without rows keep their
+    centroid.  Returns (count int32 [K], wsum fp32 [K]).  fp64 sums in a fixed order: the same bits on every run.  An idx
+    outside [0,K) is skipped.  weights: fp32 [P] or None (all ones)."""
+    _vq_args(rows, idx, codebook, "vq_update")
+    if not codebook.is_contiguous():
+        raise ValueError("vq_update: the codebook is updated in place and must be contiguous")
+    rows, idx = rows.detach().contiguous(), idx.contiguous()
+    (P, D), K = rows.shape, codebook.shape[0]
+    if weights is not None:
+        if not weights.is_cuda:
+            raise RuntimeError("diff_gaussian_rasterization: `weights` must live on the gfx950 device (no CPU fallback)")
+        if weights.dtype != torch.float32 or weights.shape != (P,):
+            raise ValueError("vq_update: weights must be float32 [P]")
+        weights = weights.detach().contiguous()
+    count = torch.zeros(K, dtype=torch.int32, device=rows.device)
+    wsum = torch.zeros(K, dtype=torch.float32, device=rows.device)
+    if P:
+        with _on(rows.device):
+            ws, nbytes = _vq_workspace(P, K, D, rows.device)
+            check(lib.gsr_vq_update(P, K, D, _ptr(rows), _ptr(idx), _ptr(weights), _ptr(codebook.detach()), _ptr(count),
+                                    _ptr(wsum), _ptr(ws), nbytes, _stream()), "gsr_vq_update")
+    return count, wsum
+
+
+def vq_segment_sum(rows, idx, K):
+    """sums fp32 [K,D], sums[k] = the sum of rows[i] over idx[i] == k (gsr_vq_segment_sum: fp64, fixed order, no
+    floating-point atomics); an idx outside [0,K) is skipped"""
+    _vq_args(rows, idx, None, "vq_segment_sum")
+    if not (1 <= K <= 65536):
+        raise ValueError(f"vq_segment_sum: 1 <= K <= 65536, got {K}")
+    rows, idx = rows.detach().contiguous(), idx.contiguous()
+    P, D = rows.shape
+    if P == 0:
+        return torch.zeros((K, D), dtype=torch.float32, device=rows.device)
+    sums = torch.empty((K, D), dtype=torch.float32, device=rows.device)
+    with _on(rows.device):
+        ws, nbytes = _vq_workspace(P, K, D, rows.device)
+        check(lib.gsr_vq_segment_sum(P, K, D, _ptr(rows), _ptr(idx), _ptr(sums), _ptr(ws), nbytes, _stream()),
+              "gsr_vq_segment_sum")
+    return sums
+
+
+class _VqDecode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, codebook, idx):
+        _vq_args(None, idx, codebook, "vq_decode")
+        cb, idx = codebook.detach().contiguous(), idx.contiguous()
+        K, D = cb.shape
+        out = torch.empty((idx.shape[0], D), dtype=torch.float32, device=cb.device)
+        with _on(cb.device):
+            check(lib.gsr_vq_decode(idx.shape[0], K, D, _ptr(cb), _ptr(idx), _ptr(out), _stream()), "gsr_vq_decode")
+        ctx.save_for_backward(idx)
+        ctx.K = K
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        return vq_segment_sum(g.float(), idx, ctx.K), None
+
+
+def vq_decode(codebook, idx):
+    """out fp32 [P,D] = codebook[idx] (zeros for an idx outside [0,K)).  Differentiable with respect to the codebook: its
+    gradient is the per-cluster sum of the upstream rows (vq_segment_sum); idx receives none."""
+    return _VqDecode.apply(codebook, idx)
 
 
 def group_rows(dest, num_groups):

@@ -86,6 +86,11 @@ SIGNATURES = {
     "gsr_scatter_add_rows": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_knn_workspace_bytes": (c_size_t, [c_int]),
     "gsr_knn_mean_dist2": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gsr_vq_workspace_bytes": (c_size_t, [c_int] * 3),
+    "gsr_vq_assign": (c_int, [c_int] * 3 + [c_void_p] * 5),
+    "gsr_vq_update": (c_int, [c_int] * 3 + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "gsr_vq_segment_sum": (c_int, [c_int] * 3 + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "gsr_vq_decode": (c_int, [c_int] * 3 + [c_void_p] * 4),
     "gsr_densify_stats": (c_int, [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_group_rows_bytes": (c_size_t, [c_int64]),
     "gsr_group_rows": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

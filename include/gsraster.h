@@ -925,6 +925,38 @@ size_t gsr_knn_workspace_bytes(int P);
 int gsr_knn_mean_dist2(int P, const float *points, float *mean_dist2, void *workspace, size_t workspace_bytes,
                        gsr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CODEBOOK COMPRESSION of parameter rows (vq.hip): k-means assignment on the fp32 matrix pipe, the Lloyd update / the
+ * per-cluster sums, and the decode.  The reference has no compression, so there is NO reference call site: plain float64
+ * torch on the host is the arbiter (tests/test_gpu_vq_rows.py).  New symbols only: gsr_abi_version does not move.
+ * rows fp32 [P,D] dense (row stride D, 4-byte alignment is all that is assumed), codebook fp32 [K,D], idx int32 [P].
+ * 0 <= P, 1 <= K <= 65536, 1 <= D <= 64; anything else, or a missing pointer with P > 0: GSR_EINVAL before any device
+ * work.  P == 0 returns 0 without a launch and touches nothing.
+ *
+ * gsr_vq_assign: idx[i] = the LOWEST k that minimises s(i,k) = |c_k|^2 - 2 x_i . c_k, the dot products on
+ *   v_mfma_f32_16x16x4_f32 (exact fp32 operands and accumulation): the squared distance to the chosen centroid exceeds
+ *   the smallest one by fp32 rounding of a D-term dot product and two norms at most.  Non-finite inputs are not a
+ *   supported case; they still give an index in [0,K).  dist2 fp32 [P] or NULL: the plain fp32 sum over d of
+ *   (x_i[d] - c_idx[d])^2, recomputed directly (>= 0; not s + |x|^2).  No workspace.
+ * gsr_vq_update: one Lloyd step in place, codebook[k] <- sum_i w_i x_i / sum_i w_i over the rows with idx[i] == k
+ *   (weights fp32 [P], or NULL for w = 1); count int32 [K] = the number of those rows, wsum fp32 [K] = sum_i w_i.  A
+ *   cluster with no rows (or whose weights do not sum to a positive number) keeps its centroid bit for bit.
+ * gsr_vq_segment_sum: sums fp32 [K,D] FULLY overwritten, sums[k] = the sum of rows[i] over idx[i] == k (zero for a
+ *   cluster with no rows): the gradient of gsr_vq_decode with respect to the codebook.
+ *   Both: an index outside [0,K) is skipped, never dereferenced.  Sums run in fp64 in a fixed order (stable sort by
+ *   cluster, then row order) and are rounded to fp32 once; no floating-point atomics, the same bits on every run; a
+ *   cluster holding most rows is spread over many wavefronts.  workspace: gsr_vq_workspace_bytes(P, K, D) bytes of device
+ *   memory, any content (0 for an invalid shape); too small: GSR_ENOSPACE.
+ * gsr_vq_decode: out fp32 [P,D], out[i] = codebook[idx[i]], all zeros for an index outside [0,K).  No workspace. */
+size_t gsr_vq_workspace_bytes(int P, int K, int D);
+int gsr_vq_assign(int P, int K, int D, const float *rows, const float *codebook, int32_t *idx, float *dist2,
+                  gsr_stream_t stream);
+int gsr_vq_update(int P, int K, int D, const float *rows, const int32_t *idx, const float *weights, float *codebook,
+                  int32_t *count, float *wsum, void *workspace, size_t workspace_bytes, gsr_stream_t stream);
+int gsr_vq_segment_sum(int P, int K, int D, const float *rows, const int32_t *idx, float *sums, void *workspace,
+                       size_t workspace_bytes, gsr_stream_t stream);
+int gsr_vq_decode(int P, int K, int D, const float *codebook, const int32_t *idx, float *out, gsr_stream_t stream);
+
 /* N4: the per-iteration densification statistics in ONE launch (ABI 12) -- densification.py:13-25 of the reference, run after
  * every backward of the densification phase: for the rows with radii > 0
  *   max_radii2D = max(max_radii2D, radii);  xyz_gradient_accum += |grad[:, :2]|;  denom += 1
