@@ -32,7 +32,8 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "_C", "load_im
            "preprocess_gaussians_raw_batched", "knn_mean_dist2", "group_rows", "gather_rows", "densify_plan", "densify_move", "exchange_need",
            "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "absgrad_rows", "densify_stats",
            "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing", "image_metrics", "metrics_from_sums",
-           "bilagrid_slice", "bilagrid_tv", "vq_assign", "vq_update", "vq_segment_sum", "vq_decode"]
+           "bilagrid_slice", "bilagrid_tv", "vq_assign", "vq_update", "vq_segment_sum", "vq_decode",
+           "tsdf_integrate", "tsdf_extract"]
 
 BLOCK_X, BLOCK_Y, ONE_DIM_BLOCK_SIZE = 16, 16, 256
 
@@ -3044,6 +3045,88 @@ def vq_decode(codebook, idx):
     """out fp32 [P,D] = codebook[idx] (zeros for an idx outside [0,K)).  Differentiable with respect to the codebook: its
     gradient is the per-cluster sum of the upstream rows (vq_segment_sum); idx receives none."""
     return _VqDecode.apply(codebook, idx)
+
+
+# ------------------------------------------------------------------ mesh extraction (tsdf.hip; include/gsraster.h)
+TSDF_MAX_VIEWS = 16
+
+
+def _tsdf_planes(what, dims, tsdf, weight, rgb):
+    """the checks gsr_tsdf_* cannot make: contiguous fp32 device planes of the brick-major shape of `dims` = (X, Y, Z)"""
+    X, Y, Z = (int(d) for d in dims)
+    if X <= 0 or Y <= 0 or Z <= 0 or X % 8 or Y % 8 or Z % 8:
+        raise ValueError(f"{what}: dims must be positive multiples of 8, got {(X, Y, Z)}")
+    shape = (Z // 8, Y // 8, X // 8, 8, 8, 8)
+    for t, n, s in ((tsdf, "tsdf", shape), (weight, "weight", shape), (rgb, "rgb", (3,) + shape)):
+        if t is None and n == "rgb":
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"diff_gaussian_rasterization: `{n}` must live on the gfx950 device (no CPU fallback)")
+        if t.dtype != torch.float32 or tuple(t.shape) != s or not t.is_contiguous() or t.device != tsdf.device:
+            raise ValueError(f"{what}: {n} must be a contiguous float32 tensor of shape {s} on {tsdf.device}")
+    return X, Y, Z
+
+
+def tsdf_integrate(tsdf, weight, rgb, origin, voxel_size, dims, trunc, depths, viewmatrices, tanfovx, tanfovy,
+                   colors=None, view_weights=None, depth_trunc=float("inf"), near=0.2):
+    """Fuse up to 16 depth maps into the brick-major planes IN PLACE (gsr_tsdf_integrate; the rule: include/gsraster.h).
+    depths fp32 [V,H,W], viewmatrices fp32 [V,4,4] (row-vector convention), colors fp32 [V,3,H,W] (required iff `rgb` is
+    a tensor), view_weights fp32 [V] (> 0) or None.  The views are applied in order; splitting them over several calls
+    gives the same bits."""
+    V = depths.shape[0] if depths.dim() == 3 else -1
+    if V > TSDF_MAX_VIEWS:
+        raise ValueError(f"tsdf_integrate: at most {TSDF_MAX_VIEWS} views per call, got {V}")
+    X, Y, Z = _tsdf_planes("tsdf_integrate", dims, tsdf, weight, rgb)
+    dev = tsdf.device
+    if (rgb is None) != (colors is None):
+        raise ValueError("tsdf_integrate: `colors` goes with a volume that has colour planes, and only with one")
+    H, W = (int(s) for s in depths.shape[1:]) if V >= 0 else (0, 0)
+    for t, n, s in ((depths, "depths", (V, H, W)), (viewmatrices, "viewmatrices", (V, 4, 4)),
+                    (colors, "colors", (V, 3, H, W)), (view_weights, "view_weights", (V,))):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"diff_gaussian_rasterization: `{n}` must live on the gfx950 device (no CPU fallback)")
+        if t.dtype != torch.float32 or tuple(t.shape) != s or t.device != dev:
+            raise ValueError(f"tsdf_integrate: {n} must be float32 {list(s)} on {dev}, got {t.dtype} {list(t.shape)}")
+    if V == 0:
+        return
+    depths, viewmatrices = depths.detach().contiguous(), viewmatrices.detach().contiguous()
+    colors = None if colors is None else colors.detach().contiguous()
+    view_weights = None if view_weights is None else view_weights.detach().contiguous()
+    with _on(dev):
+        nbytes = lib.gsr_tsdf_integrate_bytes(V, W, H)
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        check(lib.gsr_tsdf_integrate(X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel_size),
+                                     float(trunc), _ptr(tsdf), _ptr(weight), _ptr(rgb), V, W, H, _ptr(viewmatrices),
+                                     float(tanfovx), float(tanfovy), _ptr(depths), _ptr(colors), _ptr(view_weights),
+                                     float(depth_trunc), float(near), _ptr(ws), nbytes, _stream()), "gsr_tsdf_integrate")
+
+
+def tsdf_extract(tsdf, weight, rgb, origin, voxel_size, dims, min_weight=0.0):
+    """Marching tetrahedra on the brick-major planes (gsr_tsdf_count, one read-back of the two totals, gsr_tsdf_emit) ->
+    (vertices fp32 [Nv,3], faces int32 [Nf,3], colors fp32 [Nv,3] or None when rgb is None).  Normals face positive
+    tsdf; the same volume gives the same bits on every run."""
+    X, Y, Z = _tsdf_planes("tsdf_extract", dims, tsdf, weight, rgb)
+    dev = tsdf.device
+    with _on(dev):
+        nbytes = lib.gsr_tsdf_extract_bytes(X, Y, Z)
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        rec = torch.empty(X * Y * Z, dtype=torch.int32, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        check(lib.gsr_tsdf_count(X, Y, Z, _ptr(tsdf), _ptr(weight), float(min_weight), _ptr(rec), _ptr(ws), nbytes,
+                                 _ptr(totals), _stream()), "gsr_tsdf_count")
+        nv, nt = totals.tolist()  # the only synchronisation: the totals size the outputs
+        if max(nv, nt) > 2 ** 31 - 1:
+            raise RuntimeError(f"tsdf_extract: {nv} vertices and {nt} triangles do not fit int32 indices; extract the "
+                               f"volume in parts or use a coarser one")
+        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        cols = torch.empty((nv, 3), dtype=torch.float32, device=dev) if rgb is not None else None
+        check(lib.gsr_tsdf_emit(X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel_size),
+                                _ptr(tsdf), _ptr(weight), _ptr(rgb), float(min_weight), _ptr(rec), _ptr(ws), nbytes, nv,
+                                nt, _ptr(verts), _ptr(faces), _ptr(cols), _stream()), "gsr_tsdf_emit")
+    return verts, faces, cols
 
 
 def group_rows(dest, num_groups):

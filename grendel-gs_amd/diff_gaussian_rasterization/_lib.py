@@ -91,6 +91,13 @@ SIGNATURES = {
     "gsr_vq_update": (c_int, [c_int] * 3 + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "gsr_vq_segment_sum": (c_int, [c_int] * 3 + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "gsr_vq_decode": (c_int, [c_int] * 3 + [c_void_p] * 4),
+    "gsr_tsdf_integrate_bytes": (c_size_t, [c_int] * 3),
+    "gsr_tsdf_integrate": (c_int, [c_int] * 3 + [c_float] * 5 + [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_float, c_float] +
+                           [c_void_p] * 3 + [c_float, c_float, c_void_p, c_size_t, c_void_p]),
+    "gsr_tsdf_extract_bytes": (c_size_t, [c_int] * 3),
+    "gsr_tsdf_count": (c_int, [c_int] * 3 + [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "gsr_tsdf_emit": (c_int, [c_int] * 3 + [c_float] * 4 + [c_void_p] * 3 + [c_float, c_void_p, c_void_p, c_size_t, c_int64,
+                                                                          c_int64] + [c_void_p] * 4),
     "gsr_densify_stats": (c_int, [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_group_rows_bytes": (c_size_t, [c_int64]),
     "gsr_group_rows": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

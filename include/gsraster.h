@@ -957,6 +957,49 @@ int gsr_vq_segment_sum(int P, int K, int D, const float *rows, const int32_t *id
                        size_t workspace_bytes, gsr_stream_t stream);
 int gsr_vq_decode(int P, int K, int D, const float *codebook, const int32_t *idx, float *out, gsr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * MESH EXTRACTION (tsdf.hip): fusion of depth maps into a truncated signed distance volume, and marching tetrahedra on
+ * it.  The reference has no mesh extraction, so there is NO reference call site: plain float64 numpy on the host is the
+ * arbiter (tests/tsdf_refs.py).  New symbols only: gsr_abi_version does not move.
+ * The volume: X x Y x Z voxels, each a multiple of 8, voxel (i,j,k) centred at (ox,oy,oz) + voxel_size (i,j,k), every
+ * plane fp32 BRICK-MAJOR [Z/8][Y/8][X/8][8][8][8] (tsdf, weight; rgb: three such planes one after the other, or NULL).
+ * Dims that are not positive multiples of 8, voxel_size <= 0, trunc <= 0, more than 16 views, a missing plane or a
+ * missing input: GSR_EINVAL before any device work.
+ *
+ * gsr_tsdf_integrate: the views in the order given, per voxel at p:  (x,y,z) = [p,1] viewmatrix (row-vector convention,
+ *   viewmatrices fp32 [views,16]);  z <= near skips the view;  px = ((x / (z tanfovx) + 1) width - 1) / 2, py alike;  the
+ *   nearest pixel, outside the image skips;  d = depths[view][py][px] (fp32 [views,height,width]), d <= 0 or
+ *   d > depth_trunc skips;  sdf = d - z outside [-trunc, trunc] skips;  then
+ *       tsdf = (tsdf w + (sdf / trunc) wv) / (w + wv),  rgb alike from colors fp32 [views,3,height,width],  w += wv
+ *   with wv = view_weights[view] (fp32 [views], > 0; NULL: 1).  One launch holds a voxel in registers across the views:
+ *   the planes are read once and a voxel is written only if a view updated it; no atomics; the result does not depend
+ *   on how a sequence of views is split into calls.  views == 0 returns 0 without a launch.  workspace:
+ *   gsr_tsdf_integrate_bytes(views, width, height) bytes of device memory, any content (the depth tiles of the brick
+ *   culling, which never changes a result); too small: GSR_ENOSPACE.
+ * gsr_tsdf_count: marching tetrahedra on the Kuhn split, first pass.  A cell is processed iff its 8 corners have
+ *   weight > 0 and >= min_weight; a corner is inside iff tsdf < 0.  records uint32 [X Y Z] (brick-major, FULLY
+ *   overwritten): bits 0..6 the voxel's owned edges (+x +y +z +xy +yz +xz +xyz) that carry a vertex, bits 7..18 and
+ *   19..31 the voxel's vertex and triangle offset inside its brick.  workspace: gsr_tsdf_extract_bytes(X, Y, Z) bytes
+ *   (brick totals and their exclusive scan, made by one workgroup); totals: two int64 in device memory, the number of
+ *   vertices and of triangles -- the caller reads them back to allocate gsr_tsdf_emit's outputs.
+ * gsr_tsdf_emit: second pass on the SAME planes, min_weight, records and workspace: vertices fp32 [num_vertices,3] at
+ *   p0 + (p1 - p0) t0 / (t0 - t1) on their edges, vertex_colors fp32 [num_vertices,3] interpolated likewise (or NULL),
+ *   faces int32 [num_triangles,3], normals towards positive tsdf.  The order is a pure function of the voxel order: the
+ *   same volume gives the same bits.  A total above 2^31 - 1: GSR_EINVAL (int32 indices).  Nothing is written past the
+ *   given totals. */
+size_t gsr_tsdf_integrate_bytes(int views, int width, int height);
+int gsr_tsdf_integrate(int X, int Y, int Z, float ox, float oy, float oz, float voxel_size, float trunc, float *tsdf,
+                       float *weight, float *rgb, int views, int width, int height, const float *viewmatrices,
+                       float tanfovx, float tanfovy, const float *depths, const float *colors, const float *view_weights,
+                       float depth_trunc, float near, void *workspace, size_t workspace_bytes, gsr_stream_t stream);
+size_t gsr_tsdf_extract_bytes(int X, int Y, int Z);
+int gsr_tsdf_count(int X, int Y, int Z, const float *tsdf, const float *weight, float min_weight, uint32_t *records,
+                   void *workspace, size_t workspace_bytes, int64_t *totals, gsr_stream_t stream);
+int gsr_tsdf_emit(int X, int Y, int Z, float ox, float oy, float oz, float voxel_size, const float *tsdf,
+                  const float *weight, const float *rgb, float min_weight, const uint32_t *records, const void *workspace,
+                  size_t workspace_bytes, int64_t num_vertices, int64_t num_triangles, float *vertices, int32_t *faces,
+                  float *vertex_colors, gsr_stream_t stream);
+
 /* N4: the per-iteration densification statistics in ONE launch (ABI 12) -- densification.py:13-25 of the reference, run after
  * every backward of the densification phase: for the rows with radii > 0
  *   max_radii2D = max(max_radii2D, radii);  xyz_gradient_accum += |grad[:, :2]|;  denom += 1
