@@ -33,7 +33,7 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "_C", "load_im
            "exchange_count", "exchange_pack", "exchange_pack_slab", "exchange_unpack", "zeros_async", "scatter_add_rows", "absgrad_rows", "densify_stats",
            "set_tie_order", "scatter_rows", "local_pixels", "GraphCapture", "capturing", "image_metrics", "metrics_from_sums",
            "bilagrid_slice", "bilagrid_tv", "vq_assign", "vq_update", "vq_segment_sum", "vq_decode",
-           "tsdf_integrate", "tsdf_extract"]
+           "tsdf_integrate", "tsdf_extract", "mesh_components", "mesh_filter"]
 
 BLOCK_X, BLOCK_Y, ONE_DIM_BLOCK_SIZE = 16, 16, 256
 
@@ -3127,6 +3127,82 @@ def tsdf_extract(tsdf, weight, rgb, origin, voxel_size, dims, min_weight=0.0):
                                 _ptr(tsdf), _ptr(weight), _ptr(rgb), float(min_weight), _ptr(rec), _ptr(ws), nbytes, nv,
                                 nt, _ptr(verts), _ptr(faces), _ptr(cols), _stream()), "gsr_tsdf_emit")
     return verts, faces, cols
+
+
+# ------------------------------------------------------------------ mesh cleaning (meshclean.hip; include/gsraster.h)
+MESH_CHUNK_FACES = 2048       # faces a workgroup of the union kernel takes (MC_CHUNK)
+MESH_WINDOW_VERTICES = 4096   # vertex indices it holds in LDS (MC_WINDOW)
+
+
+def _mesh_args(what, faces, num_vertices, vertices=None, colors=None):
+    """the checks gsr_mesh_* cannot make: int32 [F,3] device faces with every index in [0, V) (one aminmax and its
+    read-back), fp32 [V,3] positions / colours on the same device -> (faces contiguous, V, F)"""
+    for t, n in ((faces, "faces"), (vertices, "vertices"), (colors, "colors")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"diff_gaussian_rasterization: `{n}` must live on the gfx950 device (no CPU fallback)")
+    V = int(num_vertices)
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or V < 0:
+        raise ValueError(f"{what}: faces must be int32 [F,3] and num_vertices >= 0, got {faces.dtype} {list(faces.shape)}, {V}")
+    for t, n in ((vertices, "vertices"), (colors, "colors")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (V, 3) or t.device != faces.device):
+            raise ValueError(f"{what}: {n} must be float32 {[V, 3]} on {faces.device}, got {t.dtype} {list(t.shape)}")
+    F = faces.shape[0]
+    if F:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= V:
+            raise ValueError(f"{what}: face indices span [{lo}, {hi}], outside [0, {V})")
+    return faces.detach().contiguous(), V, F
+
+
+def _mesh_components(faces, V, F):
+    dev = faces.device
+    nbytes = lib.gsr_mesh_clean_bytes(V, F)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    labels = torch.empty(V, dtype=torch.int32, device=dev)
+    tri_count = torch.empty(V, dtype=torch.int32, device=dev)
+    num = torch.empty(1, dtype=torch.int64, device=dev)
+    check(lib.gsr_mesh_components(V, F, _ptr(faces) if F else None, _ptr(labels) if V else None,
+                                  _ptr(tri_count) if V else None, _ptr(num), _ptr(ws), nbytes, _stream()),
+          "gsr_mesh_components")
+    return labels, tri_count, ws, nbytes
+
+
+def mesh_components(faces, num_vertices):
+    """Connected components of an indexed triangle mesh (gsr_mesh_components; the definitions: include/gsraster.h) ->
+    (labels int32 [V]: the smallest vertex index of each vertex's component, tri_count int32 [V]: the triangles of the
+    component labelled l at index l, 0 elsewhere).  No read-back; the same bits on every run."""
+    faces, V, F = _mesh_args("mesh_components", faces, num_vertices)
+    with _on(faces.device):
+        labels, tri_count, _, _ = _mesh_components(faces, V, F)
+    return labels, tri_count
+
+
+def mesh_filter(vertices, faces, colors=None, keep_largest=0, min_triangles=0):
+    """Keep the components with at least max(min_triangles, 1) triangles that are among the `keep_largest` largest (by
+    triangle count, ties to the lowest label; 0: no limit), and compact: (vertices [Nv,3], faces [Nf,3] re-indexed,
+    colors [Nv,3] or None), order kept, rows copied bit for bit (gsr_mesh_components / _select, one read-back of the two
+    totals, gsr_mesh_compact)."""
+    if int(keep_largest) < 0 or int(min_triangles) < 0:
+        raise ValueError("mesh_filter: keep_largest and min_triangles must be >= 0")
+    faces, V, F = _mesh_args("mesh_filter", faces, vertices.shape[0], vertices, colors)
+    dev = faces.device
+    vertices = vertices.detach().contiguous()
+    colors = None if colors is None else colors.detach().contiguous()
+    with _on(dev):
+        nv = nt = 0
+        if V and F:
+            labels, tri_count, ws, nbytes = _mesh_components(faces, V, F)
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+            check(lib.gsr_mesh_select(V, F, _ptr(faces), _ptr(labels), _ptr(tri_count), int(keep_largest),
+                                      int(min_triangles), _ptr(ws), nbytes, _ptr(totals), _stream()), "gsr_mesh_select")
+            nv, nt = totals.tolist()  # the only synchronisation: the totals size the outputs
+        out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        out_f = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        out_c = torch.empty((nv, 3), dtype=torch.float32, device=dev) if colors is not None else None
+        if nv or nt:
+            check(lib.gsr_mesh_compact(V, F, _ptr(vertices), _ptr(colors), _ptr(faces), _ptr(labels), _ptr(ws), nbytes,
+                                       nv, nt, _ptr(out_v), _ptr(out_c), _ptr(out_f), _stream()), "gsr_mesh_compact")
+    return out_v, out_f, out_c
 
 
 def group_rows(dest, num_groups):

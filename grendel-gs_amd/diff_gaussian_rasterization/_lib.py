@@ -98,6 +98,11 @@ SIGNATURES = {
     "gsr_tsdf_count": (c_int, [c_int] * 3 + [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "gsr_tsdf_emit": (c_int, [c_int] * 3 + [c_float] * 4 + [c_void_p] * 3 + [c_float, c_void_p, c_void_p, c_size_t, c_int64,
                                                                           c_int64] + [c_void_p] * 4),
+    "gsr_mesh_clean_bytes": (c_size_t, [c_int64, c_int64]),
+    "gsr_mesh_components": (c_int, [c_int64, c_int64] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "gsr_mesh_select": (c_int, [c_int64, c_int64] + [c_void_p] * 3 + [c_int64, c_int64, c_void_p, c_size_t, c_void_p,
+                                                                       c_void_p]),
+    "gsr_mesh_compact": (c_int, [c_int64, c_int64] + [c_void_p] * 5 + [c_size_t, c_int64, c_int64] + [c_void_p] * 4),
     "gsr_densify_stats": (c_int, [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_group_rows_bytes": (c_size_t, [c_int64]),
     "gsr_group_rows": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -4,14 +4,15 @@ no mesh extraction: nothing here mirrors a reference call site.
 
 Both stages run on the HIP kernels of tsdf.hip (`tsdf_integrate`: one launch per 16 views with a voxel's state in
 registers; `tsdf_extract`: count, scan, emit), without atomics: the same views in the same order give the same bits,
-however they are batched.  World size 1 only; DESIGN.md 3.21.
+however they are batched.  World size 1 only; DESIGN.md 3.21.  `clean_mesh` / `extract(keep_largest=...)` then drop the
+small disconnected shells on the device (meshclean.hip).
 """
 import math
 
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization import TSDF_MAX_VIEWS, tsdf_extract, tsdf_integrate
+from diff_gaussian_rasterization import TSDF_MAX_VIEWS, mesh_filter, tsdf_extract, tsdf_integrate
 
 
 class TSDFVolume:
@@ -75,10 +76,23 @@ class TSDFVolume:
             dst.copy_(v.permute(*range(n), n, n + 2, n + 4, n + 1, n + 3, n + 5))
         return self
 
-    def extract(self, min_weight=0.0):
+    def extract(self, min_weight=0.0, keep_largest=0, min_triangles=0):
         """-> (vertices [Nv,3] fp32, faces [Nf,3] int32, colors [Nv,3] or None); a cell counts iff its 8 corners have a
-        positive weight that is at least min_weight; normals face positive tsdf (the free side)"""
-        return tsdf_extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel_size, self.dims, min_weight)
+        positive weight that is at least min_weight; normals face positive tsdf (the free side).  With keep_largest or
+        min_triangles above 0 the mesh then goes through mesh_filter (see clean_mesh); with both 0 it does not."""
+        mesh = tsdf_extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel_size, self.dims, min_weight)
+        if keep_largest == 0 and min_triangles == 0:
+            return mesh
+        return mesh_filter(*mesh, keep_largest=keep_largest, min_triangles=min_triangles)
+
+
+def clean_mesh(vertices, faces, colors=None, keep_largest=50, min_triangles=0):
+    """Drop the floaters of a fused mesh on the device (meshclean.hip): keep the connected components that
+    are among the `keep_largest` largest by triangle count (ties to the one with the lowest vertex index; 0: no limit;
+    the default is 2DGS's post_process_mesh(cluster_to_keep=50)) and have at least max(min_triangles, 1) triangles.
+    -> (vertices, faces re-indexed, colors or None), order kept, rows copied bit for bit.  Any indexed triangle mesh on
+    the device will do: vertices fp32 [V,3], faces int32 [F,3], colors fp32 [V,3]."""
+    return mesh_filter(vertices, faces, colors, keep_largest=keep_largest, min_triangles=min_triangles)
 
 
 def save_ply(path, vertices, faces, colors=None):

@@ -1000,6 +1000,48 @@ int gsr_tsdf_emit(int X, int Y, int Z, float ox, float oy, float oz, float voxel
                   size_t workspace_bytes, int64_t num_vertices, int64_t num_triangles, float *vertices, int32_t *faces,
                   float *vertex_colors, gsr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * MESH CLEANING (meshclean.hip): connected components of an indexed triangle mesh, their triangle counts, the selection
+ * of the largest ones and the stable compaction of what is kept -- Open3D's cluster_connected_triangles plus
+ * remove_triangles_by_mask / remove_unreferenced_vertices, as 2DGS's post_process_mesh uses them.  NO reference call
+ * site: a plain numpy union-find on the host is the arbiter (tests/meshclean_refs.py).  Integer work only, every result
+ * exact and the same bits on every run.  New symbols only: gsr_abi_version does not move.
+ * The mesh: V vertices, faces int32 [F,3] with every index in [0,V) (the CALLER's duty: the kernels do not test it),
+ * optionally vertices fp32 [V,3] and colors fp32 [V,3].  It need not come from gsr_tsdf_emit.
+ *   component: two vertices are connected if some triangle uses both; a component is a class of the transitive closure,
+ *     and a triangle belongs to the component of its vertices.  (On the manifold output of gsr_tsdf_emit this is the
+ *     partition Open3D's edge adjacency gives.)
+ *   label: the smallest vertex index of the component.  A vertex no triangle uses is its own component with 0 triangles.
+ *   selection: a component is kept iff tri_count >= max(min_triangles, 1) and, with keep_largest = k > 0, it is among the
+ *     first k in the order (tri_count descending, label ascending) taken over ALL components, before the min_triangles
+ *     test.  k = 0: no limit.
+ *   compaction: kept vertices and kept triangles keep their relative order, faces are re-indexed, positions and colours
+ *     are copied bit for bit; no unreferenced vertex survives.
+ * Negative sizes, V or F above 2^31 - 1, negative keep_largest / min_triangles, a missing pointer with a non-zero size:
+ * GSR_EINVAL; a workspace below gsr_mesh_clean_bytes(V, F) (0 for invalid sizes): GSR_ENOSPACE; both before any device
+ * work.  The three calls share ONE workspace, whose content carries from each to the next.
+ *
+ * gsr_mesh_components: labels int32 [V] and tri_count int32 [V] FULLY overwritten (tri_count[l] = the triangles of the
+ *   component labelled l, 0 where l is no label); num_components: one int64 in device memory.  Union-find with the
+ *   larger root hooked under the smaller by compare-and-swap: no wait on another workgroup, no host read-back.  F == 0:
+ *   every vertex its own component; V == 0: only num_components = 0 is written.
+ * gsr_mesh_select: after gsr_mesh_components on the same mesh and workspace.  totals: two int64 in device memory, the
+ *   kept vertices and kept triangles -- the caller reads them back to allocate gsr_mesh_compact's outputs.  V == 0 or
+ *   F == 0: both 0, nothing else is touched.
+ * gsr_mesh_compact: after gsr_mesh_select, with its totals.  out_vertices fp32 [num_vertices,3], out_colors alike (given
+ *   iff colors is), out_faces int32 [num_triangles,3].  Both totals 0: returns 0 without a launch.  Nothing is written
+ *   past the given totals. */
+size_t gsr_mesh_clean_bytes(int64_t V, int64_t F);
+int gsr_mesh_components(int64_t V, int64_t F, const int32_t *faces, int32_t *labels, int32_t *tri_count,
+                        int64_t *num_components, void *workspace, size_t workspace_bytes, gsr_stream_t stream);
+int gsr_mesh_select(int64_t V, int64_t F, const int32_t *faces, const int32_t *labels, const int32_t *tri_count,
+                    int64_t keep_largest, int64_t min_triangles, void *workspace, size_t workspace_bytes, int64_t *totals,
+                    gsr_stream_t stream);
+int gsr_mesh_compact(int64_t V, int64_t F, const float *vertices, const float *colors, const int32_t *faces,
+                     const int32_t *labels, const void *workspace, size_t workspace_bytes, int64_t num_vertices,
+                     int64_t num_triangles, float *out_vertices, float *out_colors, int32_t *out_faces,
+                     gsr_stream_t stream);
+
 /* N4: the per-iteration densification statistics in ONE launch (ABI 12) -- densification.py:13-25 of the reference, run after
  * every backward of the densification phase: for the rows with radii > 0
  *   max_radii2D = max(max_radii2D, radii);  xyz_gradient_accum += |grad[:, :2]|;  denom += 1
